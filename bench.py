@@ -24,6 +24,10 @@ collective); the final hit list is gathered to rank 0 once, after the timed regi
   python bench.py --config c4 --gpus 8              # BASELINE config 4: 16384 centres x 4096-pt, 16384/N per rank
                                                     # (strong scaling), planted emitters, gathered list checked on rank 0
   python bench.py --gpus 2 --dry-run                # CPU/gloo run of the launcher, sharding, gather and JSON plumbing
+  python bench.py --full                            # + the side legs, the final sweep's gather, the checks against the
+                                                    # oracle / closed form and the CPU baseline (a plain run times the
+                                                    # headline steps and nothing else)
+  python bench.py --dump-outputs DIR                # + what the last timed step computed, as DIR/<name>.npy
 """
 import argparse
 import json
@@ -41,7 +45,7 @@ FS = 8000000           # scan.cpp:92 default sample rate
 USE_BW = 0.75          # scan.cpp:65
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
@@ -103,7 +107,17 @@ def parse():
     ap.add_argument("--welch", action="store_true", help="BASELINE config C5: streaming 65536-pt 50%%-overlap Welch PSD")
     ap.add_argument("--welch-psd", type=int, default=32, help="PSDs per submit (K=16 segments each)")
     ap.add_argument("--welch-pinned", action="store_true", help="feed from pinned host memory through the captured hipGraph")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline steps: the records / overlap / hits-only / copy / configs legs, the final "
+                         "sweep's gather with its checks, the C5 check against the oracle, the CPU baseline (each still subject to its "
+                         "--no-* switch).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a fixed, seeded sample of the rows of a larger output)")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: the headline steps and nothing beside them
+        args.no_cpu_baseline = args.no_records_leg = args.no_overlap_leg = args.no_hits_only_leg = True
+        args.no_copy_ref = args.no_configs_leg = True
     if args.threshold is None:
         args.threshold = round(10.0 + 5.0 * np.log10((4096 if args.config == "c4" else args.n) / 4096.0), 2)
     return args
@@ -151,10 +165,47 @@ class ParityError(Exception):
     """A timed leg's output differs from the oracle's: the number is void and the run exits non-zero."""
 
 
+DUMP_BUDGET = 64 << 20   # bytes of array data that --dump-outputs writes in all
+DUMP_SEED = 20261016     # the sample of a larger output is the same in every run and every build
+
+
+def sample_rows(n_rows, row_bytes, budget):
+    """None when n_rows rows of row_bytes fit in `budget` bytes, else a fixed, seeded, sorted sample of row indices that does"""
+    k = max(1, budget // row_bytes)
+    if n_rows <= k:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, k, replace=False))
+
+
+def hit_arrays(h, budget=16 << 20):
+    """An ordered hit list as arrays of numbers (ids and frequencies as float64, dB as float32); a seeded sample of the
+    records when there are more than `budget` bytes of them"""
+    rows = sample_rows(len(h), 28, budget)
+    out = {}
+    if rows is not None:
+        h = h[rows]
+        out["hits_rows"] = rows.astype(np.float64)
+    out.update({"hits_seq_id": h["seq_id"].astype(np.float64), "hits_bin": h["i"].astype(np.float64),
+                "hits_power_db": h["power_db"].astype(np.float32), "hits_freq_hz": h["freq_hz"].astype(np.float64)})
+    return out
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float32 or float64, DUMP_BUDGET bytes at most in all"""
+    arrays = {k: np.ascontiguousarray(v, np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the budget of {DUMP_BUDGET}")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 WELCH_KINDS = {"cfloat": (4, 8, None), "int16": (3, 4, 2047.0), "int16p": (2, 4, 2047.0), "int8": (1, 2, 127.0)}   # SCN_KIND, B/sample, full scale
 
 
-def welch_leg(torch, dev, local_rank, seed, npsd, steps, warmup, rotate=0, pinned=False, sync=None, kind="cfloat", dc=False, check=None):
+def welch_leg(torch, dev, local_rank, seed, npsd, steps, warmup, rotate=0, pinned=False, sync=None, kind="cfloat", dc=False, check=None,
+              dump=None):
     """C5 steps on this GPU: a step = one submit of `npsd` PSDs = (npsd*16 + 1) * 32768 complex samples, device-resident (rotated
     over R streams past the Infinity Cache) or, with `pinned`, staged from pinned host memory through the captured hipGraph
     (PCIe-bound).  Returns (seconds for `steps` steps, new samples per step); sync() brackets the timed region (N > 1).
@@ -226,19 +277,24 @@ def welch_leg(torch, dev, local_rank, seed, npsd, steps, warmup, rotate=0, pinne
     if sync:
         sync()
     elapsed = time.perf_counter() - t0
+    if (check is not None or dump is not None) and steps > 0:
+        last = steps - 1
+        if pinned:
+            plan.submit(last & 1, npsd)       # the slot's pinned input is still the last step's: replay it for its PSDs
+            got = plan.collect(last & 1)
+        else:
+            got = outs[last % R].cpu().numpy()
+        if dump is not None:                  # --dump-outputs: the last timed step's PSDs (dB)
+            rows = sample_rows(npsd, N * 4, DUMP_BUDGET)
+            dump["psd_db"] = got if rows is None else got[rows]
+            if rows is not None:
+                dump["psd_db_rows"] = rows.astype(np.float64)
     if check is not None and steps > 0:
         # the LAST timed step's first and last PSD against the CPU oracle (K1 per delivery block, window, FFT, mean |X|^2, dB)
         from oracle import oracle as O
         from tests import tolerances as tol
 
-        last = steps - 1
-        if pinned:
-            plan.submit(last & 1, npsd)       # the slot's pinned input is still the last step's: replay it for its PSDs
-            got = plan.collect(last & 1)
-            raw = host_in[last & 1]
-        else:
-            got = outs[last % R].cpu().numpy()
-            raw = xs[last % R].cpu().numpy().view(np.uint8).reshape(-1)
+        raw = host_in[last & 1] if pinned else xs[last % R].cpu().numpy().view(np.uint8).reshape(-1)
         hop_b = (N // 2) * bps
         worst = 0.0
         try:
@@ -484,14 +540,17 @@ def welch_main(args):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=dev)
     npsd = args.welch_psd
-    check = {} if rank == 0 else None
+    check = {} if rank == 0 and args.full else None
+    dump = {} if rank == 0 and args.dump_outputs else None
     rc = 0
     try:
         elapsed, new_samples = welch_leg(torch, dev, local_rank, 5 + rank, npsd, args.steps, args.warmup, args.rotate, args.welch_pinned,
-                                         sync=dist.barrier if world > 1 else None, kind=args.kind, dc=args.dc, check=check)
+                                         sync=dist.barrier if world > 1 else None, kind=args.kind, dc=args.dc, check=check, dump=dump)
     except ParityError as e:
         print(f"bench.py: {e}", file=sys.stderr)
         sys.exit(3)
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
     if world > 1:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -1042,7 +1101,7 @@ def main():
         def collect(s):
             tc0 = time.perf_counter()
             if td:  # time-domain plans: max / min dB and the above-threshold flag per buffer (process.cpp:203-237)
-                pl.collect_time_domain(s)
+                state[("td", s)] = pl.collect_time_domain(s)
                 pending[s] = False
                 return
             if zero_copy:  # counts + trigger flags from scn_collect, the records read in place (scn_hits_view)
@@ -1069,6 +1128,7 @@ def main():
             pl.submit_device(s, graws[g][:a * shard], a * shard, None if table else fc_launch[:a * shard], seq_launch[:a * shard], sync_producer=False,
                              d_power_db=gouts[g][:a * shard] if spectrum else None, first_index=0 if table else None)
             pending[s] = True
+            state["last_launch"] = (g, a)
             state["acc"] = 0
 
         state["flush"] = flush
@@ -1145,6 +1205,7 @@ def main():
             best = chunk if best is None else min(best, chunk)
             if now - t_settle >= 3.0 or (now - t_settle >= args.settle and chunk <= 1.02 * best):
                 break
+    main_state["group"] = 0  # S > 1: the rotation from here on does not depend on how long the settling took
     for k in range(args.warmup):
         step(k)
     drain()
@@ -1174,6 +1235,36 @@ def main():
         tt = torch.tensor([elapsed, kernel_ms], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms = tt.tolist()
+
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before any later launch reuses the plan's slots or the output buffers:
+        # the dB spectra, the ordered hit records (read in place, scn_hits_view) or the time-domain max / min dB per buffer
+        L = main_state["launch"]
+        if S == 1:
+            slots = [j % main_depth for j in range(L - len(chunks), L)]
+            spec, lo_sweep = outs[(args.steps - 1) % R], None
+        else:   # the last launch holds the last step: its last sweep
+            g_last, a_last = main_state["last_launch"]
+            slots = [(L - 1) % main_depth]
+            spec = gouts[g_last][(a_last - 1) * shard:a_last * shard]
+            lo_sweep = int(seq_launch[(a_last - 1) * shard])
+        dump = {}
+        if td:
+            parts = [main_state[("td", s_)] for s_ in slots]
+            dump.update({"td_max_db": np.concatenate([p[0] for p in parts]), "td_min_db": np.concatenate([p[1] for p in parts]),
+                         "td_above": np.concatenate([p[2] for p in parts]).astype(np.float64)})
+        else:
+            if want_spec:
+                rows = sample_rows(shard, n * 4, 40 << 20)
+                dump["power_db"] = (spec if rows is None else spec[torch.from_numpy(rows).to(dev)]).cpu().numpy()
+                if rows is not None:
+                    dump["power_db_rows"] = rows.astype(np.float64)
+            if want_hit:
+                h = np.concatenate([plan.hits_view(s_).copy() for s_ in slots])
+                if lo_sweep is not None:
+                    h = h[(h["seq_id"] >= np.uint64(lo_sweep)) & (h["seq_id"] < np.uint64(lo_sweep + shard))]
+                dump.update(hit_arrays(h))
+        write_outputs(args.dump_outputs, dump)
 
     # the extra legs (reported beside the contract leg, never in `value`) time their own number of steps: a 20-step region is
     # mostly its own start and end, and these legs exist to show steady-state rates
@@ -1307,11 +1398,11 @@ def main():
         del src, dst
 
     # final sweep's hit list: collected with records, gathered to rank 0 by the C-ABI's scn_gather_hits
-    # (RCCL: count all-gather + grouped send/recv), not timed above
+    # (RCCL: count all-gather + grouped send/recv), not timed above; --full only
     tg0 = time.perf_counter()
     parts = []
     for j, (lo, hi) in enumerate(chunks):
-        if td or not want_hit:  # nothing to gather: a time-domain plan reports two floats per buffer, a spectrum-only plan no records
+        if td or not want_hit or not args.full:  # nothing to gather: a time-domain plan reports two floats per buffer, a spectrum-only plan no records
             parts.append(np.zeros(0, capi.HIT_DTYPE))
             continue
         plan.submit_device(j & 1, raw[lo:hi], hi - lo, fc[lo:hi], seq[lo:hi], sync_producer=False)
@@ -1320,7 +1411,7 @@ def main():
     gather_info = {"transport": "none (1 rank)"}
     all_hits, per_rank = hits, np.array([len(hits)])
     stuck = False
-    if use_dist:
+    if use_dist and args.full:
         # The gather runs on a helper thread with a deadline: this is the one place where ranks exchange data through a
         # library the launcher did not set up, and a rank that never arrives must cost the line one field, not the run.
         import threading
@@ -1477,10 +1568,11 @@ def main():
                 **{k: v for k, v in roofline_from_profile(prof, algo_bytes_per_launch).items() if k != "traffic"},
             },
             "threshold_db": args.threshold,
-            "hit_density": round(len(all_hits) / max(1, samples_per_step * 0.7485), 6),  # hits per EVALUATED bin (the mask of process.cpp:46-52 keeps 3066 of 4096)
-            "final_sweep_hits": int(len(all_hits)),
-            "final_sweep_collect_gather_ms": round(gather_ms, 3),
-            "gather": gather_info,
+            # hits per EVALUATED bin (the mask of process.cpp:46-52 keeps 3066 of 4096); the final sweep: --full only
+            "hit_density": round(len(all_hits) / max(1, samples_per_step * 0.7485), 6) if args.full else None,
+            "final_sweep_hits": int(len(all_hits)) if args.full else None,
+            "final_sweep_collect_gather_ms": round(gather_ms, 3) if args.full else None,
+            "gather": gather_info if args.full else None,
         }
         # the records legs again, from a C++ process on the system HIP runtime: the product's consumer (N = 1 only)
         if records is not None and world == 1 and not c4:  # (abi_bench generates the C2 recipe's input, not the C4 sweep)
@@ -1519,7 +1611,7 @@ def main():
                             "the FFT launch instead of on an SDMA engine",
                 }
         rc = 0
-        if c4:
+        if c4 and args.full:
             want = synth.c4_expected_hits(plan.window(), fc_all, centres, i0, n, FS, args.threshold)
             ok, worst = compare_hit_lists(all_hits, want)
             out["c4_check"] = {"expected_hits": int(len(want)), "gathered_hits": int(len(all_hits)), "match": ok,

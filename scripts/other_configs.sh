@@ -5,7 +5,7 @@ TAG=${1:-r03}
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/configs_$TAG.jsonl
 : > $OUT
-run() { python3 bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1 >> $OUT; }
+run() { python3 bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1 >> $OUT; }
 run --n 1024 --batch 32768
 run --n 2048 --batch 16384
 run --n 4096 --batch 8192

@@ -5,7 +5,7 @@ O=gpurun_out/r05e; mkdir -p $O
 timeout 1500 python3 -m pytest tests/test_dispatch_gpu.py -x -q -k "12000 or 12288 or 14400 or 15000 or 16000 or documented" > $O/pytest_dispatch.txt 2>&1; echo "dispatch rc $?"; tail -3 $O/pytest_dispatch.txt
 for cfg in "12000 2796" "12288 2730" "14400 2330" "15000 2236" "16000 2097"; do set -- $cfg
   for kind in cfloat int16; do
-    timeout 300 python3 bench.py --n $1 --batch $2 --kind $kind --no-cpu-baseline --no-records-leg --no-overlap-leg --no-copy-ref --steps 300 --warmup 20 2>/dev/null | tail -1 >> $O/bench.jsonl
+    timeout 300 python3 bench.py --full --n $1 --batch $2 --kind $kind --no-cpu-baseline --no-records-leg --no-overlap-leg --no-copy-ref --steps 300 --warmup 20 2>/dev/null | tail -1 >> $O/bench.jsonl
   done
 done
 python3 - <<'PY'

@@ -9,14 +9,14 @@ for rnd in 1 2; do
 for v in default pair8k pair8k2; do
   lib=$PWD/scanner_amd/variants/lib_$v.so; [ $v = default ] && lib=$PWD/scanner_amd/libscanner_hip.so
   for kind in int16 int8; do
-    SCN_LIB=$lib timeout 300 python3 bench.py --n 8192 --kind $kind --batch 4096 --no-cpu-baseline --no-records-leg --no-overlap-leg --no-copy-ref --steps 500 --warmup 20 2>/dev/null | tail -1 | \
+    SCN_LIB=$lib timeout 300 python3 bench.py --full --n 8192 --kind $kind --batch 4096 --no-cpu-baseline --no-records-leg --no-overlap-leg --no-copy-ref --steps 500 --warmup 20 2>/dev/null | tail -1 | \
       python3 -c "import json,sys; d=json.loads(sys.stdin.read()); h=d['hits_only']; print('$v $kind round $rnd: spectrum+hits %.2f us per launch (events), %.1f Gs/s; hits-only %.2f us, %.1f Gs/s' % (d['roofline']['kernel_avg_ms']*1e3, d['value']/1e3, h['kernel_avg_ms']*1e3, h['value']/1e3))"
   done
 done
 done 2>&1 | tee $O/ab.txt
 for v in default pair8k; do
   lib=$PWD/scanner_amd/variants/lib_$v.so; [ $v = default ] && lib=$PWD/scanner_amd/libscanner_hip.so
-  SCN_LIB=$lib rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$v -- python3 bench.py --n 8192 --kind int16 --batch 4096 --no-cpu-baseline --no-records-leg --no-overlap-leg --no-copy-ref --steps 500 --warmup 20 > /dev/null 2>&1
+  SCN_LIB=$lib rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$v -- python3 bench.py --full --n 8192 --kind int16 --batch 4096 --no-cpu-baseline --no-records-leg --no-overlap-leg --no-copy-ref --steps 500 --warmup 20 > /dev/null 2>&1
   grep -h "scn_fft8k" $O/trace_$v/*/*kernel_stats.csv | head -3 | tee -a $O/ab.txt
   rm -rf $O/trace_$v
 done

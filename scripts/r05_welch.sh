@@ -9,15 +9,15 @@ done
 for rnd in 1 2 3; do
 for v in welch_old default welch_nt; do
   lib=$PWD/scanner_amd/variants/lib_$v.so; [ $v = default ] && lib=$PWD/scanner_amd/libscanner_hip.so
-  SCN_LIB=$lib timeout 300 python3 bench.py --welch --welch-psd 32 --steps 300 --warmup 30 2>/dev/null | tail -1 | \
+  SCN_LIB=$lib timeout 300 python3 bench.py --full --welch --welch-psd 32 --steps 300 --warmup 30 2>/dev/null | tail -1 | \
     python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v round $rnd: %.1f us per step, %.1f Gs/s, frac %.4f' % (d['ms_per_step']*1e3, d['value']/1e3, d['roofline']['frac']))"
 done
 done 2>&1 | tee $O/ab.txt
 for v in welch_old default; do
   lib=$PWD/scanner_amd/variants/lib_$v.so; [ $v = default ] && lib=$PWD/scanner_amd/libscanner_hip.so
-  SCN_LIB=$lib rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$v -- python3 bench.py --welch --welch-psd 32 --steps 300 --warmup 30 > /dev/null 2>&1
+  SCN_LIB=$lib rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$v -- python3 bench.py --full --welch --welch-psd 32 --steps 300 --warmup 30 > /dev/null 2>&1
   echo "$v:"; grep -h "scn_welch" $O/trace_$v/*/*kernel_stats.csv | head -3 | tee -a $O/ab.txt
-  SCN_LIB=$lib rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "scn_welch" --kernel-trace --output-format csv -d $O/pmc_$v -- python3 bench.py --welch --welch-psd 32 --steps 40 --warmup 5 > /dev/null 2>&1
+  SCN_LIB=$lib rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "scn_welch" --kernel-trace --output-format csv -d $O/pmc_$v -- python3 bench.py --full --welch --welch-psd 32 --steps 40 --warmup 5 > /dev/null 2>&1
   python3 - $O/pmc_$v <<'PY' | tee -a gpurun_out/r05f/ab.txt
 import csv, glob, sys, collections
 acc = collections.defaultdict(list)

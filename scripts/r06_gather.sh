@@ -5,7 +5,7 @@ OUT=gpurun_out/r06_gather
 mkdir -p $OUT
 export TMPDIR=/tmp
 for c in 16384 2048; do
-  timeout 900 python bench.py --config c4 --centres $c --gather-every-sweep --no-cpu-baseline --no-overlap-leg --no-records-leg --no-hits-only-leg --no-copy-ref \
+  timeout 900 python bench.py --full --config c4 --centres $c --gather-every-sweep --no-cpu-baseline --no-overlap-leg --no-records-leg --no-hits-only-leg --no-copy-ref \
      2>>$OUT/bench.err > $OUT/bench_c4_${c}_gather.json
 done
 python - <<'PY' | tee $OUT/summary.txt

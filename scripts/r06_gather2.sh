@@ -1,7 +1,7 @@
 #!/bin/bash
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 OUT=gpurun_out/r06_gather2; mkdir -p $OUT
-run() { tag=$1; shift; timeout 600 python bench.py --config c4 --gather-every-sweep --steps 20 --warmup 5 --settle 0.05 --no-cpu-baseline --no-overlap-leg --no-records-leg --no-hits-only-leg --no-copy-ref "$@" 2>>$OUT/err.txt > $OUT/$tag.json
+run() { tag=$1; shift; timeout 600 python bench.py --full --config c4 --gather-every-sweep --steps 20 --warmup 5 --settle 0.05 --no-cpu-baseline --no-overlap-leg --no-records-leg --no-hits-only-leg --no-copy-ref "$@" 2>>$OUT/err.txt > $OUT/$tag.json
   python - "$OUT/$tag.json" "$tag" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read()); g = d["gather_every_sweep"]

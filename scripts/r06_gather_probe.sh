@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 TAG=${1:-probe}; C=${2:-2048}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r06_gather_probe/$TAG; mkdir -p $OUT
 TR=$(mktemp -d /tmp/gtl.XXXXXX); export TR OUT
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $TR -- python3 bench.py --config c4 --centres $C --gather-every-sweep --steps 20 --warmup 5 --settle 0.05 \
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $TR -- python3 bench.py --full --config c4 --centres $C --gather-every-sweep --steps 20 --warmup 5 --settle 0.05 \
    --no-cpu-baseline --no-overlap-leg --no-records-leg --no-hits-only-leg --no-copy-ref > $OUT/bench.json 2> $OUT/trace.log
 python3 - <<'PY'
 import csv, glob, os, json

@@ -5,7 +5,7 @@ OUT=gpurun_out/r06_small; mkdir -p $OUT
 ( time timeout 2400 python -m pytest tests -m gpu -q 2>&1 | grep -v "^Frequency " | tail -40 ) > $OUT/suite.log 2>&1
 tail -12 $OUT/suite.log
 for spec in "16 524288" "64 262144" "128 262144" "256 131072"; do set -- $spec
-  timeout 600 python bench.py --n $1 --batch $2 --no-cpu-baseline --no-overlap-leg --no-records-leg --no-copy-ref --no-configs-leg 2>>$OUT/err.txt > $OUT/n$1.json
+  timeout 600 python bench.py --full --n $1 --batch $2 --no-cpu-baseline --no-overlap-leg --no-records-leg --no-copy-ref --no-configs-leg 2>>$OUT/err.txt > $OUT/n$1.json
   python - $OUT/n$1.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read())

@@ -6,7 +6,7 @@ timeout 600 python -m pytest tests/test_parity_gpu.py tests/test_oracle_ref_dsp.
 for spec in "16 524288" "64 262144" "128 262144" "256 131072" "512 65536" "1024 32768"; do set -- $spec
   for v in product t17 t16 t15; do
     lib=""; [ $v != product ] && lib=scanner_amd/variants/lib_$v.so
-    SCN_LIB=$lib timeout 600 python bench.py --n $1 --batch $2 --no-cpu-baseline --no-overlap-leg --no-records-leg --no-copy-ref --no-configs-leg 2>>$OUT/err.txt > $OUT/n$1_$v.json
+    SCN_LIB=$lib timeout 600 python bench.py --full --n $1 --batch $2 --no-cpu-baseline --no-overlap-leg --no-records-leg --no-copy-ref --no-configs-leg 2>>$OUT/err.txt > $OUT/n$1_$v.json
     python - $OUT/n$1_$v.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read())

@@ -3,8 +3,8 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r06_welch_double; mkdir -p $O
 timeout 900 python3 -m pytest tests/test_welch.py -m gpu -q 2>&1 | grep -v "^Frequency " | tail -3
 timeout 900 python3 scripts/r06_welch_acc.py 2>&1 | grep -v amdgpu.ids | tee $O/welch_acc.txt
-for k in cfloat int16 int8; do timeout 300 python3 bench.py --welch --kind $k --steps 300 --warmup 20 2>/dev/null | tail -1; done > $O/welch.jsonl
-timeout 300 python3 bench.py --welch --welch-psd 8 --steps 300 --warmup 20 2>/dev/null | tail -1 >> $O/welch.jsonl
+for k in cfloat int16 int8; do timeout 300 python3 bench.py --full --welch --kind $k --steps 300 --warmup 20 2>/dev/null | tail -1; done > $O/welch.jsonl
+timeout 300 python3 bench.py --full --welch --welch-psd 8 --steps 300 --warmup 20 2>/dev/null | tail -1 >> $O/welch.jsonl
 python3 - <<'PY'
 import json
 for l in open("gpurun_out/r06_welch_double/welch.jsonl"):

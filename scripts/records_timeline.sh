@@ -8,7 +8,7 @@ TAG=${1:-run}; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/records_tl/$TAG; mkdir -p $OUT
 TR=$(mktemp -d /tmp/rtl.XXXXXX)   # a directory of this run's own: traces of earlier runs on the box must not merge into the timeline
 export TR OUT
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $TR -- python3 bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-overlap-leg --no-hits-only-leg --no-copy-ref "$@" > $OUT/bench.json 2> $OUT/trace.log
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $TR -- python3 bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --no-overlap-leg --no-hits-only-leg --no-copy-ref "$@" > $OUT/bench.json 2> $OUT/trace.log
 python3 - <<'PY'
 import csv, glob, os
 import numpy as np

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -16,11 +17,11 @@ CONTRACT = {"metric": str, "value": (int, float), "unit": str, "n_gpus": int, "s
             "config": dict}
 
 
-def run_bench(extra, env=None, batch=("--batch", "512")):
+def run_bench(extra, env=None, batch=("--batch", "512"), full=("--full",)):
     e = dict(os.environ)
     e.update(env or {})
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--settle",
-                          "0.05", *batch, "--cpu-seconds", "0.6"] + extra,
+                          "0.05", *batch, "--cpu-seconds", "0.6", *full] + extra,
                          capture_output=True, text=True, timeout=600, env=e, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -138,7 +139,7 @@ def test_c4_line_with_a_gather_every_sweep():
     """`bench.py --config c4 --gather-every-sweep`: the strong-scaling sweep with every launch's hit list gathered to rank 0 inside
     the timed region, beside the same sweeps without the gather (one rank here: the communicator has no peers)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c4", "--centres", "4096", "--steps", "4", "--warmup", "1",
-                          "--settle", "0.05", "--no-cpu-baseline", "--no-overlap-leg", "--no-records-leg", "--no-hits-only-leg", "--no-copy-ref",
+                          "--settle", "0.05", "--full", "--no-cpu-baseline", "--no-overlap-leg", "--no-records-leg", "--no-hits-only-leg", "--no-copy-ref",
                           "--gather-every-sweep"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip())
@@ -179,7 +180,7 @@ def test_welch_line_checks_its_own_output(extra, kind):
     """`bench.py --welch` (BASELINE C5): the first and last PSD of the last TIMED step are held to the oracle outside the timed
     region (a mismatch exits non-zero and prints no line), for float samples and for the integer wire formats, device-resident and
     through pinned memory + the captured hipGraph."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--welch", "--welch-psd", "8", "--steps", "4", "--warmup", "1"] + extra,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--welch", "--welch-psd", "8", "--steps", "4", "--warmup", "1", "--full"] + extra,
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip())
@@ -191,3 +192,34 @@ def test_welch_line_checks_its_own_output(extra, kind):
     r = d["roofline"]
     want = 8 * 16 * 32768 * {"cfloat": 8, "int16": 4, "int8": 2}[kind] + 8 * 65536 * 4     # bytes of NEW samples + the PSDs
     assert r["bound"] == "hbm" and r["algorithmic_bytes_per_launch"] == want and 0 < r["frac"] < 1
+
+
+def test_plain_line_times_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full a run sets up, warms up and times its steps, nothing beside them; --dump-outputs writes what the last
+    timed step computed, identical from run to run with the same arguments."""
+    runs = []
+    for r in range(2):
+        d = run_bench(["--dump-outputs", str(tmp_path / f"run{r}")], full=())
+        check_common(d)
+        for k in ("cpu_baseline", "overlap", "with_hit_records", "hits_only", "final_sweep_hits", "gather"):
+            assert d[k] is None, k
+        assert "configs" not in d and d["roofline"]["measured_copy_GBs"] is None
+        arrs = {f: np.load(tmp_path / f"run{r}" / f) for f in os.listdir(tmp_path / f"run{r}")}
+        assert {"power_db.npy", "hits_seq_id.npy", "hits_bin.npy", "hits_power_db.npy", "hits_freq_hz.npy"} <= set(arrs)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        runs.append(arrs)
+    a, b = runs
+    assert a["power_db.npy"].shape == (512, 4096) and len(a["hits_bin.npy"]) > 0
+    assert np.all(a["hits_seq_id.npy"] < 512) and np.all(np.diff(a["hits_seq_id.npy"]) >= 0)
+    assert a.keys() == b.keys() and all(np.array_equal(a[f], b[f]) for f in a)
+
+
+def test_plain_welch_line_dumps_its_psds(tmp_path):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--welch", "--welch-psd", "8", "--steps", "4", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads(out.stdout.strip())
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["c5_check"] is None
+    p = np.load(tmp_path / "psd_db.npy")
+    assert p.dtype == np.float32 and p.shape == (8, 65536) and np.isfinite(p).all()

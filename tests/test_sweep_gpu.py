@@ -136,7 +136,7 @@ def test_gather_from_the_slots_device_list_and_fetch_windows(torch_cuda, oracle_
 def test_bench_c4_line(torch_cuda):
     """bench.py --config c4 end to end (reduced table so the suite stays short; the full table is the test above)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c4", "--centres", "4096", "--steps", "4",
-                          "--warmup", "1", "--settle", "0.05", "--no-cpu-baseline", "--no-overlap-leg"],
+                          "--warmup", "1", "--settle", "0.05", "--full", "--no-cpu-baseline", "--no-overlap-leg"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip())
