@@ -150,8 +150,8 @@ enum {
   SCN_PATH_UNSUPPORTED = 0,
   SCN_PATH_FUSED = 1,     /* one launch, the FFT staged in LDS (the powers of two 16 ... 16384) */
   SCN_PATH_FOUR_STEP = 2, /* two launches around a work buffer (32768, 65536) */
-  SCN_PATH_STAGED = 3,    /* one launch per radix stage through HBM, in double.  No size reports it any more (until round 4:
-                             16 ... 128); the stages live on as the transform inside SCN_PATH_BLUESTEIN */
+  SCN_PATH_STAGED = 3,    /* never returned: kept so that the numbering stays (the staged radix passes are the transform
+                             inside SCN_PATH_BLUESTEIN) */
   SCN_PATH_BLUESTEIN = 4  /* the staged path around a chirp-z convolution (sizes that are not powers of two) */
 };
 SCN_API int scn_size_path(uint32_t n, uint32_t *path);

@@ -58,7 +58,7 @@ namespace {
   } while (0)
 
 struct Slot {
-  void *d_gen_work[2] = {nullptr, nullptr};  // staged sizes only: double[max_batch][fft_m][2], ping-pong between the stages
+  void *d_gen_work[2] = {nullptr, nullptr};  // scratch of the four-step and Bluestein paths (launch_transform)
   void *h_raw = nullptr;            // pinned staging, max_batch raw buffers
   void *d_raw = nullptr;            // device copy of the staging slot
   float *d_power = nullptr;         // [max_batch][N] dB spectra (plan-owned destination)
@@ -123,6 +123,18 @@ struct Slot {
 #endif
 constexpr uint32_t kTotalKernelFrom = SCN_TOTAL_KERNEL_FROM;
 
+// How a plan computes its spectrum: decided once, by path_of, and read by everything that depends on it
+enum class Path { TimeDomain, FusedPow2, FusedMixed, FourStep, Bluestein, Unsupported };
+
+Path path_of(uint32_t mode, uint32_t n) {
+  if (mode == SCN_MODE_TIME_DOMAIN) return Path::TimeDomain;
+  if (scn_fft_size_supported(n)) return Path::FusedPow2;    // scn_kernels.hip: the powers of two 16 ... 16384
+  if (scn_mixed_size_supported(n)) return Path::FusedMixed;  // scn_mixed.hip: the sizes 2^a 3^b 5^c of scn_mixed_plans.h
+  if (scn_big_size_supported(n)) return Path::FourStep;      // scn_big.hip: 32768, 65536
+  if (scn_bluestein_size_supported(n)) return Path::Bluestein;  // scn_generic.hip: every other size from 16 to 65535
+  return Path::Unsupported;
+}
+
 }  // namespace
 
 // Where the ordered hit list of a submit is built: behind the kernel on the list stream, overlapping the next launch (plus a
@@ -151,11 +163,9 @@ struct scn_plan {
   // kernel stores each count to pinned host memory as well (one 4-byte PCIe write per buffer; costs a 4096-point launch
   // ~4 us of completion latency, measured in round 1, and the 8192-point ones less than the late copy did).
   bool direct_counts = false;
-  bool mixed = false;    // a fused kernel of scn_mixed.hip: the sizes 2^a 3^b 5^c of scn_mixed_plans.h
-  bool generic = false;  // no fused kernel for this size: the staged path of scn_generic.hip
-  bool big = false;      // 65536 / 32768 points: the four-step pair of scn_big.hip
-  uint32_t fft_m = 0, log2m = 0;     // ... and its transform length: n for a power of two, >= 2n - 1 for Bluestein
-  double *d_twiddle64 = nullptr;     // [fft_m][2]: W_m^k in double (the staged path applies its tables in double)
+  Path path = Path::Unsupported;
+  uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
+  double *d_twiddle64 = nullptr;     // four-step: [256][2] W_256^k; Bluestein: [fft_m][2] W_m^k; in double
   double *d_table = nullptr;         // [table_count] the plan's frequency table (scn_plan_set_table), read by the compaction kernel
   uint32_t table_count = 0, table_cap = 0;  // entries in use / allocated
   double *d_chirp = nullptr;         // Bluestein: [n][2], w[i] = exp(-i pi i^2 / n)
@@ -257,6 +267,85 @@ void host_fft(std::vector<double> &re, std::vector<double> &im) {
         im[i] += xi;
       }
     }
+  }
+}
+
+// W_m^k = exp(-2 pi i k / m), k < m, as (re, im) pairs, evaluated in double
+template <class T>
+std::vector<T> twiddles(uint32_t m) {
+  std::vector<T> tw(2 * (size_t)m);
+  const double pi = 3.14159265358979323846;
+  for (uint32_t k = 0; k < m; k++) {
+    const double a = -2.0 * pi * (double)k / (double)m;
+    tw[2 * k] = (T)std::cos(a);
+    tw[2 * k + 1] = (T)std::sin(a);
+  }
+  return tw;
+}
+
+template <class D, class T>
+hipError_t upload(D **dst, const std::vector<T> &v) {
+  hipError_t e = hipMalloc(dst, sizeof(T) * v.size());
+  return e != hipSuccess ? e : hipMemcpy(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+}
+
+// The window and the tables the plan's path reads (a time-domain plan reads none)
+hipError_t build_tables(scn_plan *p) {
+  const uint32_t n = p->d.n;
+  hipError_t e;
+  if (p->path == Path::TimeDomain) return hipSuccess;
+  if ((e = upload(&p->d_window, p->h_window)) != hipSuccess) return e;
+  switch (p->path) {
+    case Path::FusedPow2:
+    case Path::FusedMixed: {
+      const std::vector<float> tw = twiddles<float>(n);
+      // the same values, regrouped per thread of the fused kernel: entry (p-1, t) = W_n^(t p)
+      uint32_t rows, threads;
+      if (p->path == Path::FusedMixed) scn_mixed_layout(n, &rows, &threads);
+      else scn_tw1_layout(n, &rows, &threads);
+      std::vector<float> tw1(2 * (size_t)rows * threads);
+      for (uint32_t pp = 1; pp <= rows; pp++)
+        for (uint32_t t = 0; t < threads; t++) {
+          const uint32_t m = (uint32_t)(((uint64_t)t * pp) % n);
+          tw1[2 * ((size_t)(pp - 1) * threads + t)] = tw[2 * m];
+          tw1[2 * ((size_t)(pp - 1) * threads + t) + 1] = tw[2 * m + 1];
+        }
+      if ((e = upload(&p->d_twiddle, tw)) != hipSuccess) return e;
+      return upload(&p->d_tw1_table, tw1);
+    }
+    case Path::FourStep:  // W_n in float; W_256 in double: the row transform of scn_big.hip
+      if ((e = upload(&p->d_twiddle, twiddles<float>(n))) != hipSuccess) return e;
+      return upload(&p->d_twiddle64, twiddles<double>(256));
+    case Path::Bluestein: {
+      // the transform length m: the power of two >= 2n - 1; w[i] = exp(-i pi i^2 / n) with i^2 reduced mod 2n in integers; the
+      // filter b[k] = conj(w[|k|]) laid out cyclically over m points, transformed here in double (m <= 131072) and scaled by 1/m
+      // (the second device transform is an inverse one up to conjugations, which needs that factor)
+      for (p->log2m = 0; (1u << p->log2m) < 2u * n - 1u; p->log2m++) {
+      }
+      const uint32_t m = p->fft_m = 1u << p->log2m;
+      const double pi = 3.14159265358979323846;
+      std::vector<double> chirp(2 * (size_t)n), br(m, 0.0), bi(m, 0.0);
+      for (uint32_t i = 0; i < n; i++) {
+        const double a = -pi * (double)(((uint64_t)i * i) % (2ull * n)) / (double)n;
+        chirp[2 * i] = std::cos(a);
+        chirp[2 * i + 1] = std::sin(a);
+        br[i] = std::cos(a);
+        bi[i] = -std::sin(a);
+        if (i) {
+          br[m - i] = br[i];
+          bi[m - i] = bi[i];
+        }
+      }
+      host_fft(br, bi);
+      std::vector<double> bfilter(2 * (size_t)m);
+      for (uint32_t k = 0; k < m; k++) {
+        bfilter[2 * k] = br[k] / (double)m;
+        bfilter[2 * k + 1] = bi[k] / (double)m;
+      }
+      if ((e = upload(&p->d_twiddle64, twiddles<double>(m))) != hipSuccess || (e = upload(&p->d_chirp, chirp)) != hipSuccess) return e;
+      return upload(&p->d_bfilter, bfilter);
+    }
+    default: return hipErrorInvalidValue;
   }
 }
 
@@ -389,6 +478,86 @@ int fetch_list(scn_plan *p, Slot &s, uint32_t count) {
   return SCN_OK;
 }
 
+// The input, the window and the K4 / K5 epilogue: the fields every transform's argument struct carries under the same names
+template <class A>
+void set_common_args(A &a, const scn_plan *p, const Slot &s, const void *d_raw, uint32_t nb, float *d_power) {
+  a.raw = d_raw;
+  a.window = p->d_window;
+  a.power_db = d_power;
+  a.n_buffers = nb;
+  a.scale = p->scale;
+  a.threshold = p->d.threshold;
+  a.dc_ignore = p->d.dc_ignore_bins;
+  a.i_lo = p->i_lo;
+  a.i_hi = p->i_hi;
+  a.hits = s.d_hits[s.gen];
+  a.hit_region = p->hit_region;
+  a.per_buffer_hits = s.d_buf_hits[s.gen];
+}
+
+// The transform of a submit on the slot's stream: the only code that knows which launcher and which argument struct a path
+// uses.  host_hits: where a fused kernel stores the counts as well (or nullptr); stop: an event a fused kernel's own
+// dispatch packet completes (or nullptr)
+int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float *d_power, uint32_t *host_hits, hipEvent_t stop) {
+  const uint32_t n = p->d.n;
+  const int kind = (int)p->d.sample_kind;
+  const bool hits = (p->d.flags & SCN_OUT_HITS) != 0, dc = p->d.correct_dc != 0;
+  switch (p->path) {
+    case Path::FusedPow2:
+    case Path::FusedMixed: {
+      ScnFftArgs a;
+      memset(&a, 0, sizeof(a));
+      set_common_args(a, p, s, d_raw, nb, d_power);
+      a.twiddle = p->d_twiddle;
+      a.tw1_table = p->d_tw1_table;
+      a.p_lo = scn_hit_prefilter(p->d.threshold);
+      a.host_hits = host_hits;
+      a.work_counter = s.d_work_counter;
+      for (uint32_t x = 0; x < 8; x++) a.work_base[x] = s.work_base[x];
+      if (p->path == Path::FusedMixed) {
+        SCN_HIP(scn_launch_mixed(n, kind, dc, hits, d_power != nullptr, a, p->num_cus, s.stream, stop));
+        return SCN_OK;
+      }
+      // (a hits-only plan handed a caller's spectrum destination runs the full kernel)
+      SCN_HIP(scn_launch_fft(n, kind, dc, hits, d_power != nullptr, a, p->num_cus, s.stream, stop));
+      if (scn_uses_queue(kind, n))
+        for (uint32_t x = 0; x < 8; x++) s.work_base[x] += scn_work_shard_count(nb, x);  // what this launch adds (wrapping, like the device side)
+      return SCN_OK;
+    }
+    case Path::FourStep: {
+      if (nb && !s.d_gen_work[0]) SCN_HIP(hipMalloc(&s.d_gen_work[0], sizeof(float) * 2 * (size_t)n * p->d.max_batch));
+      ScnBigArgs a;
+      set_common_args(a, p, s, d_raw, nb, d_power);
+      a.twiddle = p->d_twiddle;
+      a.work = s.d_gen_work[0];
+      a.tw256 = reinterpret_cast<const double2_scn *>(p->d_twiddle64);
+      a.p_lo = scn_hit_prefilter(p->d.threshold);
+      const bool int_dc = dc && p->d.sample_kind != SCN_KIND_FLOAT_COMPLEX;
+      if (nb && int_dc && !s.d_gen_work[1]) SCN_HIP(hipMalloc(&s.d_gen_work[1], sizeof(int) * 2 * (size_t)p->d.max_batch));
+      a.dc_sums = int_dc ? static_cast<int *>(s.d_gen_work[1]) : nullptr;
+      SCN_HIP(scn_launch_big(n, kind, int_dc, hits, d_power != nullptr, a, p->num_cus, s.stream));
+      return SCN_OK;
+    }
+    case Path::Bluestein: {
+      for (int g = 0; g < 2 && nb; g++)
+        if (!s.d_gen_work[g]) SCN_HIP(hipMalloc(&s.d_gen_work[g], 2u * sizeof(double) * (size_t)p->fft_m * p->d.max_batch));
+      ScnGenericArgs a;
+      set_common_args(a, p, s, d_raw, nb, d_power);
+      a.twiddle = p->d_twiddle64;
+      a.work0 = s.d_gen_work[0];
+      a.work1 = s.d_gen_work[1];
+      a.n = n;
+      a.m = p->fft_m;
+      a.log2m = p->log2m;
+      a.chirp = p->d_chirp;
+      a.bfilter = p->d_bfilter;
+      SCN_HIP(scn_launch_generic(kind, dc, hits, a, p->num_cus, s.stream));
+      return SCN_OK;
+    }
+    default: return fail(SCN_E_STATE, "the plan has no transform");
+  }
+}
+
 // fc == nullptr: the buffers carry entries table_first, table_first + 1, ... (wrapping) of the plan's frequency table
 int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const double *fc, const uint64_t *seq,
                   float *d_power, uint32_t table_first = 0) {
@@ -446,23 +615,6 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
     if (seq) memcpy(h_seq, seq, sizeof(uint64_t) * nb);
   }
 
-  ScnFftArgs a;
-  memset(&a, 0, sizeof(a));
-  a.raw = d_raw;
-  a.window = p->d_window;
-  a.twiddle = p->d_twiddle;
-  a.tw1_table = p->d_tw1_table;
-  a.power_db = d_power;
-  a.n_buffers = nb;
-  a.scale = p->scale;
-  a.threshold = p->d.threshold;
-  a.p_lo = scn_hit_prefilter(p->d.threshold);
-  a.dc_ignore = p->d.dc_ignore_bins;
-  a.i_lo = p->i_lo;
-  a.i_hi = p->i_hi;
-  a.hits = s.d_hits[s.gen];
-  a.hit_region = p->hit_region;
-  a.per_buffer_hits = s.d_buf_hits[s.gen];
   // The per-buffer counts reach the host either by a DMA behind the kernel or by the kernel's own stores to pinned memory.
   // Both have a price (profiles/r04_experiments.md section 10).  A store over PCIe holds its wave's in-order memory returns up:
   // ~0.4 ns per buffer on the launch (8192 buffers: 73.5 -> 76.7 us; 32768 1024-point buffers: 75 -> 96 us).  A DMA that waits
@@ -472,10 +624,8 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   // on that stream against 73 us of FFT; records read in place, three in flight: 373 .. 403 -> 429 Gsamples/s).  So the kernel
   // stores the counts itself when the launch has few buffers or the list follows eagerly, and a DMA carries them otherwise.
   const bool eager = hits && nb && (p->records_wanted || p->device_list_wanted);
-  const bool direct = !p->generic && !p->big && (p->direct_counts || nb <= 4096u || eager);
-  a.host_hits = (hits && direct) ? s.h_buf_hits : nullptr;
-  a.work_counter = s.d_work_counter;
-  for (uint32_t x = 0; x < 8; x++) a.work_base[x] = s.work_base[x];
+  const bool fused = p->path == Path::FusedPow2 || p->path == Path::FusedMixed;
+  const bool direct = fused && (p->direct_counts || nb <= 4096u || eager);
   // What follows the kernel: the counts (a DMA on the d2h stream: needs no CU -- or nothing, when the kernel stores them to
   // pinned memory itself) and, when the caller is known to want records, the ordered list (two small kernels + a DMA on
   // the list stream, beside the next launch).  With overlapped slots both follow the kernel on the slot's own stream --
@@ -495,63 +645,9 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   // 16.8 M samples 44 -> 46..58 and 8.4 M 31 -> 29..56 (erratic: short kernels that carry an event get serialised).
   const bool after_is_done = cnt == s.stream && !s.own_stream;  // direct counts on the plan's stream
   hipEvent_t after = (!nb || s.own_stream || total_path) ? nullptr : !hits ? s.done : after_is_done ? s.done : s.kernel_done;
-  const bool in_packet = after && !p->generic && !p->big && (uint64_t)nb * n >= (1u << 25);
-  if (p->big) {
-    if (nb && !s.d_gen_work[0]) SCN_HIP(hipMalloc(&s.d_gen_work[0], sizeof(float) * 2 * (size_t)n * p->d.max_batch));
-    ScnBigArgs ba;
-    ba.raw = d_raw;
-    ba.window = p->d_window;
-    ba.twiddle = p->d_twiddle;
-    ba.work = s.d_gen_work[0];
-    ba.tw256 = reinterpret_cast<const double2_scn *>(p->d_twiddle64);
-    ba.power_db = d_power;
-    ba.n_buffers = nb;
-    ba.scale = p->scale;
-    ba.threshold = p->d.threshold;
-    ba.p_lo = a.p_lo;
-    ba.dc_ignore = p->d.dc_ignore_bins;
-    ba.i_lo = p->i_lo;
-    ba.i_hi = p->i_hi;
-    ba.hits = a.hits;
-    ba.hit_region = p->hit_region;
-    ba.per_buffer_hits = a.per_buffer_hits;
-    const bool dc = p->d.correct_dc && p->d.sample_kind != SCN_KIND_FLOAT_COMPLEX;
-    if (nb && dc && !s.d_gen_work[1]) SCN_HIP(hipMalloc(&s.d_gen_work[1], sizeof(int) * 2 * (size_t)p->d.max_batch));
-    ba.dc_sums = dc ? static_cast<int *>(s.d_gen_work[1]) : nullptr;
-    SCN_HIP(scn_launch_big(n, (int)p->d.sample_kind, dc, hits, d_power != nullptr, ba, p->num_cus, s.stream));
-  } else if (p->generic) {
-    for (int g = 0; g < 2 && nb; g++)
-      if (!s.d_gen_work[g]) SCN_HIP(hipMalloc(&s.d_gen_work[g], 2u * sizeof(double) * (size_t)p->fft_m * p->d.max_batch));
-    ScnGenericArgs ga;
-    ga.raw = d_raw;
-    ga.window = p->d_window;
-    ga.twiddle = p->d_twiddle64;
-    ga.work0 = s.d_gen_work[0];
-    ga.work1 = s.d_gen_work[1];
-    ga.power_db = d_power;
-    ga.n = n;
-    ga.m = p->fft_m;
-    ga.log2m = p->log2m;
-    ga.chirp = p->d_chirp;
-    ga.bfilter = p->d_bfilter;
-    ga.n_buffers = nb;
-    ga.scale = p->scale;
-    ga.threshold = p->d.threshold;
-    ga.dc_ignore = p->d.dc_ignore_bins;
-    ga.i_lo = p->i_lo;
-    ga.i_hi = p->i_hi;
-    ga.hits = a.hits;
-    ga.hit_region = p->hit_region;
-    ga.per_buffer_hits = a.per_buffer_hits;
-    SCN_HIP(scn_launch_generic((int)p->d.sample_kind, p->d.correct_dc != 0, hits, ga, p->num_cus, s.stream));
-  } else if (p->mixed) {
-    SCN_HIP(scn_launch_mixed(n, (int)p->d.sample_kind, p->d.correct_dc != 0, hits, d_power != nullptr, a, p->num_cus, s.stream, in_packet ? after : nullptr));
-  } else {
-    // (a hits-only plan handed a caller's spectrum destination runs the full kernel)
-    SCN_HIP(scn_launch_fft(n, (int)p->d.sample_kind, p->d.correct_dc != 0, hits, d_power != nullptr, a, p->num_cus, s.stream, in_packet ? after : nullptr));
-  }
-  if (!p->generic && !p->big && !p->mixed && scn_uses_queue((int)p->d.sample_kind, p->d.n))
-    for (uint32_t x = 0; x < 8; x++) s.work_base[x] += scn_work_shard_count(nb, x);  // what this launch adds (wrapping, like the device side)
+  const bool in_packet = after && fused && (uint64_t)nb * n >= (1u << 25);
+  st = launch_transform(p, s, d_raw, nb, d_power, (hits && direct) ? s.h_buf_hits : nullptr, in_packet ? after : nullptr);
+  if (st) return st;
   if (hits && nb) {
     if (after && !in_packet) SCN_HIP(hipEventRecord(after, s.stream));
     if (cnt != s.stream) SCN_HIP(hipStreamWaitEvent(cnt, after, 0));
@@ -645,11 +741,13 @@ int scn_device_count(int *count) {
 
 int scn_size_path(uint32_t n, uint32_t *path) {
   if (!path) return fail(SCN_E_INVALID, "null argument");
-  *path = (scn_fft_size_supported(n) || scn_mixed_size_supported(n)) ? SCN_PATH_FUSED
-          : scn_big_size_supported(n) ? SCN_PATH_FOUR_STEP
-          : scn_generic_size_supported(n) ? SCN_PATH_STAGED
-          : scn_bluestein_size_supported(n) ? SCN_PATH_BLUESTEIN
-                                            : SCN_PATH_UNSUPPORTED;
+  switch (path_of(SCN_MODE_FREQUENCY_DOMAIN, n)) {
+    case Path::FusedPow2:
+    case Path::FusedMixed: *path = SCN_PATH_FUSED; break;
+    case Path::FourStep: *path = SCN_PATH_FOUR_STEP; break;
+    case Path::Bluestein: *path = SCN_PATH_BLUESTEIN; break;
+    default: *path = SCN_PATH_UNSUPPORTED;
+  }
   return SCN_OK;
 }
 
@@ -675,9 +773,8 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   if (d.window_type < SCN_WIN_HANN || d.window_type > SCN_WIN_HAMMING) return fail(SCN_E_INVALID, "unsupported window_type %u", d.window_type);
   if (d.mode != SCN_MODE_FREQUENCY_DOMAIN && d.mode != SCN_MODE_TIME_DOMAIN)
     return fail(SCN_E_INVALID, "unsupported mode %u", d.mode);
-  if (d.mode == SCN_MODE_FREQUENCY_DOMAIN && !scn_fft_size_supported(d.n) && !scn_mixed_size_supported(d.n) && !scn_generic_size_supported(d.n) &&
-      !scn_bluestein_size_supported(d.n))
-    return fail(SCN_E_INVALID, "unsupported FFT size %u (16 to 65536)", d.n);
+  const Path path = path_of(d.mode, d.n);
+  if (path == Path::Unsupported) return fail(SCN_E_INVALID, "unsupported FFT size %u (16 to 65536)", d.n);
   if (d.n == 0 || d.n > (1u << 24)) return fail(SCN_E_INVALID, "bad sample count %u", d.n);
   if (d.sample_rate == 0) return fail(SCN_E_INVALID, "sample_rate must be > 0");
 
@@ -689,6 +786,7 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   scn_plan *p = new (std::nothrow) scn_plan();
   if (!p) return fail(SCN_E_NOMEM, "out of host memory");
   p->d = d;
+  p->path = path;
   p->buf_bytes = bytes_per_sample(d.sample_kind) * d.n;
   p->scale = convert_scale(d.sample_kind, d.enob);
   // process.cpp:85 m_useWindow = uint32_t(useBandWidth * numSamples / 2.0); :51 bounds in uint32
@@ -696,10 +794,11 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   p->i_lo = d.n / 2 - use_window;
   p->i_hi = d.n / 2 + use_window;
   {  // the mask exactly as the kernels apply it (process.cpp:46-52, uint32 arithmetic)
+    const struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {d.dc_ignore_bins, p->i_lo, p->i_hi};
     uint32_t kept = 0;
     for (uint32_t i = 0; i < d.n; i++) {
       const uint32_t j = (i + d.n / 2) % d.n;
-      kept += !(j < d.dc_ignore_bins || (d.n - j) < d.dc_ignore_bins) && !(i < p->i_lo || i > p->i_hi);
+      kept += scn_bin_evaluated(j, i, d.n, mask);
     }
     p->hit_region = std::max<uint32_t>(kept, 1u);
   }
@@ -715,10 +814,8 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   }
     SCN_TRY(hipGetDeviceProperties(&prop, d.device_id));
     p->num_cus = prop.multiProcessorCount;
-    p->big = d.mode == SCN_MODE_FREQUENCY_DOMAIN && scn_big_size_supported(d.n);
-    p->mixed = d.mode == SCN_MODE_FREQUENCY_DOMAIN && scn_mixed_size_supported(d.n);  // a fused kernel of scn_mixed.hip (2^a 3^b 5^c)
-    p->generic = d.mode == SCN_MODE_FREQUENCY_DOMAIN && !scn_fft_size_supported(d.n) && !p->big && !p->mixed;
-    p->direct_counts = d.n >= 8192 && !p->generic && !p->big;  // (the fused kernels from 8192 points up store the counts to pinned memory themselves)
+    // (the fused kernels from 8192 points up store the counts to pinned memory themselves)
+    p->direct_counts = d.n >= 8192 && (path == Path::FusedPow2 || path == Path::FusedMixed);
     SCN_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     SCN_TRY(hipStreamCreateWithFlags(&p->h2d_stream, hipStreamNonBlocking));
     SCN_TRY(hipStreamCreateWithFlags(&p->d2h_stream, hipStreamNonBlocking));
@@ -738,92 +835,11 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
         if (k == 1) SCN_TRY(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
       }
     }
-    // the transform length: the buffer length, except for sizes that are not powers of two (Bluestein, scn_generic.hip)
-    const bool blue = p->generic && (d.n & (d.n - 1u)) != 0u;
-    uint32_t tn = d.n;
-    if (blue)
-      for (tn = 1; tn < 2u * d.n - 1u; tn <<= 1) {
-      }
-    p->fft_m = tn;
-    for (p->log2m = 0; (1u << p->log2m) < tn; p->log2m++) {
-    }
-    SCN_TRY(hipMalloc(&p->d_window, sizeof(float) * d.n));
-    SCN_TRY(hipMalloc(&p->d_twiddle, sizeof(scn_v2f) * tn));
-    std::vector<float> tw(2 * (size_t)tn);
-    const double pi = 3.14159265358979323846;
-    for (uint32_t m = 0; m < tn; m++) {
-      double a = -2.0 * pi * (double)m / (double)tn;
-      tw[2 * m] = (float)std::cos(a);
-      tw[2 * m + 1] = (float)std::sin(a);
-    }
-    SCN_TRY(hipMemcpyAsync(p->d_window, p->h_window.data(), sizeof(float) * d.n, hipMemcpyHostToDevice, p->stream));
-    SCN_TRY(hipMemcpyAsync(p->d_twiddle, tw.data(), sizeof(float) * 2 * tn, hipMemcpyHostToDevice, p->stream));
-    if (p->big) {  // W_256^m in double: the row transform of scn_big.hip
-      std::vector<double> tw256(2 * 256);
-      for (uint32_t m = 0; m < 256; m++) {
-        const double a = -2.0 * pi * (double)m / 256.0;
-        tw256[2 * m] = std::cos(a);
-        tw256[2 * m + 1] = std::sin(a);
-      }
-      SCN_TRY(hipMalloc(&p->d_twiddle64, sizeof(double) * tw256.size()));
-      SCN_TRY(hipMemcpy(p->d_twiddle64, tw256.data(), sizeof(double) * tw256.size(), hipMemcpyHostToDevice));
-    }
-    if (p->generic) {
-      std::vector<double> tw64(2 * (size_t)tn);
-      for (uint32_t m = 0; m < tn; m++) {
-        const double a = -2.0 * pi * (double)m / (double)tn;
-        tw64[2 * m] = std::cos(a);
-        tw64[2 * m + 1] = std::sin(a);
-      }
-      SCN_TRY(hipMalloc(&p->d_twiddle64, sizeof(double) * tw64.size()));
-      SCN_TRY(hipMemcpy(p->d_twiddle64, tw64.data(), sizeof(double) * tw64.size(), hipMemcpyHostToDevice));
-    }
-    std::vector<double> chirp, bfilter;
-    if (blue) {
-      // w[i] = exp(-i pi i^2 / n) with i^2 reduced mod 2n in integers; the filter b[k] = conj(w[|k|]) laid out cyclically over
-      // tn points, transformed here in double (tn <= 65536) and scaled by 1/tn (the second device transform is an inverse
-      // one up to conjugations, which needs that factor)
-      chirp.resize(2 * (size_t)d.n);
-      std::vector<double> br(tn, 0.0), bi(tn, 0.0);
-      for (uint32_t i = 0; i < d.n; i++) {
-        const double a = -pi * (double)(((uint64_t)i * i) % (2ull * d.n)) / (double)d.n;
-        chirp[2 * i] = std::cos(a);
-        chirp[2 * i + 1] = std::sin(a);
-        br[i] = std::cos(a);
-        bi[i] = -std::sin(a);
-        if (i) {
-          br[tn - i] = br[i];
-          bi[tn - i] = bi[i];
-        }
-      }
-      host_fft(br, bi);
-      bfilter.resize(2 * (size_t)tn);
-      for (uint32_t k = 0; k < tn; k++) {
-        bfilter[2 * k] = br[k] / (double)tn;
-        bfilter[2 * k + 1] = bi[k] / (double)tn;
-      }
-      SCN_TRY(hipMalloc(&p->d_chirp, sizeof(double) * chirp.size()));
-      SCN_TRY(hipMalloc(&p->d_bfilter, sizeof(double) * bfilter.size()));
-      SCN_TRY(hipMemcpy(p->d_chirp, chirp.data(), sizeof(double) * chirp.size(), hipMemcpyHostToDevice));
-      SCN_TRY(hipMemcpy(p->d_bfilter, bfilter.data(), sizeof(double) * bfilter.size(), hipMemcpyHostToDevice));
-    }
-    // the same values, regrouped per thread of the fused kernel: entry (p-1, t) = W_n^(t p), t < n/16
-    uint32_t tw1_rows = 15, nthreads = 1;  // (only the fused kernels read it)
-    if (p->mixed) scn_mixed_layout(d.n, &tw1_rows, &nthreads);
-    else if (!p->generic && !p->big) scn_tw1_layout(d.n, &tw1_rows, &nthreads);
-    std::vector<float> tw1(2 * (size_t)tw1_rows * nthreads);
-    for (uint32_t pp = 1; pp <= tw1_rows; pp++)
-      for (uint32_t t = 0; t < nthreads; t++) {
-        const uint32_t m = (uint32_t)(((uint64_t)t * pp) % tn);
-        tw1[2 * ((size_t)(pp - 1) * nthreads + t)] = tw[2 * m];
-        tw1[2 * ((size_t)(pp - 1) * nthreads + t) + 1] = tw[2 * m + 1];
-      }
+    SCN_TRY(build_tables(p));
     for (int k = 0; k < SCN_NUM_SLOTS; k++) {
       SCN_TRY(hipMalloc(&p->slot[k].d_work_counter, sizeof(uint32_t) * 8 * 32));
       SCN_TRY(hipMemsetAsync(p->slot[k].d_work_counter, 0, sizeof(uint32_t) * 8 * 32, p->stream));
     }
-    SCN_TRY(hipMalloc(&p->d_tw1_table, sizeof(float) * tw1.size()));
-    SCN_TRY(hipMemcpyAsync(p->d_tw1_table, tw1.data(), sizeof(float) * tw1.size(), hipMemcpyHostToDevice, p->stream));
     SCN_TRY(hipStreamSynchronize(p->stream));
 #undef SCN_TRY
   } while (0);

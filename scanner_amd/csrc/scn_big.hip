@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256, 3) void scn_big_rows_kernel(ScnBigArgs args) {
     for (int q = 0; q < 16; q++) {
       const uint32_t jj = k1 + 256u * (lo + 16u * q);
       const uint32_t ii = jj ^ (BN / 2);  // (j + N/2) % N, process.cpp:47
-      const bool keep = !(jj < args.dc_ignore || (BN - jj) < args.dc_ignore) && !(ii < args.i_lo || ii > args.i_hi);
+      const bool keep = scn_bin_evaluated(jj, ii, BN, args);
       keepmask |= keep ? (1u << q) : 0u;
     }
     const float pmax = fmaxf(fmaxf(gmax[0], gmax[1]), fmaxf(gmax[2], gmax[3]));
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(256, 3) void scn_big_rows32k_kernel(ScnBigArgs args
     for (int o = 0; o < 16; o++) {
       const uint32_t jj = k1 + 256u * k2_of(o);
       const uint32_t ii = jj ^ (N / 2);  // (j + N/2) % N, process.cpp:47
-      const bool keep = !(jj < args.dc_ignore || (N - jj) < args.dc_ignore) && !(ii < args.i_lo || ii > args.i_hi);
+      const bool keep = scn_bin_evaluated(jj, ii, N, args);
       keepmask |= keep ? (1u << o) : 0u;
     }
     const float pmax = fmaxf(fmaxf(gmax[0], gmax[1]), fmaxf(gmax[2], gmax[3]));

@@ -1,25 +1,24 @@
-// scn_generic.hip -- the same per-buffer path for the FFT sizes the fused LDS kernels do not cover.
+// scn_generic.hip -- the same per-buffer path for the FFT sizes no fused kernel covers: Bluestein's algorithm.
 //
-// The reference plans an FFT for whatever --count it is given (fft.cpp:4-11, scan.cpp:85).  The fused kernels of
-// scn_kernels.hip exist for N = 1024 ... 16384 (the sizes whose buffer fits a CU's LDS, and the reference's own
-// default 8192 among them); every other power of two from 16 to 65536 runs here, through HBM, stage by stage:
-//
-//   scn_gen_load_kernel     K1 + K2: raw wire format -> complex float, DC removal, window  (utility.cpp:9-84, process.cpp:28-34)
-//   scn_gen_stage_kernel    K3: one out-of-place Stockham stage of radix 4 (or 2): after log_R N launches the spectrum is
-//                           in natural order (fft.cpp:20-25: forward, unnormalised)
-//   scn_gen_finish_kernel   K4 + K5: dB (utility.cpp:86-98), fftshift-indexed mask, strict > threshold, hit records into the
-//                           buffer's region (process.cpp:46-62)
-//
-// Sizes that are NOT powers of two (16 <= N < 65536) use the same kernels around Bluestein's identity
+// The reference plans an FFT for whatever --count it is given (fft.cpp:4-11, scan.cpp:85).  Every power of two from 16 to
+// 65536 has a fused or four-step kernel, and so have the 5-smooth sizes of scn_mixed_plans.h; every other size from 16 to
+// 65535 runs here, through HBM, around Bluestein's identity
 //   X[k] = w[k] * sum_n (x[n] w[n]) conj(w)[k - n],   w[n] = exp(-i pi n^2 / N):
-// a cyclic convolution of length M = the power of two >= 2N - 1, i.e. load (x window w, zero-padded to M) -> FFT_M ->
-// multiply by the precomputed FFT_M of the chirp filter (scaled by 1/M) and conjugate -> FFT_M again (an inverse transform
-// up to a conjugation) -> finish.  The final w[k] and the conjugation have modulus one and never reach the dB value.
+// a cyclic convolution of length M = the power of two >= 2N - 1, transformed stage by stage:
 //
-// The same outputs as the fused path (spectrum, per-buffer counts, unordered regions that scn_hits.hip orders), at
-// 2 + log_4 N passes over the data instead of one, in double between input and spectrum: a correctness path for unusual
-// sizes, not a fast one -- each kernel is a plain streaming kernel (coalesced reads; the stage writes are strided by the
-// sub-transform length).
+//   scn_gen_load_kernel       K1 + K2: raw wire format -> complex float, DC removal, window (utility.cpp:9-84, process.cpp:28-34),
+//                             times w, zero-padded to M
+//   scn_gen_stage_kernel      one out-of-place Stockham stage of radix 16, 4 or 2: after log_R M launches the transform is in
+//                             natural order
+//   scn_gen_pointwise_kernel  times the precomputed FFT_M of the chirp filter (scaled by 1/M), conjugated; then the stages
+//                             again (an inverse transform up to a conjugation)
+//   scn_gen_finish_kernel     K4 + K5: dB (utility.cpp:86-98), fftshift-indexed mask, strict > threshold, hit records into the
+//                             buffer's region (process.cpp:46-62)
+//
+// The final w[k] and the conjugation have modulus one and never reach the dB value.  The same outputs as the fused path
+// (spectrum, per-buffer counts, unordered regions that scn_hits.hip orders), in double between input and spectrum: a
+// correctness path for unusual sizes, not a fast one -- each kernel is a plain streaming kernel (coalesced reads; the stage
+// writes are strided by the sub-transform length).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -119,20 +118,14 @@ __global__ __launch_bounds__(256) void scn_gen_load_kernel(ScnGenericArgs a) {
     scn_v2d *out = static_cast<scn_v2d *>(a.work0) + (size_t)b * a.m;
     // the windowed sample is a FLOAT product, as in the reference (process.cpp:28-34 multiplies floats) and in the fused
     // kernels: float(s - dc)*onebymax*w and float(s - dc)*(onebymax*w) round identically (onebymax is +-2^-k)
-    if (a.chirp) {  // Bluestein: times the chirp, zero-padded to the convolution length
-      for (uint32_t i = t; i < a.m; i += 256u) {
-        cd v = cd{0.0, 0.0};
-        if (i < n) {
-          const cf x = L::conv(buf, n, i, dc_re, dc_im, 1.0f) * (a.window[i] * a.scale);
-          v = cmul_d(cd{(double)x.x, (double)x.y}, static_cast<const scn_v2d *>(a.chirp)[i]);
-        }
-        out[i] = to_v2d(v);
-      }
-    } else {
-      for (uint32_t i = t; i < n; i += 256u) {
+    // times the chirp, zero-padded to the convolution length
+    for (uint32_t i = t; i < a.m; i += 256u) {
+      cd v = cd{0.0, 0.0};
+      if (i < n) {
         const cf x = L::conv(buf, n, i, dc_re, dc_im, 1.0f) * (a.window[i] * a.scale);
-        out[i] = scn_v2d{(double)x.x, (double)x.y};
+        v = cmul_d(cd{(double)x.x, (double)x.y}, static_cast<const scn_v2d *>(a.chirp)[i]);
       }
+      out[i] = to_v2d(v);
     }
   }
 }
@@ -199,41 +192,20 @@ __global__ __launch_bounds__(256) void scn_gen_stage_kernel(ScnGenericArgs a, co
   }
 }
 
-template <bool HITS, bool POW2>
+template <bool HITS>
 __global__ __launch_bounds__(256) void scn_gen_finish_kernel(ScnGenericArgs a, const scn_v2d *__restrict__ spec) {
   const uint32_t n = a.n;
   const size_t total = (size_t)a.n_buffers * n;
   for (size_t g = (size_t)blockIdx.x * 256u + threadIdx.x; g < total; g += (size_t)gridDim.x * 256u) {
-    uint32_t b, j;
-    if (POW2) {
-      b = (uint32_t)(g >> a.log2m);
-      j = (uint32_t)g & (n - 1u);
-    } else {
-      b = (uint32_t)(g / n);
-      j = (uint32_t)(g - (size_t)b * n);
-    }
-    const scn_v2d X = spec[((size_t)b << a.log2m) + j];  // rows are m long (= n for the powers of two)
+    const uint32_t b = (uint32_t)(g / n), j = (uint32_t)(g - (size_t)b * n);
+    const scn_v2d X = spec[((size_t)b << a.log2m) + j];  // rows are m long
     const float d = power_db(cf{(float)X.x, (float)X.y});  // the spectrum in float (fft.cpp:20-25 delivers floats), then utility.cpp:86-98
     if (a.power_db) a.power_db[g] = d;
     if (HITS) {
-      const uint32_t i = POW2 ? (j + n / 2u) & (n - 1u) : (j + n - n / 2u) % n;  // the i with (i + N/2) % N == j, process.cpp:47
-      const bool keep = !(j < a.dc_ignore || (n - j) < a.dc_ignore) && !(i < a.i_lo || i > a.i_hi);
+      const uint32_t i = (j + n - n / 2u) % n;  // the i with (i + N/2) % N == j, process.cpp:47
+      const bool keep = scn_bin_evaluated(j, i, n, a);
       const bool hit = keep && d > a.threshold;  // strict >, process.cpp:54
-      if (POW2 && n >= 64u) {
-        // a wave's 64 consecutive bins belong to one buffer: ONE atomic per wave hands out its slots (a noisy 65536-point
-        // batch has ~20 k hits per buffer; one atomic per hit on 512 counters took 7 of the step's 10 ms)
-        const unsigned long long m = __ballot(hit);
-        if (m) {
-          const uint32_t lane = threadIdx.x & 63u;
-          uint32_t base = 0;
-          if (lane == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(&a.per_buffer_hits[b], (uint32_t)__popcll(m));
-          base = (uint32_t)__builtin_amdgcn_readlane((int)base, __builtin_ctzll(m));
-          if (hit) {
-            const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (pos < a.hit_region) a.hits[(size_t)b * a.hit_region + pos] = ScnDevHit{i, d};
-          }
-        }
-      } else if (hit) {
+      if (hit) {
         const uint32_t pos = atomicAdd(&a.per_buffer_hits[b], 1u);
         if (pos < a.hit_region) a.hits[(size_t)b * a.hit_region + pos] = ScnDevHit{i, d};
       }
@@ -250,7 +222,6 @@ hipError_t launch_load(bool dc, const ScnGenericArgs &a, int grid, hipStream_t s
 
 }  // namespace
 
-bool scn_generic_size_supported(uint32_t n) { return n >= 16u && n <= 65536u && (n & (n - 1u)) == 0u; }
 bool scn_bluestein_size_supported(uint32_t n) { return n >= 16u && n < 65536u && (n & (n - 1u)) != 0u; }  // transform length <= 131072
 
 hipError_t scn_launch_generic(int kind, bool dc, bool hits, const ScnGenericArgs &a, int num_cus, hipStream_t s) {
@@ -301,16 +272,12 @@ hipError_t scn_launch_generic(int kind, bool dc, bool hits, const ScnGenericArgs
   scn_v2d *const w0 = static_cast<scn_v2d *>(a.work0), *const w1 = static_cast<scn_v2d *>(a.work1);
   scn_v2d *spec = transform(w0, w1);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  if (a.chirp) {  // Bluestein: multiply by the filter's transform, conjugate, transform again
-    hipLaunchKernelGGL(scn_gen_pointwise_kernel, dim3(blocks_for((size_t)a.m * a.n_buffers)), dim3(256), 0, s, a, spec);
-    spec = transform(spec, spec == w0 ? w1 : w0);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
+  // multiply by the filter's transform, conjugate, transform again
+  hipLaunchKernelGGL(scn_gen_pointwise_kernel, dim3(blocks_for((size_t)a.m * a.n_buffers)), dim3(256), 0, s, a, spec);
+  spec = transform(spec, spec == w0 ? w1 : w0);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
   const int fin = blocks_for((size_t)a.n * a.n_buffers);
-  const bool pow2 = a.chirp == nullptr;
-  if (hits && pow2) hipLaunchKernelGGL((scn_gen_finish_kernel<true, true>), dim3(fin), dim3(256), 0, s, a, spec);
-  else if (hits) hipLaunchKernelGGL((scn_gen_finish_kernel<true, false>), dim3(fin), dim3(256), 0, s, a, spec);
-  else if (pow2) hipLaunchKernelGGL((scn_gen_finish_kernel<false, true>), dim3(fin), dim3(256), 0, s, a, spec);
-  else hipLaunchKernelGGL((scn_gen_finish_kernel<false, false>), dim3(fin), dim3(256), 0, s, a, spec);
+  if (hits) hipLaunchKernelGGL((scn_gen_finish_kernel<true>), dim3(fin), dim3(256), 0, s, a, spec);
+  else hipLaunchKernelGGL((scn_gen_finish_kernel<false>), dim3(fin), dim3(256), 0, s, a, spec);
   return hipGetLastError();
 }

@@ -51,6 +51,12 @@ struct ScnFftArgs {
   uint32_t *work_counter;
   uint32_t work_base[8];
 };
+// K5's mask (process.cpp:46-52, uint32 arithmetic): is bin j of an n-point spectrum, fftshift index i = (j + n/2) % n, held
+// against the threshold?  `a` carries dc_ignore, i_lo and i_hi (the argument structs of every path; the host sizes hit_region by it)
+template <class A>
+__host__ __device__ __forceinline__ bool scn_bin_evaluated(uint32_t j, uint32_t i, uint32_t n, const A &a) {
+  return !(j < a.dc_ignore || (n - j) < a.dc_ignore) && !(i < a.i_lo || i > a.i_hi);
+}
 // which wire formats pull their buffers from the queue (the compute-bound integer ones; the float path is
 // memory-bound and measurably better off with the static assignment)
 // ... and only from 4096 points up: a launch of the same sample count makes 4x / 2x as many dequeues at 1024 / 2048
@@ -114,7 +120,7 @@ hipError_t scn_launch_hit_compact(const ScnCompactArgs &args, hipStream_t stream
 hipError_t scn_launch_hit_total(const uint32_t *counts, uint32_t n_buffers, uint32_t trigger_count, unsigned long long *acc, unsigned long long *host_total,
                                 uint32_t *trigger_bits, hipStream_t stream);
 
-// The same path for the power-of-two sizes without a fused kernel (scn_generic.hip): through HBM, stage by stage
+// The same path for the sizes without a fused or four-step kernel (scn_generic.hip): Bluestein, through HBM, stage by stage
 struct ScnGenericArgs {
   const void *raw;            // n_buffers raw buffers back to back
   const float *window;        // [n]
@@ -122,9 +128,9 @@ struct ScnGenericArgs {
   void *work0, *work1;        // double[n_buffers][m][2] each: ping-pong between the stages
   float *power_db;            // [n_buffers][n] or nullptr
   uint32_t n, n_buffers;      // buffer length (samples, bins)
-  uint32_t m, log2m;          // transform length: n for a power of two, the power of two >= 2n - 1 for Bluestein
-  const void *chirp;          // Bluestein only: double[n][2], w[i] = exp(-i pi i^2 / n);  nullptr for the powers of two
-  const void *bfilter;        // Bluestein only: double[m][2], FFT_m of the chirp filter, scaled by 1/m
+  uint32_t m, log2m;          // transform length: the power of two >= 2n - 1
+  const void *chirp;          // double[n][2], w[i] = exp(-i pi i^2 / n)
+  const void *bfilter;        // double[m][2], FFT_m of the chirp filter, scaled by 1/m
   float scale, threshold;
   uint32_t dc_ignore, i_lo, i_hi;
   ScnDevHit *hits;            // [n_buffers][hit_region]
@@ -132,8 +138,7 @@ struct ScnGenericArgs {
   uint32_t *per_buffer_hits;  // [n_buffers], zeroed by the launcher
 };
 hipError_t scn_launch_generic(int kind, bool correct_dc, bool hits, const ScnGenericArgs &args, int num_cus, hipStream_t stream);
-bool scn_generic_size_supported(uint32_t n);    // powers of two, 16 ... 65536
-bool scn_bluestein_size_supported(uint32_t n);  // everything else from 16 to 32768
+bool scn_bluestein_size_supported(uint32_t n);  // the sizes from 16 to 65535 that are not powers of two
 
 // Plain 65536- / 32768-point plans through the four-step pair of scn_big.hip (columns -> tiled work buffer -> rows + K4 + K5)
 struct ScnBigArgs {

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(16 * M, Geo<M>::WAVES_PER_SIMD) void scn_fft_kernel
     for (int o = 0; o < 16; o++) {
       const uint32_t j = t + joff_of(o);
       const uint32_t i = j ^ (N / 2);  // (j + N/2) % N, process.cpp:47
-      const bool keep = !(j < args.dc_ignore || (N - j) < args.dc_ignore) && !(i < args.i_lo || i > args.i_hi);
+      const bool keep = scn_bin_evaluated(j, i, N, args);
       keepmask |= keep ? (1u << o) : 0u;
     }
   }
@@ -503,7 +503,7 @@ __global__ __launch_bounds__(256, 3) void scn_fft_small_kernel(ScnFftArgs args) 
     for (int o = 0; o < 16; o++) {
       const uint32_t j = t + joff_of(o);
       const uint32_t i = j ^ (N / 2);  // (j + N/2) % N, process.cpp:47
-      const bool keep = !(j < args.dc_ignore || (N - j) < args.dc_ignore) && !(i < args.i_lo || i > args.i_hi);
+      const bool keep = scn_bin_evaluated(j, i, N, args);
       keepmask |= keep ? (1u << o) : 0u;
     }
   }
@@ -714,7 +714,7 @@ __global__ __launch_bounds__(256, 3) void scn_fft_tiny_kernel(ScnFftArgs args) {
     for (int o = 0; o < 16; o++) {
       const uint32_t j = t + joff_of(o);
       const uint32_t i = j ^ (N / 2);  // (j + N/2) % N, process.cpp:47
-      const bool keep = !(j < args.dc_ignore || (N - j) < args.dc_ignore) && !(i < args.i_lo || i > args.i_hi);
+      const bool keep = scn_bin_evaluated(j, i, N, args);
       keepmask |= keep ? (1u << o) : 0u;
     }
   }
@@ -910,7 +910,7 @@ __device__ __forceinline__ void scn_fft8k_body(const ScnFftArgs &args) {
     for (int r = 0; r < 32; r++) {
       const uint32_t j = t + 256u * r;
       const uint32_t i = j ^ (N / 2);  // (j + N/2) % N, process.cpp:47
-      const bool keep = !(j < args.dc_ignore || (N - j) < args.dc_ignore) && !(i < args.i_lo || i > args.i_hi);
+      const bool keep = scn_bin_evaluated(j, i, N, args);
       keepmask |= keep ? (1u << r) : 0u;
     }
   }
@@ -1184,7 +1184,7 @@ __device__ __forceinline__ void scn_fft16k2_body(const ScnFftArgs &args) {
     for (int r = 0; r < 32; r++) {
       const uint32_t j = t + 512u * r;
       const uint32_t i = j ^ (N / 2);  // (j + N/2) % N, process.cpp:47
-      const bool keep = !(j < args.dc_ignore || (N - j) < args.dc_ignore) && !(i < args.i_lo || i > args.i_hi);
+      const bool keep = scn_bin_evaluated(j, i, N, args);
       keepmask |= keep ? (1u << r) : 0u;
     }
   }

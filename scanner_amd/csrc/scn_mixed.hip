@@ -113,6 +113,7 @@ __global__ __launch_bounds__(G::W) void scn_fft_mixed_kernel(ScnFftArgs args, ui
 #pragma unroll
     for (uint32_t r = 0; r < R3; r++) {
       const uint32_t j = t + V3 * r, i = bin_i((int)r);
+      // scn_bin_evaluated written out, here and in scn_fft_mixed_big_kernel: called, it costs the hits kernels of 17 sizes an instruction
       const bool keep = !(j < args.dc_ignore || (N - j) < args.dc_ignore) && !(i < args.i_lo || i > args.i_hi);
       keepmask |= keep ? (1u << r) : 0u;
     }

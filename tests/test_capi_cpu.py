@@ -107,6 +107,21 @@ def test_size_paths(built_lib):
         assert capi.size_path(n) == capi.PATH_BLUESTEIN, n
     for n in (0, 1, 8, 15, 65537, 1 << 17):
         assert capi.size_path(n) == capi.PATH_UNSUPPORTED, n
+    # every size against the rule stated plainly (the mixed sizes as scn_mixed_plans.h lists them); PATH_STAGED is never reported
+    with open(os.path.join(ROOT, "scanner_amd", "csrc", "scn_mixed_plans.h")) as fh:
+        mixed = {int(m) for m in re.findall(r"^\s*X\((\d+),", fh.read(), flags=re.M)}
+    assert len(mixed) == 34
+
+    def rule(n):
+        pow2 = n > 0 and n & (n - 1) == 0
+        if (pow2 and 16 <= n <= 16384) or n in mixed:
+            return capi.PATH_FUSED
+        if n in (32768, 65536):
+            return capi.PATH_FOUR_STEP
+        return capi.PATH_BLUESTEIN if 16 <= n <= 65535 and not pow2 else capi.PATH_UNSUPPORTED
+
+    for n in range(70001):
+        assert capi.size_path(n) == rule(n) != capi.PATH_STAGED, n
 
 
 def test_no_gpu_means_loud_failure(built_lib):

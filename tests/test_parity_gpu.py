@@ -440,9 +440,9 @@ def test_sizes_integer_kinds(torch_cuda, oracle_mod, n, kind, enob, dc):
     (32768, capi.KIND_SHORT_COMPLEX, 12, True), (65536, capi.KIND_FLOAT_COMPLEX, 12, False), (65536, capi.KIND_BYTE_COMPLEX, 8, False),
 ])
 def test_generic_sizes_vs_oracle(torch_cuda, oracle_mod, n, kind, enob, dc):
-    """The reference plans any --count (fft.cpp:4-11).  Powers of two outside 1024 ... 16384: 16 ... 128 and 32768 run through the
-    staged path of scn_generic.hip, 256 / 512 through the several-buffers-per-workgroup kernel, 65536 through the four-step pair
-    of scn_big.hip: same spectra (to the bar), same hit lists, same trigger flags."""
+    """The reference plans any --count (fft.cpp:4-11).  Powers of two outside 1024 ... 16384: 16 ... 512 run through the fused
+    kernels that hold several buffers per workgroup, 32768 and 65536 through the four-step pairs of scn_big.hip: same spectra (to
+    the bar), same hit lists, same trigger flags."""
     nb = {16: 200, 64: 150, 256: 90, 512: 75, 32768: 9, 65536: 5}[n]
     x = synth.cfloat_batch(n, nb, seed=70 + n % 1000, sigma=0.1)
     raw = synth.quantize(x, kind) if kind != capi.KIND_FLOAT_COMPLEX else x
