@@ -34,9 +34,11 @@ extern "C" {
 #define SCN_API
 #endif
 
-#define SCN_ABI_VERSION 5 /* 3: SCN_NUM_SLOTS 4, scn_gather_hits_device, scn_gather_fetch, scn_size_path; 4: scn_plan_set_table, scn_submit*_indexed;
+#define SCN_ABI_VERSION 6 /* 3: SCN_NUM_SLOTS 4, scn_gather_hits_device, scn_gather_fetch, scn_size_path; 4: scn_plan_set_table, scn_submit*_indexed;
                              5: scn_welch_desc.sample_kind / enob / correct_dc (carved out of its reserved words: same size, zero = the
-                             version-4 behaviour), scn_welch_partition, scn_gather_post, scn_gather_wait */
+                             version-4 behaviour), scn_welch_partition, scn_gather_post, scn_gather_wait;
+                             6: scn_plan_desc.average / average_layout (carved out of its reserved words: same size, zero = the
+                             version-5 behaviour), SCN_AVG_*, scn_plan_average_parts */
 
 /* status codes */
 enum {
@@ -127,8 +129,27 @@ typedef struct scn_plan_desc {
                               scn_collect can return; the rest stays on the GPU for scn_collect_more); 0 -> 64 per buffer */
   uint32_t flags;          /* SCN_OUT_* (neither -> SPECTRUM|HITS), SCN_PLAN_OVERLAP_SLOTS */
   int32_t device_id;       /* HIP device ordinal */
-  uint32_t reserved[5];
+  uint32_t average;        /* 0 -> 1.  K > 1: average K buffers per centre frequency before detection (below) */
+  uint32_t average_layout; /* 0 -> SCN_AVG_DWELL: which buffers of a submit form a group */
+  uint32_t reserved[3];
 } scn_plan_desc;
+
+/* Averaged plans (average = K > 1; Bartlett's method: no overlap, whole buffers).  A submit of n_buffers = K*G buffers forms G
+ * groups of K buffers.  Every buffer goes through convert (with its own DC removal), window and FFT exactly as in a plain plan;
+ * the group's spectrum is 5*log10(P[j]), P[j] = (sum over the group's buffers, in order, of |X_b[j]|^2) / (float)K, and the
+ * mask, threshold, records and trigger run on it ONCE per group with the group's centre frequency.  So every output is per
+ * group: power_db / d_power_db / scn_device_spectrum hold G*N floats, trigger G bytes, and the ordered hit list is ordered by
+ * (group, i); a record's seq_id is that of the group's FIRST buffer (its seq_ids entry, or its index when seq_ids is NULL).
+ * Frequency-domain plans of 1024, 2048, 4096 and 8192 points only (other sizes, time-domain mode, a max_batch that is not a
+ * multiple of K and an unknown layout: SCN_E_INVALID at create).  A submit with n_buffers % K != 0 is SCN_E_INVALID; so is one whose
+ * center_freqs (still one per buffer) differ inside a group.  Indexed submits: group g carries
+ * center_freqs[(first_index + g) % count] of the plan's table.  When G is small the K buffers of a group are split over
+ * several workgroups whose partial sums are added in a fixed order (scn_plan_average_parts): results are deterministic, but
+ * with more than one part the float sum is grouped differently from a single running sum.  K = 1 is the plain plan. */
+enum {
+  SCN_AVG_DWELL = 0,  /* group g = buffers g*K ... g*K + K - 1: K buffers of one centre back to back (a dwell) */
+  SCN_AVG_SWEEPS = 1  /* group g = buffers g, g + G, ..., g + (K-1)*G: K whole sweeps of a G-centre table back to back */
+};
 
 #define SCN_DC_IGNORE_NONE 0xffffffffu
 /* Submits a plan can have in flight (submit ... collect per slot).  Two cover kernel-only pipelines; with the ordered records
@@ -157,6 +178,10 @@ enum {
 SCN_API int scn_size_path(uint32_t n, uint32_t *path);
 
 SCN_API int scn_plan_create(const scn_plan_desc *desc, scn_plan **out);
+/* Averaged plans: the number of workgroups (*parts) that share the K buffers of one group in a submit of n_buffers buffers
+ * (1 for plain plans).  Chosen from the CU count, G and K: enough parts to fill the GPU when G is small, at least two buffers
+ * per part, 1 when G alone fills it. */
+SCN_API int scn_plan_average_parts(const scn_plan *plan, uint32_t n_buffers, uint32_t *parts);
 SCN_API int scn_plan_destroy(scn_plan *plan);
 
 /* Bytes of one raw buffer (N samples) in the plan's wire format. */

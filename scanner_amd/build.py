@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libscanner_hip.so")
-SOURCES = ["scn_kernels.hip", "scn_mixed.hip", "scn_generic.hip", "scn_big.hip", "scn_hits.hip", "scn_welch.hip", "scn_gather.hip", "scn_api.hip"]
+SOURCES = ["scn_kernels.hip", "scn_mixed.hip", "scn_generic.hip", "scn_big.hip", "scn_hits.hip", "scn_welch.hip", "scn_average.hip", "scn_gather.hip", "scn_api.hip"]
 HEADERS = ["scn_kernels.h", "scn_device.h", "scn_mixed_dft.h", "scn_mixed_plans.h", "scn_gather_protocol.h", os.path.join("..", "..", "include", "scanner_hip.h")]
 ARCH = "gfx950"
 # The library's dynamic symbol table is the C-ABI and nothing else: everything is compiled with hidden visibility, the entry
@@ -37,7 +37,7 @@ def write_map():
     with open(MAP_FILE, "w") as fh:
         fh.write("{\n  global:\n" + "".join(f"    {n};\n" for n in declared_symbols()) + "  local:\n    *;\n};\n")
 # files compiled once per value of a macro, side by side, each translation unit instantiating one group of sizes
-SPLIT = {"scn_kernels.hip": ("SCN_TU", 8), "scn_mixed.hip": ("SCN_MIXED_TU", 8)}
+SPLIT = {"scn_kernels.hip": ("SCN_TU", 8), "scn_mixed.hip": ("SCN_MIXED_TU", 8), "scn_average.hip": ("SCN_AVG_TU", 4)}
 
 
 def hipcc():

@@ -21,7 +21,8 @@ OUT_SPECTRUM, OUT_HITS = 1, 2
 PLAN_OVERLAP_SLOTS = 4  # each slot on its own compute stream (scanner_hip.h)
 DC_IGNORE_NONE = 0xFFFFFFFF
 NUM_SLOTS = 4
-ABI_VERSION = 5
+ABI_VERSION = 6
+AVG_DWELL, AVG_SWEEPS = 0, 1  # scn_plan_desc.average_layout
 PATH_UNSUPPORTED, PATH_FUSED, PATH_FOUR_STEP, PATH_STAGED, PATH_BLUESTEIN = range(5)
 COMM_ID_BYTES = 128
 GATHER_TICKETS = 4
@@ -52,7 +53,9 @@ class PlanDesc(C.Structure):
         ("max_hits", C.c_uint32),
         ("flags", C.c_uint32),
         ("device_id", C.c_int32),
-        ("reserved", C.c_uint32 * 5),
+        ("average", C.c_uint32),
+        ("average_layout", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
     ]
 
 
@@ -82,6 +85,7 @@ SYMBOLS = {
     "scn_size_path": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32)]),
     "scn_plan_create": (C.c_int, [C.POINTER(PlanDesc), C.POINTER(_vp)]),
     "scn_plan_destroy": (C.c_int, [_vp]),
+    "scn_plan_average_parts": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint32)]),
     "scn_buffer_bytes": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "scn_host_buffer": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "scn_submit": (C.c_int, [_vp, C.c_int, C.c_uint32, _vp, _vp]),

@@ -59,6 +59,7 @@ namespace {
 
 struct Slot {
   void *d_gen_work[2] = {nullptr, nullptr};  // scratch of the four-step and Bluestein paths (launch_transform)
+  float *d_avg_partial = nullptr;   // averaged plans: the partial power sums between the two kernels of scn_average.hip
   void *h_raw = nullptr;            // pinned staging, max_batch raw buffers
   void *d_raw = nullptr;            // device copy of the staging slot
   float *d_power = nullptr;         // [max_batch][N] dB spectra (plan-owned destination)
@@ -164,6 +165,7 @@ struct scn_plan {
   // ~4 us of completion latency, measured in round 1, and the 8192-point ones less than the late copy did).
   bool direct_counts = false;
   Path path = Path::Unsupported;
+  uint32_t avg = 1, avg_layout = SCN_AVG_DWELL;  // scn_plan_desc.average / average_layout with the defaults applied
   uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
   double *d_twiddle64 = nullptr;     // four-step: [256][2] W_256^k; Bluestein: [fft_m][2] W_m^k; in double
   double *d_table = nullptr;         // [table_count] the plan's frequency table (scn_plan_set_table), read by the compaction kernel
@@ -182,6 +184,8 @@ struct scn_plan {
   float *d_window = nullptr;
   scn_v2f *d_twiddle = nullptr;
   scn_v2f *d_tw1_table = nullptr;  // [15][n/16], ScnFftArgs::tw1_table
+  scn_v2f *d_avg_tw1 = nullptr;    // averaged 8192-point plans: ScnAvgArgs::tw1_half ([15][256], W_4096^(t p))
+  double *d_avg_tw = nullptr;      // ... and ScnAvgArgs::tw_half ([4096][2], W_8192^k in double)
   // scn_convert_raw's device staging (the capture writer calls it per record): plan-owned, grown on demand, never per call
   void *d_conv_in = nullptr;
   scn_v2f *d_conv_out = nullptr;
@@ -311,6 +315,18 @@ hipError_t build_tables(scn_plan *p) {
           tw1[2 * ((size_t)(pp - 1) * threads + t) + 1] = tw[2 * m + 1];
         }
       if ((e = upload(&p->d_twiddle, tw)) != hipSuccess) return e;
+      if (p->avg > 1u && n == 8192) {  // the averaged kernel's two 4096-point halves and the radix-2 step that joins them
+        std::vector<float> half(2 * 15 * 256);
+        for (uint32_t pp = 1; pp <= 15; pp++)
+          for (uint32_t t = 0; t < 256; t++) {
+            const uint32_t m = (2u * t * pp) % n;  // W_4096^(t p) = W_8192^(2 t p)
+            half[2 * ((pp - 1) * 256 + t)] = tw[2 * m];
+            half[2 * ((pp - 1) * 256 + t) + 1] = tw[2 * m + 1];
+          }
+        std::vector<double> join = twiddles<double>(n);
+        join.resize(n);  // k < 4096
+        if ((e = upload(&p->d_avg_tw1, half)) != hipSuccess || (e = upload(&p->d_avg_tw, join)) != hipSuccess) return e;
+      }
       return upload(&p->d_tw1_table, tw1);
     }
     case Path::FourStep:  // W_n in float; W_256 in double: the row transform of scn_big.hip
@@ -502,6 +518,37 @@ int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float
   const uint32_t n = p->d.n;
   const int kind = (int)p->d.sample_kind;
   const bool hits = (p->d.flags & SCN_OUT_HITS) != 0, dc = p->d.correct_dc != 0;
+  if (p->avg > 1u) {  // nb buffers = nb / K groups (scn_average.hip)
+    const uint32_t ng = nb / p->avg;
+    if (ng && !s.d_avg_partial)
+      SCN_HIP(hipMalloc(&s.d_avg_partial, sizeof(float) * scn_avg_partial_floats(n, p->d.max_batch / p->avg, p->num_cus)));
+    ScnAvgArgs a;
+    memset(&a, 0, sizeof(a));
+    a.raw = d_raw;
+    a.window = p->d_window;
+    a.twiddle = p->d_twiddle;
+    a.tw1_table = p->d_tw1_table;
+    a.tw1_half = p->d_avg_tw1;
+    a.tw_half = reinterpret_cast<const double2_scn *>(p->d_avg_tw);
+    a.partial = s.d_avg_partial;
+    a.power_db = d_power;
+    a.n = n;
+    a.n_groups = ng;
+    a.k = p->avg;
+    a.parts = scn_avg_parts(n, ng, p->avg, p->num_cus);
+    a.layout = p->avg_layout == SCN_AVG_SWEEPS ? SCN_AVG_L_SWEEPS : SCN_AVG_L_DWELL;
+    a.scale = p->scale;
+    a.threshold = p->d.threshold;
+    a.p_lo = scn_hit_prefilter(p->d.threshold);
+    a.dc_ignore = p->d.dc_ignore_bins;
+    a.i_lo = p->i_lo;
+    a.i_hi = p->i_hi;
+    a.hits = s.d_hits[s.gen];
+    a.hit_region = p->hit_region;
+    a.per_group_hits = s.d_buf_hits[s.gen];
+    SCN_HIP(scn_launch_average(kind, dc && kind != SCN_KIND_FLOAT_COMPLEX, hits, d_power != nullptr, a, p->num_cus, s.stream));
+    return SCN_OK;
+  }
   switch (p->path) {
     case Path::FusedPow2:
     case Path::FusedMixed: {
@@ -558,9 +605,52 @@ int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float
   }
 }
 
+// Averaged plans: a submit's arguments alone decide whether it can run -- checked before any copy or kernel is queued
+int check_average(const scn_plan *p, uint32_t nb, const double *fc) {
+  if (p->avg <= 1u) return SCN_OK;
+  const uint32_t k = p->avg;
+  if (nb % k) return fail(SCN_E_INVALID, "n_buffers %u is not a multiple of average %u", nb, k);
+  if (!fc) return SCN_OK;
+  const uint32_t ng = nb / k;
+  const bool sweeps = p->avg_layout == SCN_AVG_SWEEPS;
+  for (uint32_t g = 0; g < ng; g++) {
+    const size_t b0 = sweeps ? g : (size_t)g * k;
+    for (uint32_t b = 1; b < k; b++) {
+      const size_t bb = sweeps ? g + (size_t)b * ng : (size_t)g * k + b;
+      if (!(fc[bb] == fc[b0]))
+        return fail(SCN_E_INVALID, "center_freqs differ inside group %u (buffer %zu: %.17g, its first buffer: %.17g)", g, bb, fc[bb],
+                    fc[b0]);
+    }
+  }
+  return SCN_OK;
+}
+
 // fc == nullptr: the buffers carry entries table_first, table_first + 1, ... (wrapping) of the plan's frequency table
 int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const double *fc, const uint64_t *seq,
                   float *d_power, uint32_t table_first = 0) {
+  // Averaged plans: from here on nb counts GROUPS -- the outputs, the records' headers, the counts and triggers are per group --
+  // and only the transform sees the buffers.  A group's header is that of its first buffer.
+  const uint32_t n_raw = nb;
+  std::vector<double> group_fc;
+  std::vector<uint64_t> group_seq;
+  if (p->avg > 1u) {
+    // (the arguments were checked by check_average before anything was queued)
+    const uint32_t k = p->avg;
+    const uint32_t ng = nb / k;
+    const bool sweeps = p->avg_layout == SCN_AVG_SWEEPS;
+    auto buffer_of = [&](uint32_t g, uint32_t b) -> size_t { return sweeps ? g + (size_t)b * ng : (size_t)g * k + b; };
+    if (fc) {
+      group_fc.resize(ng);
+      for (uint32_t g = 0; g < ng; g++) group_fc[g] = fc[buffer_of(g, 0)];
+      fc = group_fc.data();
+    }
+    if (seq || !sweeps) {  // (sweeps without seq_ids: group g's first buffer is buffer g, the compaction kernel's default)
+      group_seq.resize(ng);
+      for (uint32_t g = 0; g < ng; g++) group_seq[g] = seq ? seq[buffer_of(g, 0)] : (uint64_t)buffer_of(g, 0);
+      seq = group_seq.data();
+    }
+    nb = ng;
+  }
   const bool will_flip = p->d.mode != SCN_MODE_TIME_DOMAIN && (p->d.flags & SCN_OUT_HITS) != 0 && nb != 0;
   int st = ensure_slot_outputs(p, s, will_flip ? s.gen ^ 1u : s.gen);
   if (st) return st;
@@ -624,7 +714,7 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   // on that stream against 73 us of FFT; records read in place, three in flight: 373 .. 403 -> 429 Gsamples/s).  So the kernel
   // stores the counts itself when the launch has few buffers or the list follows eagerly, and a DMA carries them otherwise.
   const bool eager = hits && nb && (p->records_wanted || p->device_list_wanted);
-  const bool fused = p->path == Path::FusedPow2 || p->path == Path::FusedMixed;
+  const bool fused = (p->path == Path::FusedPow2 || p->path == Path::FusedMixed) && p->avg == 1u;
   const bool direct = fused && (p->direct_counts || nb <= 4096u || eager);
   // What follows the kernel: the counts (a DMA on the d2h stream: needs no CU -- or nothing, when the kernel stores them to
   // pinned memory itself) and, when the caller is known to want records, the ordered list (two small kernels + a DMA on
@@ -646,7 +736,7 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   const bool after_is_done = cnt == s.stream && !s.own_stream;  // direct counts on the plan's stream
   hipEvent_t after = (!nb || s.own_stream || total_path) ? nullptr : !hits ? s.done : after_is_done ? s.done : s.kernel_done;
   const bool in_packet = after && fused && (uint64_t)nb * n >= (1u << 25);
-  st = launch_transform(p, s, d_raw, nb, d_power, (hits && direct) ? s.h_buf_hits : nullptr, in_packet ? after : nullptr);
+  st = launch_transform(p, s, d_raw, n_raw, d_power, (hits && direct) ? s.h_buf_hits : nullptr, in_packet ? after : nullptr);
   if (st) return st;
   if (hits && nb) {
     if (after && !in_packet) SCN_HIP(hipEventRecord(after, s.stream));
@@ -679,6 +769,7 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
 void free_slot(Slot &s) {
   for (int g = 0; g < 2; g++)
     if (s.d_gen_work[g]) (void)hipFree(s.d_gen_work[g]);
+  if (s.d_avg_partial) (void)hipFree(s.d_avg_partial);
   if (s.h_raw) (void)hipHostFree(s.h_raw);
   if (s.d_raw) (void)hipFree(s.d_raw);
   if (s.d_power) (void)hipFree(s.d_power);
@@ -777,6 +868,14 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   if (path == Path::Unsupported) return fail(SCN_E_INVALID, "unsupported FFT size %u (16 to 65536)", d.n);
   if (d.n == 0 || d.n > (1u << 24)) return fail(SCN_E_INVALID, "bad sample count %u", d.n);
   if (d.sample_rate == 0) return fail(SCN_E_INVALID, "sample_rate must be > 0");
+  const uint32_t avg = d.average ? d.average : 1u;
+  if (avg > 1u) {  // (checked before the device: these are properties of the descriptor alone)
+    if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return fail(SCN_E_INVALID, "average %u needs a frequency-domain plan", avg);
+    if (!scn_avg_size_supported(d.n)) return fail(SCN_E_INVALID, "average %u: n = %u is not supported (1024, 2048, 4096, 8192)", avg, d.n);
+    if (d.max_batch % avg) return fail(SCN_E_INVALID, "average %u does not divide max_batch %u", avg, d.max_batch);
+    if (d.average_layout != SCN_AVG_DWELL && d.average_layout != SCN_AVG_SWEEPS)
+      return fail(SCN_E_INVALID, "unknown average_layout %u", d.average_layout);
+  }
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SCN_E_NO_DEVICE, "no HIP device visible");
@@ -787,6 +886,8 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   if (!p) return fail(SCN_E_NOMEM, "out of host memory");
   p->d = d;
   p->path = path;
+  p->avg = avg;
+  p->avg_layout = avg > 1u ? d.average_layout : (uint32_t)SCN_AVG_DWELL;
   p->buf_bytes = bytes_per_sample(d.sample_kind) * d.n;
   p->scale = convert_scale(d.sample_kind, d.enob);
   // process.cpp:85 m_useWindow = uint32_t(useBandWidth * numSamples / 2.0); :51 bounds in uint32
@@ -866,6 +967,8 @@ int scn_plan_destroy(scn_plan *p) {
   if (p->d_chirp) (void)hipFree(p->d_chirp);
   if (p->d_bfilter) (void)hipFree(p->d_bfilter);
   if (p->d_tw1_table) (void)hipFree(p->d_tw1_table);
+  if (p->d_avg_tw1) (void)hipFree(p->d_avg_tw1);
+  if (p->d_avg_tw) (void)hipFree(p->d_avg_tw);
   if (p->d_conv_in) (void)hipFree(p->d_conv_in);
   if (p->d_conv_out) (void)hipFree(p->d_conv_out);
   if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -873,6 +976,17 @@ int scn_plan_destroy(scn_plan *p) {
   if (p->d2h_stream) (void)hipStreamDestroy(p->d2h_stream);
   if (p->list_stream) (void)hipStreamDestroy(p->list_stream);
   delete p;
+  return SCN_OK;
+}
+
+int scn_plan_average_parts(const scn_plan *p, uint32_t nb, uint32_t *parts) {
+  if (!p || !parts) return fail(SCN_E_INVALID, "null argument");
+  if (p->avg <= 1u) {
+    *parts = 1;
+    return SCN_OK;
+  }
+  if (nb % p->avg) return fail(SCN_E_INVALID, "n_buffers %u is not a multiple of average %u", nb, p->avg);
+  *parts = scn_avg_parts(p->d.n, nb / p->avg, p->avg, p->num_cus);
   return SCN_OK;
 }
 
@@ -901,6 +1015,7 @@ int submit_host(scn_plan *p, int slot, uint32_t nb, const double *fc, const uint
   int st;
   Slot &s = p->slot[slot];
   if (nb > p->d.max_batch) return fail(SCN_E_INVALID, "n_buffers %u > max_batch %u", nb, p->d.max_batch);
+  if ((st = check_average(p, nb, fc))) return st;
   if (s.pending) return fail(SCN_E_STATE, "slot %d has an uncollected submit", slot);
   if (!s.h_raw) return fail(SCN_E_STATE, "slot %d: scn_host_buffer was never called", slot);
   SCN_HIP(hipSetDevice(p->d.device_id));
@@ -932,6 +1047,7 @@ int scn_submit_device(scn_plan *p, int slot, const void *d_raw, uint32_t nb, con
   Slot &s = p->slot[slot];
   if (nb > p->d.max_batch) return fail(SCN_E_INVALID, "n_buffers %u > max_batch %u", nb, p->d.max_batch);
   if (nb && (!fc || !d_raw)) return fail(SCN_E_INVALID, "null argument");
+  if ((st = check_average(p, nb, fc))) return st;
   if (s.pending) return fail(SCN_E_STATE, "slot %d has an uncollected submit", slot);
   SCN_HIP(hipSetDevice(p->d.device_id));
   if ((st = ensure_slot_stream(p, s))) return st;
@@ -992,6 +1108,7 @@ int scn_submit_device_indexed(scn_plan *p, int slot, const void *d_raw, uint32_t
   Slot &s = p->slot[slot];
   if (nb > p->d.max_batch) return fail(SCN_E_INVALID, "n_buffers %u > max_batch %u", nb, p->d.max_batch);
   if (nb && !d_raw) return fail(SCN_E_INVALID, "null argument");
+  if ((st = check_average(p, nb, nullptr))) return st;
   if (s.pending) return fail(SCN_E_STATE, "slot %d has an uncollected submit", slot);
   SCN_HIP(hipSetDevice(p->d.device_id));
   if ((st = ensure_slot_stream(p, s))) return st;

@@ -159,6 +159,33 @@ struct ScnBigArgs {
 hipError_t scn_launch_big(uint32_t n, int kind, bool correct_dc, bool hits, bool spectrum, const ScnBigArgs &args, int num_cus, hipStream_t stream);
 bool scn_big_size_supported(uint32_t n);  // 65536, 32768
 
+// Averaged plans (scn_average.hip, scn_plan_desc.average = K > 1): n_groups groups of k buffers, each buffer through K1 + K2 +
+// K3 as in the fused kernels, the group's powers summed in float, divided by k, then K4 + K5 once per group
+#define SCN_AVG_L_DWELL 0   // buffers g k ... g k + k - 1 (SCN_AVG_DWELL)
+#define SCN_AVG_L_SWEEPS 1  // buffers g, g + n_groups, ... (SCN_AVG_SWEEPS)
+struct ScnAvgArgs {
+  const void *raw;            // n_groups * k raw buffers back to back
+  const float *window;        // [n]
+  const scn_v2f *twiddle;     // W_n^m
+  const scn_v2f *tw1_table;   // as ScnFftArgs::tw1_table (1024 ... 4096 points)
+  const scn_v2f *tw1_half;    // 8192 points: the same table of the 4096-point transform of each half, [15][256]
+  const double2_scn *tw_half; // 8192 points: W_8192^k, k < 4096, in double (the radix-2 step that joins the halves)
+  float *partial;             // [n_groups][parts][n] linear power sums of the parts (between the two kernels)
+  float *power_db;            // [n_groups][n] or nullptr
+  uint32_t n, n_groups, k, parts, layout;
+  float scale, threshold, p_lo;
+  uint32_t dc_ignore, i_lo, i_hi;
+  ScnDevHit *hits;            // [n_groups][hit_region]
+  uint32_t hit_region;
+  uint32_t *per_group_hits;   // [n_groups], zeroed by the launcher
+};
+bool scn_avg_size_supported(uint32_t n);  // 1024, 2048, 4096, 8192
+// workgroups that share the k buffers of one group (1 <= parts <= max(1, ceil(k / 2)))
+uint32_t scn_avg_parts(uint32_t n, uint32_t n_groups, uint32_t k, int num_cus);
+// floats of the partial-sum buffer a launch of up to max_groups groups needs
+size_t scn_avg_partial_floats(uint32_t n, uint32_t max_groups, int num_cus);
+hipError_t scn_launch_average(int kind, bool correct_dc, bool hits, bool spectrum, const ScnAvgArgs &args, int num_cus, hipStream_t stream);
+
 // K1 alone (capture path)
 hipError_t scn_launch_convert(int kind, bool correct_dc, const void *raw, scn_v2f *out, uint32_t n, uint32_t n_buffers,
                               float scale, hipStream_t stream);

@@ -15,7 +15,11 @@ class Plan:
     def __init__(self, n, sample_rate=8000000, threshold=10.0, kind=capi.KIND_FLOAT_COMPLEX, enob=12,
                  correct_dc=False, max_batch=1, use_bandwidth=0.75, dc_ignore_bins=4, trigger_count=1047,
                  max_hits=0, flags=capi.OUT_SPECTRUM | capi.OUT_HITS, device_id=0,
-                 window_type=capi.WIN_BLACKMAN_HARRIS, mode=capi.MODE_FREQUENCY_DOMAIN):
+                 window_type=capi.WIN_BLACKMAN_HARRIS, mode=capi.MODE_FREQUENCY_DOMAIN, average=1,
+                 average_layout=capi.AVG_DWELL):
+        """average = K > 1: every K buffers of a submit form a group (average_layout: capi.AVG_DWELL, buffers gK ... gK+K-1,
+        or capi.AVG_SWEEPS, buffers g, g+G, ...) whose mean power spectrum is what the plan reports and detects on; the
+        outputs of collect are then per group (scanner_hip.h)."""
         self._L = capi.lib()
         d = capi.PlanDesc()
         d.struct_size = C.sizeof(capi.PlanDesc)
@@ -34,6 +38,9 @@ class Plan:
         d.max_hits = max_hits
         d.flags = flags
         d.device_id = device_id
+        d.average = average
+        d.average_layout = average_layout
+        self.average, self.average_layout = max(1, int(average)), average_layout
         self.n, self.kind, self.max_batch, self.flags, self.device_id = n, kind, max_batch, flags, device_id
         self.sample_rate = int(sample_rate)
         self.use_bandwidth = use_bandwidth
@@ -67,6 +74,17 @@ class Plan:
 
     def __exit__(self, *a):
         self.close()
+
+    def groups(self, n_buffers):
+        """Spectra (and trigger bytes) a submit of n_buffers buffers yields: n_buffers / average."""
+        assert n_buffers % self.average == 0, f"n_buffers {n_buffers} is not a multiple of average {self.average}"
+        return n_buffers // self.average
+
+    def average_parts(self, n_buffers):
+        """Workgroups that share one group's buffers in a submit of n_buffers (scn_plan_average_parts)."""
+        parts = C.c_uint32()
+        capi.check(self._L.scn_plan_average_parts(self._h, n_buffers, C.byref(parts)), "scn_plan_average_parts")
+        return parts.value
 
     # -- staging ------------------------------------------------------------
     def host_buffer(self, slot):
@@ -124,7 +142,7 @@ class Plan:
             ptr = int(d_raw)
         out_ptr = None
         if d_power_db is not None:
-            assert d_power_db.is_contiguous() and d_power_db.numel() >= n_buffers * self.n
+            assert d_power_db.is_contiguous() and d_power_db.numel() >= (n_buffers // self.average) * self.n
             out_ptr = C.c_void_p(d_power_db.data_ptr())
         if first_index is not None:  # a run of the plan's frequency table (set_table)
             assert center_freqs is None, "a submit names its centres or a run of the plan's table, not both"
@@ -170,13 +188,14 @@ class Plan:
         capi.check(self._L.scn_wait(self._h, slot), "scn_wait")
 
     def collect(self, slot, want_power=True, want_hits=True, hit_cap=None, hits_out=None):
-        """Block on the slot and return (power_db [B,n] | None, hits (HIT_DTYPE) | None, trigger uint8[B] | None).
+        """Block on the slot and return (power_db [B,n] | None, hits (HIT_DTYPE) | None, trigger uint8[B] | None), B the
+        submit's buffers -- or its groups, n_buffers / average, on an averaged plan.
         The hit list arrives ordered by (buffer, i) and complete from the GPU.  With hit_cap=None every hit is returned
         however many there are (the part beyond the plan's pinned list is fetched with scn_collect_more); with an
         explicit hit_cap the C-ABI's own behaviour shows: ScannerError(E_TRUNCATED) when more hits exist.
         hits_out: a caller-owned HIT_DTYPE array to receive the records (its length is the capacity): a loop that
         collects every step should not pay for a fresh 12 MB allocation and its page faults each time."""
-        nb = self._nb[slot]
+        nb = self._nb[slot] // self.average
         have_hits = bool(self.flags & capi.OUT_HITS)
         power = np.empty((nb, self.n), np.float32) if (want_power and self.flags & capi.OUT_SPECTRUM) else None
         want_hits = want_hits and have_hits
