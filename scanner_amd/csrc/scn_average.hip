@@ -6,8 +6,10 @@
 // records) run once per group.
 //
 //   scn_avg_power_kernel    persistent workgroups over work items (group g, part q): the transform of scn_fft_kernel
-//                           (scn_kernels.hip -- the same n = T a + M b + c decomposition, LDS layouts and prefetch of the next
-//                           buffer's samples into registers across the three passes; a fix to one belongs in the other), but
+//                           (scn_kernels.hip) on the one geometry both take from scn_device.h (Geo<M>, out_reg<M>: the
+//                           n = T a + M b + c decomposition and the LDS layouts); passes 1 - 3 with the prefetch of the next
+//                           buffer's samples are written out in both kernels, line for line (as one shared function every
+//                           kernel of both families is scheduled differently: profiles/refactor_isa_digest.md), but
 //                           the thread's output powers are ADDED into VGPR accumulators.  At the end of an item:
 //                           P = 1 (OUT != OUT_PARTIAL): the item is the whole group, and the kernel runs K4 + K5 itself --
 //                             db_of_power for the spectrum, the hits-only decision (candidate by linear power p > p_lo, then
@@ -45,28 +47,16 @@ enum { OUT_PARTIAL = 0, OUT_SPEC = 1, OUT_HITS = 2, OUT_BOTH = 3 };
 
 namespace {
 
-// (Geo / out_reg of scn_kernels.hip for the transform of 256 M points, M in {4, 8, 16}; H halves per buffer)
+// Geo<M> (scn_device.h) for a buffer of H halves, each one transform of 256 M points
 template <int M, int H>
-struct AvgGeo {
-  static_assert(M == 4 || M == 8 || M == 16, "1024, 2048 or 4096 points per transform");
+struct AvgGeo : Geo<M> {
   static_assert(H == 1 || (H == 2 && M == 16), "8192 points as two 4096-point halves");
-  static constexpr uint32_t N = 256u * M;  // transform
-  static constexpr uint32_t NT = N * H;    // buffer = plan size
-  static constexpr uint32_t T = 16u * M;
-  static constexpr uint32_t P1 = T + M;
-  static constexpr uint32_t P2 = 256u + 16u / M;
-  static constexpr uint32_t EXCH = (16u * P1 > M * P2) ? 16u * P1 : M * P2;  // slots
-  static constexpr uint32_t LDS_BYTES = EXCH * 8u + T * 8u + 32u * 4u + 4u;
-  static constexpr uint32_t WAVES = T / 64;
+  static constexpr uint32_t NT = Geo<M>::N * H;  // buffer = plan size
+  static constexpr uint32_t LDS_BYTES = Geo<M>::EXCH * 8u + Geo<M>::T * 8u + 32u * 4u + 4u;
   static constexpr uint32_t WAVES_PER_SIMD = H == 1 ? 3 : 2;  // H = 2 keeps the even half's 16 outputs and 32 sums besides
-  static constexpr uint32_t WG_PER_CU = (WAVES_PER_SIMD * 4u) / WAVES;
+  static constexpr uint32_t WG_PER_CU = (WAVES_PER_SIMD * 4u) / Geo<M>::WAVES;
   static constexpr int NB = 16 * H;  // outputs (bins) per thread
 };
-
-template <int M>
-__device__ __forceinline__ constexpr int avg_out_reg(int o) {
-  return M == 4 ? o : M == 8 ? (o & ~7) + OUT8(o & 7) : OUT16(o & 15);
-}
 
 // The walk of one workgroup over its items w = blockIdx.x + i gridDim.x, inside an item over the part's buffers, inside a
 // buffer over its H halves.  Everything here is wave-uniform.
@@ -271,14 +261,14 @@ __global__ __launch_bounds__(16 * M, H == 1 ? 3 : 2) void scn_avg_power_kernel(S
     // the same thread owns the same bins for every buffer: the group's sums stay in registers
     if constexpr (H == 1) {
 #pragma unroll
-      for (int o = 0; o < 16; o++) acc[o] = acc[o] + power_of(v[avg_out_reg<M>(o)]);
+      for (int o = 0; o < 16; o++) acc[o] = acc[o] + power_of(v[out_reg<M>(o)]);
     } else if (h == 0) {
 #pragma unroll
-      for (int o = 0; o < 16; o++) even[o] = v[avg_out_reg<M>(o)];
+      for (int o = 0; o < 16; o++) even[o] = v[out_reg<M>(o)];
     } else {
 #pragma unroll
       for (int o = 0; o < 16; o++) {
-        const cf e = even[o], od = v[avg_out_reg<M>(o)];
+        const cf e = even[o], od = v[out_reg<M>(o)];
         const double2_scn w = args.tw_half[t + joff_of(o)];  // W_8192^k, k < 4096, in double
         const double wr = (double)od.x * w.x - (double)od.y * w.y, wi = (double)od.x * w.y + (double)od.y * w.x;
         const double ar = (double)e.x + wr, ai = (double)e.y + wi, br = (double)e.x - wr, bi = (double)e.y - wi;

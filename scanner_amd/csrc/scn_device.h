@@ -166,6 +166,13 @@ __device__ __forceinline__ void fft16_d(cd v[16]) {
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, uint32_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, bytes, 0x00020000);
 }
+// Cache-policy immediates of the buffer instructions on gfx950: bit0 = sc0, bit1 = nt, bit4 = sc1.
+// Both streams are touched exactly once, so both are non-temporal: measured with inputs AND outputs
+// rotated over 1.5 GiB (nothing can live in the 256 MiB Infinity Cache), a no-compute skeleton
+// of this kernel's traffic moves 5.66 TB/s with the default policy and 6.40 TB/s with nt on both
+// (scripts/membw.hip); the FFT kernel itself gains 4-5 %.
+constexpr int SCN_AUX_LD = 2;
+constexpr int SCN_AUX_ST = 2;
 
 // sum over the 64 lanes of a wave (result in every lane)
 __device__ __forceinline__ int wave_sum(int v) {
@@ -398,18 +405,39 @@ __device__ __forceinline__ void scn_record_hits_lanes(VEC &pw, const float (&gma
   }
 }
 
-// ---- global memory access through buffer descriptors ---------------------------------
-// A raw buffer resource (SGPR descriptor, wave-uniform base) + one per-lane VGPR offset
-// + scalar/immediate offsets: the 16 strided accesses of a thread cost no address VGPRs.
-//
-// Cache-policy immediates of the buffer instructions on gfx950: bit0 = sc0, bit1 = nt, bit4 = sc1.
-// Both streams are touched exactly once, so both are non-temporal: measured with inputs AND outputs
-// rotated over 1.5 GiB (nothing can live in the 256 MiB Infinity Cache), a no-compute skeleton
-// of this kernel's traffic moves 5.66 TB/s with the default policy and 6.40 TB/s with nt on both
-// (scripts/membw.hip); the FFT kernel itself gains 4-5 %.
-constexpr int SCN_AUX_LD = 2;
-constexpr int SCN_AUX_ST = 2;
+// ---- K4, the exact half of the dB map stored over the product-form values the spectrum already holds --------------------
+// `pw` holds the linear powers of the thread's NB outputs, `gmax` the largest of each of the four groups of NB / 4, `pmax`
+// the largest of those; output o goes to voffset st_voff + scalar byte offset soff_of(o).  Only in waves that hold a bin
+// from SCN_P_EXACT_FROM up; the other lanes' stores go to an out-of-range offset and are dropped by the descriptor's range
+// check (no branch per bin).
+// Strong bins are neighbours -- a tone's main lobe sits in ONE or two output indices o of a wave -- and the bench input has
+// such a wave in most buffers, so this path must stay short: all 16 outputs at ~14 operations each made the wave its
+// workgroup's straggler (+4 us per C2 launch), 16 wave-wide tests still +1 .. 4 us; so: the groups first, then the outputs
+// of a group that holds one.
+// (scn_small_db_store_record and the two mixed-radix kernels keep written-out copies: see there.  The 16384-point kernel's
+// variant -- the exact value of the group maximum only -- is the documented exception above.)
+template <int NB, typename VEC, typename SOFF>
+__device__ __forceinline__ void scn_store_exact_db(const VEC &pw, const float (&gmax)[4], float pmax, __amdgpu_buffer_rsrc_t rout, uint32_t st_voff,
+                                                   SOFF soff_of) {
+  constexpr int GS = NB / 4;
+  if (__ballot(pmax >= SCN_P_EXACT_FROM)) {
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+      if (__ballot(gmax[g] >= SCN_P_EXACT_FROM)) {
+#pragma unroll
+        for (int o = g * GS; o < (g + 1) * GS; o++) {
+          const float q = pw[o];  // NB: never __builtin_bit_cast a vector ELEMENT: clang reads element 0 for every o
+          if (__ballot(q >= SCN_P_EXACT_FROM)) {
+            const float d = db_exact(q);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, d), rout, q >= SCN_P_EXACT_FROM ? st_voff : 0x80000000u, soff_of(o), SCN_AUX_ST);
+          }
+        }
+      }
+    }
+  }
+}
 
+// ---- K1: the wire formats (8 / 4 / 2 bytes per sample) --------------------------------------------------------------
 template <int KIND>
 struct RawLoader;
 
@@ -522,5 +550,27 @@ struct RawLoader<SCN_K_SHORT> {
   }
 };
 
+// ---- geometry of the 256*M-point transform (M in {4, 8, 16}: 1024 / 2048 / 4096 points) of scn_fft_kernel (scn_kernels.hip,
+//      where the decomposition and the LDS layouts are described) and scn_avg_power_kernel (scn_average.hip) ----
+template <int M>
+struct Geo {
+  static_assert(M == 4 || M == 8 || M == 16, "1024, 2048 or 4096 points");
+  static constexpr uint32_t N = 256u * M;
+  static constexpr uint32_t T = 16u * M;
+  static constexpr uint32_t P1 = T + M;
+  static constexpr uint32_t P2 = 256u + 16u / M;
+  static constexpr uint32_t EXCH = (16u * P1 > M * P2) ? 16u * P1 : M * P2;  // slots
+  static constexpr uint32_t LDS_BYTES = EXCH * 8u + T * 8u + 16u * 4u + 2u * 4u + 64u * 4u + 8u;
+  static constexpr uint32_t WAVES = T / 64;
+  // the register prefetch of the next buffer costs a wave per SIMD (4 -> 3): VGPR budget 168
+  static constexpr uint32_t WAVES_PER_SIMD = 3;
+  static constexpr uint32_t WG_PER_CU = (WAVES_PER_SIMD * 4u) / WAVES;
+};
+
+// natural output index o of a thread -> register that holds it after pass 3
+template <int M>
+__device__ __forceinline__ constexpr int out_reg(int o) {
+  return M == 4 ? o : M == 8 ? (o & ~7) + OUT8(o & 7) : OUT16(o & 15);
+}
 
 }  // namespace

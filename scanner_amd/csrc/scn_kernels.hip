@@ -97,27 +97,6 @@
   auto wq_take = [&]() -> uint32_t { return atomicAdd(wq_head + wq_zero, 1u); };                       \
   auto wq_buffer = [&](uint32_t taken) -> uint32_t { return 8u * (wq_j0 + (taken - wq_base)) + wq_shard; }
 
-template <int M>
-struct Geo {
-  static_assert(M == 4 || M == 8 || M == 16, "1024, 2048 or 4096 points");
-  static constexpr uint32_t N = 256u * M;
-  static constexpr uint32_t T = 16u * M;
-  static constexpr uint32_t P1 = T + M;
-  static constexpr uint32_t P2 = 256u + 16u / M;
-  static constexpr uint32_t EXCH = (16u * P1 > M * P2) ? 16u * P1 : M * P2;  // slots
-  static constexpr uint32_t LDS_BYTES = EXCH * 8u + T * 8u + 16u * 4u + 2u * 4u + 64u * 4u + 8u;
-  static constexpr uint32_t WAVES = T / 64;
-  // the register prefetch of the next buffer costs a wave per SIMD (4 -> 3): VGPR budget 168
-  static constexpr uint32_t WAVES_PER_SIMD = 3;
-  static constexpr uint32_t WG_PER_CU = (WAVES_PER_SIMD * 4u) / WAVES;
-};
-
-// natural output index o of a thread -> register that holds it after pass 3
-template <int M>
-__device__ __forceinline__ constexpr int out_reg(int o) {
-  return M == 4 ? o : M == 8 ? (o & ~7) + OUT8(o & 7) : OUT16(o & 15);
-}
-
 // Output modes (template parameters HITS, SPEC): spectrum only (false, true), spectrum + hits (true, true), hits only
 // (true, false).  The hits-only kernel has NO store instructions and no per-bin v_log_f32: it compares the linear power with a
 // guarded linear threshold (ScnFftArgs::p_lo, a shade below 10^(threshold/5)) and evaluates the dB map -- the same function
@@ -296,8 +275,7 @@ __global__ __launch_bounds__(16 * M, Geo<M>::WAVES_PER_SIMD) void scn_fft_kernel
     // ---- K4 + K5 ----
     // The thread's 16 LINEAR powers stay in `pw` for the hit path; the spectrum gets the dB map of scn_device.h: its product
     // form inline, and -- only in waves that hold a bin from SCN_P_EXACT_FROM up -- the exact form stored over it for those
-    // bins (the other lanes' stores go to an out-of-range offset and are dropped by the descriptor's range check: no branch
-    // per bin).
+    // bins (scn_store_exact_db).
     v16f pw;
     float gmax[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // the largest power of each group of four outputs (max ignores NaN)
     __amdgpu_buffer_rsrc_t rout = make_rsrc(args.power_db + (size_t)buf * N, (SPEC && args.power_db) ? 4u * N : 0u);
@@ -309,27 +287,7 @@ __global__ __launch_bounds__(16 * M, Geo<M>::WAVES_PER_SIMD) void scn_fft_kernel
       if constexpr (SPEC) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, db_fast(q)), rout, st_voff, 4u * joff_of(o), AUX_ST);
     }
     const float pmax = fmaxf(fmaxf(gmax[0], gmax[1]), fmaxf(gmax[2], gmax[3]));  // pre-filter of the hit path and of the exact half
-    if constexpr (SPEC) {
-      if (__ballot(pmax >= SCN_P_EXACT_FROM)) {
-        // Strong bins are neighbours -- a tone's main lobe sits in ONE or two output indices o of a wave -- and the bench
-        // input has such a wave in most buffers, so this path must stay short: all 16 outputs at ~14 operations each made
-        // the wave its workgroup's straggler (+4 us per C2 launch), 16 wave-wide tests still +1 .. 4 us; so: the groups of
-        // four first, then the outputs of a group that holds one.
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-          if (__ballot(gmax[g] >= SCN_P_EXACT_FROM)) {
-#pragma unroll
-            for (int o = 4 * g; o < 4 * g + 4; o++) {
-              const float q = pw[o];  // NB: never __builtin_bit_cast a vector ELEMENT: clang reads element 0 for every o
-              if (__ballot(q >= SCN_P_EXACT_FROM)) {
-                const float d = db_exact(q);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, d), rout, q >= SCN_P_EXACT_FROM ? st_voff : 0x80000000u, 4u * joff_of(o), AUX_ST);
-              }
-            }
-          }
-        }
-      }
-    }
+    if constexpr (SPEC) scn_store_exact_db<16>(pw, gmax, pmax, rout, st_voff, [&](int o) -> uint32_t { return 4u * joff_of(o); });
     if (t == 0) lds_next[0] = !more ? 0xffffffffu : DYN ? wq_buffer(taken) : nxt + gridDim.x;
     __syncthreads();  // barrier 4: exchange area free again; lds_next visible (it is rewritten three barriers from now)
     const uint32_t after = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_next[0]);
@@ -404,7 +362,7 @@ __device__ __forceinline__ void scn_small_db_store_record(POWER power_at, JOFF j
 #pragma unroll
       for (int o = 0; o < 16; o++) dbv[o] = db_fast(pw[o]);
     }
-    if (__ballot(pmax >= SCN_P_EXACT_FROM)) {
+    if (__ballot(pmax >= SCN_P_EXACT_FROM)) {  // scn_store_exact_db (scn_device.h) written out, keeping the value in dbv: through a sink functor 32 of the 96 kernels of 16 .. 128 points gain 32 instructions each
 #pragma unroll
       for (int g = 0; g < 4; g++) {
         if (__ballot(gmax[g] >= SCN_P_EXACT_FROM)) {
@@ -1043,23 +1001,7 @@ __device__ __forceinline__ void scn_fft8k_body(const ScnFftArgs &args) {
     }
 
     const float pmax = fmaxf(fmaxf(gmax[0], gmax[1]), fmaxf(gmax[2], gmax[3]));  // pre-filter of the hit path and of the exact half
-    if constexpr (SPEC) {
-      if (__ballot(pmax >= SCN_P_EXACT_FROM)) {
-#pragma unroll
-        for (int g = 0; g < 4; g++) {  // groups of eight outputs first, then the outputs of a group that holds a strong bin (see scn_fft_kernel)
-          if (__ballot(gmax[g] >= SCN_P_EXACT_FROM)) {
-#pragma unroll
-            for (int r = 8 * g; r < 8 * g + 8; r++) {
-              const float q = pw[r];
-              if (__ballot(q >= SCN_P_EXACT_FROM)) {
-                const float d = db_exact(q);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, d), rout, q >= SCN_P_EXACT_FROM ? st_voff : 0x80000000u, 1024u * r, AUX_ST);
-              }
-            }
-          }
-        }
-      }
-    }
+    if constexpr (SPEC) scn_store_exact_db<32>(pw, gmax, pmax, rout, st_voff, [](int r) -> uint32_t { return 1024u * (uint32_t)r; });
     if (t == 0) lds_next[0] = !more ? 0xffffffffu : DYN ? wq_buffer(taken) : nxt + gridDim.x;
     __syncthreads();  // barrier 4: exchange area free again; lds_next visible
     const uint32_t after = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_next[0]);

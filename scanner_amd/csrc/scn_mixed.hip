@@ -222,7 +222,7 @@ __global__ __launch_bounds__(G::W) void scn_fft_mixed_kernel(ScnFftArgs args, ui
     if constexpr (SPEC) {
       if (__ballot(pmax >= SCN_P_EXACT_FROM)) {
 #pragma unroll
-        for (int g = 0; g < 4; g++) {  // the groups first, then the outputs of a group that holds a strong bin (see scn_fft_kernel)
+        for (int g = 0; g < 4; g++) {  // scn_store_exact_db (scn_device.h) written out: called, 104 of the 312 kernels change (23 in their instruction counts)
           if (__ballot(gmax[g] >= SCN_P_EXACT_FROM)) {
 #pragma unroll
             for (int r = g * (NB / 4); r < (g + 1) * (NB / 4); r++) {
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(G::W) void scn_fft_mixed_big_kernel(ScnFftArgs args
       if constexpr (SPEC) {
         if (__ballot(pmax >= SCN_P_EXACT_FROM)) {
 #pragma unroll
-          for (int g = 0; g < 4; g++) {
+          for (int g = 0; g < 4; g++) {  // scn_store_exact_db written out, as in scn_fft_mixed_kernel: called, 8 of the 96 kernels come out in another order
             if (__ballot(gmax[g] >= SCN_P_EXACT_FROM)) {
 #pragma unroll
               for (int r = g * (NB / 4); r < (g + 1) * (NB / 4); r++) {
