@@ -43,6 +43,9 @@ namespace {
 // product-form value equals db_fast(gm) -- i.e. the group's strongest bin (a tone's strongest bins, one per thread), plus
 // any bin of the group within the product form's resolution of it; every other bin keeps the product form's <= 2.2 ulp.
 // Spectrum + hits and hits-only plans therefore report bit-identical records (tests/test_dispatch_gpu.py).
+// The bounds, the purity and the strict > are asserted on exactly known powers in every family by tests/test_db_map_gpu.py.
+// LIMIT: v_log_f32 takes no denormal input, so a power below FLT_MIN (2^-149 <= P < 2^-126, |X| < 1.1e-19) maps to -inf like a
+// zero power and never forms a record; the reference returns a finite -190 ... -224 dB there (its sqrtf of a denormal is normal).
 #define SCN_P_EXACT_FROM 1584.8932f
 __device__ __forceinline__ float db_fast(float p) { return 1.50514997831990597607f * __builtin_amdgcn_logf(p); }
 __device__ __forceinline__ float db_exact(float p) {

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from scanner_amd import build
+from tests import tolerances as tol
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
@@ -62,9 +63,9 @@ def _db(p):
 
 
 def _map_bound(t):
-    """the device map's error bound at a value near t, plus half an ulp of rounding to float"""
+    """the device map's error bound at a value near t (tests/tolerances.py), plus half an ulp of rounding to float"""
     t = np.abs(np.asarray(t, np.float64))
-    return np.maximum(4.2e-6, 2.2 * np.spacing(t.astype(F32)).astype(np.float64)) + 0.5 * np.spacing(t.astype(F32)).astype(np.float64)
+    return tol.db_map_bound(t) + 0.5 * np.spacing(t.astype(F32)).astype(np.float64)
 
 
 def _smallest_float_above(t_db):
@@ -119,7 +120,7 @@ def test_prefilter_special_values(prefilter):
     p = prefilter(t)
     assert np.isnan(p[0])                      # NaN: nothing passes (P > NaN is false), and nothing can hit
     assert np.isnan(p[1]) or p[1] == np.inf    # +inf: no dB value exceeds it, so the gate may pass nothing
-    assert p[2] == 0.0                         # -inf: every nonzero power (even the smallest denormal) may hit
+    assert p[2] == 0.0                         # -inf: every nonzero power passes the gate (the device's map then sends a denormal one to -inf: no hit)
     assert p[3] == p[4] and 0.999 < p[3] <= 1.0
     assert p[5] == FLT_MAX or p[5] == np.inf   # above FLT_MAX's 192.65 dB only +inf power can hit: an inf-valued bin
-    assert p[6] == 0.0                         # below every denormal: the smallest denormal still passes
+    assert p[6] == 0.0                         # below every denormal: the smallest denormal still passes the gate (tests/test_db_map_gpu.py: not the map)

@@ -27,6 +27,34 @@ DB_ABS = 1e-4
 DB_MIN_POWER_RATIO = 1.0     # dB criterion applies to bins with P >= this * mean(P)
 GUARD_DB = 1e-3              # no evaluated bin may sit this close to the threshold
 
+# The device's dB map (scn_device.h): the product form below SCN_P_EXACT_FROM = 10^3.2 (16 dB), the
+# exponent-split "exact" form from there up.  Stated once, for the host proof of the gate (tests/test_prefilter_cpu.py) and for
+# the GPU measurement of the map (tests/test_db_map_gpu.py), so that the two cannot drift apart.
+P_EXACT_FROM = np.float32(1584.8932)   # SCN_P_EXACT_FROM
+DB_MAP_ABS = 4.2e-6                    # dB: the product form's floor near 0 dB, where an ulp of the value vanishes
+DB_MAP_ULP_FAST = 2.2                  # ulp of the value: the product form, below P_EXACT_FROM
+DB_MAP_ULP_EXACT = 1.0                 # ulp of the value: the exact form, at and above P_EXACT_FROM
+
+
+def _ulp32(db):
+    return np.spacing(np.abs(np.asarray(db, np.float64)).astype(np.float32)).astype(np.float64)
+
+
+def db_map_bound(db):
+    """The product form's error bound in dB at a value near `db`, against the float64 value 5 log10 P (DESIGN.md section 3.1:
+    max(4.2e-6 dB, 2.2 ulp of the value)).  It is the wider of the two halves, hence the one the gate is proved against."""
+    return np.maximum(DB_MAP_ABS, DB_MAP_ULP_FAST * _ulp32(db))
+
+
+def db_map_bound_exact(db):
+    """The exact form's bound (powers >= P_EXACT_FROM, values from 16 dB up): 1.0 ulp of the value."""
+    return DB_MAP_ULP_EXACT * _ulp32(db)
+
+
+def db_map_bound_of_power(p, db):
+    """The bound that applies to a bin of float power `p` whose float64 value is `db`: by the half of the map that p takes."""
+    return np.where(np.asarray(p) >= P_EXACT_FROM, db_map_bound_exact(db), db_map_bound(db))
+
 
 def db_to_power(db):
     """inverse of dB = 5*log10(P)  (utility.cpp:86-98 computes 10*log10 |X|)"""
