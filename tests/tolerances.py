@@ -18,6 +18,21 @@ max_db_err_all_bins / strict_per_bin_rel_power_max of compare_spectra's result, 
 noise floor on Rayleigh-small bins, present between any two float32 FFTs (the reference's FFTW included), not an
 implementation error -- but it is not "1e-5 per bin" either.  And the oracle these figures are taken against is itself pinned
 by float64 mathematics only, not by the reference's own output (parity unpinned).
+
+THE THIRD CRITERION (floor_errors; tests/test_dynamic_range_cpu.py, tests/test_dynamic_range_gpu.py).  Under one strong signal nearly
+every bin lies below 1e-5 of the buffer's mean power (88 % at 64 points, over 99 % from 4096 up): there the first criterion allows an
+error of a hundred times the bin, and flip_unsafe takes the bin out of the hit comparison.  On exactly those bins floor_errors measures
+|a_test - a_float64| in amplitude, less the dB map's own proven allowance, relative to the buffer's rms level, and a kernel must stay
+within twice what the larger of two float32 transforms that are not the kernel gives on the same buffers (the oracle's chain and
+scipy.fft on complex64: 3e-7 at 16 points, 3e-6 at 4096, 6e-6 ... 1.1e-5 at 65536 -- Y is a maximum over a launch's floor bins and
+moves by up to 2x with the draw of the scene; profiles/dynamic_range.txt has the figure of every launch).  Hit lists on those scenes are demanded exact wherever the float64
+amplitude is further than that bound from the threshold.  This closes the gap of four orders of magnitude in which a coarse twiddle
+table or a float pass where double is promised would raise the floor by tens of dB unnoticed.  WHAT REMAINS UNASSERTED: a bin between
+the floor criterion's limit (1e-5 of the mean) and the mean itself is still held to 1e-5 of the MEAN only, i.e. to 1e-5 ... 1 of its
+own power; the criterion is asserted on the scenes of tests/dr_scenes.py, not on the suite's other inputs; and a SINGLE table entry
+ten ulp off is seen only where it carries enough of a buffer's energy to rise over a float32 transform's own rounding -- at 16 ... 128
+points, and in the table a workgroup shares up to 1024 points; from 4096 points up, and for one thread's pass-1 constant from 512 up,
+it stays under Y and unseen (measured: the docstring of tests/test_dynamic_range_gpu.py).
 """
 import numpy as np
 
@@ -97,6 +112,44 @@ def compare_spectra(db_test, db_ref):
     assert out["max_rel_power_vs_max_bin_mean"] <= REL_POWER, out
     assert np.all(db_err[big] <= db_bar[big]), out
     return out
+
+
+def floor_errors(db_test, a64):
+    """The third criterion: the bins compare_spectra is blind to -- those with a64^2 < REL_POWER * mean(a64^2), the floor under a
+    strong signal -- in AMPLITUDE, relative to the buffer's rms level.  db_test [..., n]: the reported dB (10 log10 |X|); a64: the
+    float64 DFT magnitude |X| of the same float32 samples.  Returns a dict:
+      floor_err     max over the floor bins of (|a_t - a64| - (ln 10 / 10) * db_map_bound_of_power(a64^2, dB64) * a64) / rms, clamped at
+                    0: a_t = 10^(dB / 10), rms = sqrt(mean a64^2) per buffer; the subtracted term is what the dB map's own proven
+                    bound is worth in amplitude.  A transform's rounding error on ANY bin scales with the buffer's rms level, not with
+                    the bin, so two correct float32 transforms give a few 1e-7 ... 1e-6 here (tests/test_dynamic_range_cpu.py
+                    prints the table) whatever the bin holds.
+      floor_share   the share of floor bins
+      strict_p99    |a_t^2 - a64^2| / a64^2 at the 99th percentile of the floor bins (reported, never asserted)
+      n_minus_inf   floor bins reported as -inf.  A -inf enters as a_t = 0, i.e. as the error a64 / rms: a caller's bound B so
+                    accepts it exactly where a64 <= B * rms (plus the map's allowance).
+    NaN and +inf are never acceptable, on any bin: AssertionError."""
+    db_test = np.asarray(db_test, np.float64)
+    a64 = np.asarray(a64, np.float64)
+    assert db_test.shape == a64.shape and np.isfinite(a64).all() and (a64 >= 0).all()
+    assert not np.isnan(db_test).any(), "NaN in a reported spectrum"
+    assert not (db_test == np.inf).any(), "+inf in a reported spectrum"
+    P = a64 * a64
+    mean = P.mean(axis=-1, keepdims=True)
+    rms = np.sqrt(mean)
+    floor = P < REL_POWER * mean
+    pos = a64 > 0
+    d64 = 10.0 * np.log10(np.where(pos, a64, 1.0))
+    allow = np.where(pos, (np.log(10.0) / 10.0) * db_map_bound_of_power(P, d64) * a64, 0.0)
+    a_t = np.where(np.isfinite(db_test), np.power(10.0, np.where(np.isfinite(db_test), db_test, 0.0) / 10.0), 0.0)
+    err = np.maximum(0.0, (np.abs(a_t - a64) - allow) / np.where(rms > 0, rms, 1.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        strict = np.where(pos, np.abs(a_t * a_t - P) / P, 0.0)
+    return {
+        "floor_err": float(err[floor].max()) if floor.any() else 0.0,
+        "floor_share": float(floor.mean()),
+        "strict_p99": float(np.quantile(strict[floor], 0.99)) if floor.any() else 0.0,
+        "n_minus_inf": int((floor & np.isneginf(db_test)).sum()),
+    }
 
 
 def flip_unsafe(db_ref, threshold, margin=4.0):
