@@ -123,7 +123,10 @@ __global__ __launch_bounds__(256) void scn_gen_load_kernel(ScnGenericArgs a) {
       cd v = cd{0.0, 0.0};
       if (i < n) {
         const cf x = L::conv(buf, n, i, dc_re, dc_im, 1.0f) * (a.window[i] * a.scale);
-        v = cmul_d(cd{(double)x.x, (double)x.y}, static_cast<const scn_v2d *>(a.chirp)[i]);
+        // (the written-out FMA form: left to the compiler, the contraction of x w = (x.x w.x - x.y w.y, ...) came out differently
+        //  in the int16 instantiation than in the others, and a constant buffer's residue bins differed between wire formats)
+        const scn_v2d c = static_cast<const scn_v2d *>(a.chirp)[i];
+        v = cmul_d(cd{(double)x.x, (double)x.y}, c.x, c.y);
       }
       out[i] = to_v2d(v);
     }

@@ -1354,8 +1354,10 @@ __global__ __launch_bounds__(256) void scn_time_domain_kernel(ScnTdArgs args) {
     }
     float pmax = -1.0f, pmin = 3.40282347e+38f;  // |x|^2 >= 0, so -1 is "no sample yet"
     for (uint32_t i = t; i < N; i += 256) {
+#pragma clang fp contract(off)  // (__fmul_rn / __fadd_rn are plain * and + in hipcc's headers, contracted like any other: the
+                                // operators are written here, where the pragma governs them)
       cf x = L::conv(L::template load<0>(rin, N, i, 0), dc_re, dc_im, args.scale);
-      float p = __fadd_rn(__fmul_rn(x.x, x.x), __fmul_rn(x.y, x.y));  // process.cpp:220, unfused
+      float p = x.x * x.x + x.y * x.y;  // process.cpp:220, unfused
       pmax = fmaxf(pmax, p);
       pmin = fminf(pmin, p);
     }
@@ -1454,8 +1456,9 @@ __global__ __launch_bounds__(256) void scn_time_domain_wave_kernel(ScnTdArgs arg
     }
     float pmax = -1.0f, pmin = 3.40282347e+38f;  // |x|^2 >= 0, so -1 is "no sample yet"
     for_each_sample([&](typename L::raw_t r) {
+#pragma clang fp contract(off)  // (as in scn_time_domain_kernel)
       const cf x = L::conv(r, dc_re, dc_im, args.scale);
-      const float p = __fadd_rn(__fmul_rn(x.x, x.x), __fmul_rn(x.y, x.y));  // process.cpp:220, unfused
+      const float p = x.x * x.x + x.y * x.y;  // process.cpp:220, unfused
       pmax = fmaxf(pmax, p);
       pmin = fminf(pmin, p);
     });

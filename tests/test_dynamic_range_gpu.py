@@ -103,25 +103,10 @@ def _threshold(a64):
     return float(thr), 10.0 ** (float(thr) / 10.0)
 
 
-def _evaluated(n, use_bandwidth=0.75, dc_ignore_bins=4):
-    """Boolean [n] over natural bin j: True where process.cpp:46-52 evaluates the bin, walked over i with j = (i + n / 2) % n as the
-    reference does -- at even n this is tolerances.evaluated_mask, at odd n (17, 1023, 4097, 65535) that mask's i = (j + n / 2) % n is
-    one bin off"""
-    half = n // 2
-    use_window = int(use_bandwidth * n / 2.0)
-    i = np.arange(n)
-    j = (i + half) % n
-    keep = ~((j < dc_ignore_bins) | ((n - j) < dc_ignore_bins) | (i < half - use_window) | (i > half + use_window))
-    m = np.zeros(n, bool)
-    m[j[keep]] = True
-    assert n % 2 or np.array_equal(m, tol.evaluated_mask(n))
-    return m
-
-
 def _owed(a64, n, a_thr, Y):
     """(owes, exempt) boolean [G, n] over natural bins: the evaluated bins the float64 spectrum puts above the threshold, and those
     within 2 Y rms of it"""
-    ev = _evaluated(n)[None, :]
+    ev = tol.evaluated_mask(n)[None, :]
     rms = np.sqrt((a64 * a64).mean(axis=1, keepdims=True))
     return ev & (a64 > a_thr), ev & (np.abs(a64 - a_thr) <= 2.0 * Y * rms)
 
@@ -129,7 +114,7 @@ def _owed(a64, n, a_thr, Y):
 def _check_hits(h, t, p, n, owes, exempt, fc_g, seq_g, trig_count, what):
     """the records h and trigger flags t of one launch against what the float64 spectrum owes; returns the exempt share"""
     G = owes.shape[0]
-    n_ev = int(_evaluated(n).sum())
+    n_ev = int(tol.evaluated_mask(n).sum())
     share = float(exempt.sum()) / (G * n_ev)
     assert share <= MAX_EXEMPT, f"{what}: {share:.2%} of the evaluated bins lie within 2 Y rms of the threshold"
     g = np.searchsorted(seq_g, h["seq_id"])
@@ -141,7 +126,7 @@ def _check_hits(h, t, p, n, owes, exempt, fc_g, seq_g, trig_count, what):
     j = (i + n // 2) % n
     got = np.zeros(owes.shape, bool)
     got[g, j] = True
-    assert _evaluated(n)[j].all(), f"{what}: a record outside the evaluated band"
+    assert tol.evaluated_mask(n)[j].all(), f"{what}: a record outside the evaluated band"
     bad = (got != owes) & ~exempt
     assert not bad.any(), (f"{what}: {int(bad.sum())} bins outside the exempt band differ from float64 "
                            f"({int((bad & got).sum())} reported and not owed, {int((bad & owes).sum())} owed and not reported); first (group, j): "

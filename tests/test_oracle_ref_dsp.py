@@ -4,7 +4,10 @@ compiles from /root/reference with `make -C oracle ref` (oracle/ref_dsp_binding.
 <fftw3.h> for the type fftwf_complex, is satisfied from this image's hipFFTW header).
 tests/golden/utility_ref.npz holds inputs and that build's outputs (tests/golden/make_utility_ref.py); held to it,
 bit for bit: the oracle's restatement (always, on CPU), the live reference object on random inputs (where oracle/_ref is
-present), and -- on the GPU -- the PRODUCT's own K1 (scn_convert_raw, the load phase of the fused kernels).
+present), and -- on the GPU -- scn_convert_raw, i.e. scn_convert_kernel: the capture path's K1.  That is NOT the load phase of the
+transform kernels: every family has its own copy (DC sums, the int32 /= uint32 division, planar addressing, onebymax folded into
+the window tap).  Those copies are pinned through this one by tests/test_fused_k1_gpu.py: an integer plan and a FLOAT_COMPLEX plan
+on scn_convert_raw's output must report identical bits, in every family, wire format and DC setting (no family is exempt).
 Still unpinned by reference code: the window (GNU Radio), the multiply (VOLK), the FFT (FFTW) and process_fft
 (process.cpp includes all three)."""
 import os

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from scanner_amd import Plan, capi, sweep, synth
+from tests import tolerances as tol
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,7 +67,23 @@ def test_c4_eight_shards_equal_unsharded_and_expectation(torch_cuda):
     assert len(want) == 7 * 4096 == len(whole)
     for f in ("seq_id", "i", "freq_hz"):
         assert np.array_equal(whole[f], want[f]), f
-    assert np.abs(whole["power_db"] - want["power_db"]).max() < 0.15
+    assert np.abs(whole["power_db"] - want["power_db"]).max() < 0.15     # against the NOISE-FREE closed form: the noise's share
+    # ... and against the float64 DFT of the emitters' own buffers (noise included): a record whose bin is at or above its buffer's
+    # mean power is held to the dB bar of tolerances.py, the others to the sanity bound of tests/test_parity_gpu.py
+    # (every eighth emitter: 512 buffers of the 4096, so that the reference stays a second's work)
+    sel = np.asarray(centres, np.int64)[::8]
+    xs = x[torch.from_numpy(sel).to(dev)].cpu().numpy().view(np.complex64).reshape(len(sel), N)
+    X = np.fft.fft((xs * window[None, :]).astype(np.complex128), axis=1)
+    P = X.real ** 2 + X.imag ** 2
+    rec = whole[np.isin(whole["seq_id"].astype(np.int64), sel)]
+    assert len(rec) == 7 * len(sel)
+    row = np.searchsorted(sel, rec["seq_id"].astype(np.int64))
+    j = (rec["i"].astype(np.int64) + N // 2) % N
+    db64 = 5.0 * np.log10(P[row, j])
+    err = np.abs(rec["power_db"].astype(np.float64) - db64)
+    big = P[row, j] >= tol.DB_MIN_POWER_RATIO * P.mean(axis=1)[row]
+    assert big.any() and np.all(err[big] <= tol.DB_REL * np.abs(db64[big]) + tol.DB_ABS), float(err[big].max())
+    assert err.max() < 2e-2
     sid, i = whole["seq_id"].astype(np.int64), whole["i"].astype(np.int64)
     assert np.all((np.diff(sid) > 0) | ((np.diff(sid) == 0) & (np.diff(i) > 0)))   # global (centre, i) order
 

@@ -170,14 +170,17 @@ def flip_unsafe(db_ref, threshold, margin=4.0):
 
 
 def evaluated_mask(n, use_bandwidth=0.75, dc_ignore_bins=4):
-    """Boolean [n] over natural bin j: True where process.cpp:46-52 evaluates the bin."""
+    """Boolean [n] over natural bin j: True where process.cpp:46-52 evaluates the bin.  Walked over i with j = (i + n / 2) % n as
+    the reference does: at odd n that map's inverse is i = (j + n - n / 2) % n, not (j + n / 2) % n, so a mask built from j (as this
+    function did until tests/test_evaluated_mask_cpu.py) sat one bin off at 17, 1023, 4097, 65535; at even n the two agree."""
     half = n // 2
     use_window = int(use_bandwidth * n / 2.0)
-    j = np.arange(n)
-    i = (j + half) % n
-    skip = (j < dc_ignore_bins) | ((n - j) < dc_ignore_bins)
-    skip |= (i < (half - use_window)) | (i > (half + use_window))
-    return ~skip
+    i = np.arange(n)
+    j = (i + half) % n
+    keep = ~((j < dc_ignore_bins) | ((n - j) < dc_ignore_bins) | (i < (half - use_window)) | (i > (half + use_window)))
+    m = np.zeros(n, bool)
+    m[j[keep]] = True
+    return m
 
 
 def pick_threshold(db_ref, n, start, use_bandwidth=0.75, dc_ignore_bins=4):
