@@ -38,7 +38,9 @@ extern "C" {
                              5: scn_welch_desc.sample_kind / enob / correct_dc (carved out of its reserved words: same size, zero = the
                              version-4 behaviour), scn_welch_partition, scn_gather_post, scn_gather_wait;
                              6: scn_plan_desc.average / average_layout (carved out of its reserved words: same size, zero = the
-                             version-5 behaviour), SCN_AVG_*, scn_plan_average_parts */
+                             version-5 behaviour), SCN_AVG_*, scn_plan_average_parts;
+                             still 6 (additions only, nothing existing changes): scn_signal, scn_collect_signals,
+                             scn_signals_from_hits */
 
 /* status codes */
 enum {
@@ -151,6 +153,24 @@ enum {
   SCN_AVG_SWEEPS = 1  /* group g = buffers g, g + G, ..., g + (K-1)*G: K whole sweeps of a G-centre table back to back */
 };
 
+/* Signals (scn_collect_signals, scn_signals_from_hits): runs of nearby hits merged into one record each.  A plan's buffer is
+ * its unit of output (for an averaged plan: the group).  The hits of one unit, in increasing i, are split into signals: a hit
+ * starts a new signal when it is the unit's first hit or when its i exceeds the previous hit's i by more than max_gap + 1.
+ * max_gap = 0 therefore merges strictly adjacent bins only; max_gap = g bridges up to g bins that are not hits, whether they lie
+ * below the threshold or are masked out.  The DC mask removes 2*dc_ignore_bins - 1 bins around i = N/2 (7 at the default of 4),
+ * so a signal straddling DC is reported as two unless max_gap >= 7.  A signal never spans two units.  The list is ordered by
+ * (unit, first_i).  There is deliberately no summed or mean power: a float sum would depend on the order of summation, and
+ * every field here is a pure function of the hit list, built from integers and float comparisons only. */
+typedef struct scn_signal { /* 40 bytes */
+  uint64_t seq_id;         /* of the buffer (the group's first buffer), as in scn_hit */
+  uint64_t peak_freq_hz;   /* freq_hz of the peak hit, bit for bit what its scn_hit carries */
+  uint32_t first_i, last_i; /* fftshift-ordered bins of the signal's first and last hit */
+  uint32_t peak_i;         /* the hit with the largest power_db; equal powers: the lowest i */
+  uint32_t n_hits;         /* hits in the signal (<= last_i - first_i + 1; equal when max_gap = 0) */
+  float peak_power_db;     /* that hit's power_db, bit for bit */
+  uint32_t bandwidth_hz;   /* (last_i - first_i + 1) * (sample_rate / n), uint32 arithmetic as process.cpp:39 */
+} scn_signal;
+
 #define SCN_DC_IGNORE_NONE 0xffffffffu
 /* Submits a plan can have in flight (submit ... collect per slot).  Two cover kernel-only pipelines; with the ordered records
  * fetched every step a submit's chain is kernel + list + DMA + the caller's copy, and three or four in flight keep the GPU fed. */
@@ -242,6 +262,22 @@ SCN_API int scn_collect_more(scn_plan *plan, int slot, uint32_t first, scn_hit *
 /* Zero-copy alternative to the hits argument of scn_collect: the plan's own pinned copy of the ordered list
  * (min(n_hits, max_hits) records), valid from scn_collect until the slot's next submit. */
 SCN_API int scn_hits_view(scn_plan *plan, int slot, const scn_hit **hits, uint32_t *n);
+
+/* Signals of the slot's last COLLECTED submit (same validity as scn_collect_more: until the slot's next submit /
+ * scn_plan_set_table).  Built on the GPU from ALL of the submit's hits, however many (not limited by max_hits).
+ * Stores records [first, first + cap) of the ordered signal list; *n_signals = the total.  SCN_E_TRUNCATED when
+ * first + cap < total (the records stored are valid), signals may be NULL with cap 0 to learn the total.
+ * Frequency-domain plans with SCN_OUT_HITS only (SCN_E_INVALID otherwise); a pending slot, or one whose list is no
+ * longer valid, is SCN_E_STATE.  Runs beside pending submits of other slots without disturbing them. */
+SCN_API int scn_collect_signals(scn_plan *plan, int slot, uint32_t max_gap, uint32_t first,
+                                scn_signal *signals, uint32_t cap, uint32_t *n_signals);
+
+/* The same merge on a host hit list ordered as scn_collect returns it (for a gathered list on the root, and the
+ * definition the GPU form is held to).  Needs no device.  A unit ends where seq_id changes or i does not increase.
+ * n and sample_rate are the plan's (bandwidth_hz).  Stores the first min(total, cap) records, *n_signals = the total;
+ * SCN_E_TRUNCATED when cap < total; signals may be NULL with cap 0. */
+SCN_API int scn_signals_from_hits(const scn_hit *hits, uint64_t n_hits, uint32_t n, uint32_t sample_rate,
+                                  uint32_t max_gap, scn_signal *signals, uint64_t cap, uint64_t *n_signals);
 
 /* Time-domain plans (mode = SCN_MODE_TIME_DOMAIN; ProcessSamples::DoTimeDomainThresholding,
  * process.cpp:203-237): wait for the slot's submit and fetch, per buffer, the maximum and

@@ -32,6 +32,10 @@ BYTES_PER_SAMPLE = {KIND_BYTE_COMPLEX: 2, KIND_SHORT: 4, KIND_SHORT_COMPLEX: 4, 
 # struct scn_hit
 HIT_DTYPE = np.dtype([("seq_id", "<u8"), ("i", "<u4"), ("power_db", "<f4"), ("freq_hz", "<u8")], align=True)
 assert HIT_DTYPE.itemsize == 24
+# struct scn_signal
+SIGNAL_DTYPE = np.dtype([("seq_id", "<u8"), ("peak_freq_hz", "<u8"), ("first_i", "<u4"), ("last_i", "<u4"), ("peak_i", "<u4"),
+                         ("n_hits", "<u4"), ("peak_power_db", "<f4"), ("bandwidth_hz", "<u4")], align=True)
+assert SIGNAL_DTYPE.itemsize == 40
 
 
 class PlanDesc(C.Structure):
@@ -96,6 +100,8 @@ SYMBOLS = {
     "scn_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, C.POINTER(C.c_uint32), _vp]),
     "scn_collect_more": (C.c_int, [_vp, C.c_int, C.c_uint32, _vp, C.c_uint32, C.POINTER(C.c_uint32)]),
     "scn_hits_view": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint32)]),
+    "scn_collect_signals": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "scn_signals_from_hits": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "scn_collect_time_domain": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "scn_convert_raw": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "scn_wait": (C.c_int, [_vp, C.c_int]),
@@ -195,6 +201,21 @@ def gather_layout(per_rank):
     off = np.empty(per_rank.size + 1, np.uint64)
     check(lib().scn_gather_layout(per_rank.ctypes.data_as(_vp), per_rank.size, off.ctypes.data_as(_vp)), "scn_gather_layout")
     return off
+
+
+def signals_from_hits(hits, n, sample_rate, max_gap=0):
+    """scn_signals_from_hits: the hits of a list ordered as collect returns it (HIT_DTYPE), merged into signals (SIGNAL_DTYPE);
+    n and sample_rate are the plan's.  Needs no device: the merge a root runs on a gathered list."""
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    L, total = lib(), C.c_uint64()
+    st = L.scn_signals_from_hits(hits.ctypes.data_as(_vp), hits.size, int(n), int(sample_rate), int(max_gap), None, 0, C.byref(total))
+    if st != E_TRUNCATED:
+        check(st, "scn_signals_from_hits")
+    out = np.zeros(total.value, SIGNAL_DTYPE)
+    if total.value:
+        check(L.scn_signals_from_hits(hits.ctypes.data_as(_vp), hits.size, int(n), int(sample_rate), int(max_gap),
+                                      out.ctypes.data_as(_vp), out.size, C.byref(total)), "scn_signals_from_hits")
+    return out
 
 
 def hackrf_sweep_fixup(transfer, scan_offset_hz=0):

@@ -107,6 +107,11 @@ struct Slot {
   uint32_t total_hits = 0;          // of the last collected submit
   scn_hit *d_window = nullptr;      // [d_window_cap] scratch of scn_collect_more
   uint32_t d_window_cap = 0;
+  // scn_collect_signals: signals per unit and their exclusive scan ([max_batch], [max_batch + 1]; allocated at the first call),
+  // and the window of records the build kernel writes before they are copied out (grown on demand, like d_window)
+  uint32_t *d_sig_counts = nullptr, *d_sig_offsets = nullptr;
+  scn_signal *d_sig_window = nullptr;
+  uint32_t d_sig_window_cap = 0;
   hipEvent_t done = nullptr;
   bool pending = false;
   uint32_t n_buffers = 0;
@@ -791,6 +796,9 @@ void free_slot(Slot &s) {
   if (s.h_td) (void)hipHostFree(s.h_td);
   if (s.d_offsets) (void)hipFree(s.d_offsets);
   if (s.d_window) (void)hipFree(s.d_window);
+  if (s.d_sig_counts) (void)hipFree(s.d_sig_counts);
+  if (s.d_sig_offsets) (void)hipFree(s.d_sig_offsets);
+  if (s.d_sig_window) (void)hipFree(s.d_sig_window);
   if (s.h_meta) (void)hipHostFree(s.h_meta);
   if (s.h_list) (void)hipHostFree(s.h_list);
   if (s.done) (void)hipEventDestroy(s.done);
@@ -1256,6 +1264,103 @@ int scn_collect_more(scn_plan *p, int slot, uint32_t first, scn_hit *hits, uint3
   SCN_HIP(hipMemcpyAsync(hits, s.d_window, sizeof(scn_hit) * want, hipMemcpyDeviceToHost, side));
   SCN_HIP(hipStreamSynchronize(side));
   *n_written = want;
+  return SCN_OK;
+}
+
+int scn_collect_signals(scn_plan *p, int slot, uint32_t max_gap, uint32_t first, scn_signal *signals, uint32_t cap, uint32_t *n_signals) {
+  int st = check_slot(p, slot);
+  if (st) return st;
+  if (!n_signals) return fail(SCN_E_INVALID, "null argument");
+  *n_signals = 0;
+  if (!signals && cap) return fail(SCN_E_INVALID, "null signals with cap %u", cap);
+  if (p->d.mode != SCN_MODE_FREQUENCY_DOMAIN) return fail(SCN_E_INVALID, "time-domain plan: it has no hits to merge");
+  if (!(p->d.flags & SCN_OUT_HITS)) return fail(SCN_E_INVALID, "plan was created without SCN_OUT_HITS");
+  Slot &s = p->slot[slot];
+  if (s.pending || !s.list_valid) return fail(SCN_E_STATE, "slot %d: no collected submit whose hit list is still on the device", slot);
+  if (s.total_hits == 0) return SCN_OK;
+  SCN_HIP(hipSetDevice(p->d.device_id));
+  if ((st = fetch_list(p, s, 0))) return st;  // (the hits' offsets come from the scan: wait for it)
+  if (!s.d_sig_counts) SCN_HIP(hipMalloc(&s.d_sig_counts, sizeof(uint32_t) * (size_t)p->d.max_batch));
+  if (!s.d_sig_offsets) SCN_HIP(hipMalloc(&s.d_sig_offsets, sizeof(uint32_t) * ((size_t)p->d.max_batch + 1u)));
+  const ScnCompactArgs c = compact_args(p, s, 0, 0, nullptr);
+  ScnSignalArgs a = {};
+  a.regions = c.regions;
+  a.hit_region = c.hit_region;
+  a.offsets = c.offsets;
+  a.center_freq = c.center_freq;
+  a.seq_id = c.seq_id;
+  a.table_count = c.table_count;
+  a.table_first = c.table_first;
+  a.n_buffers = c.n_buffers;
+  a.n = c.n;
+  a.sample_rate = c.sample_rate;
+  a.max_gap = max_gap;
+  a.sig_counts = s.d_sig_counts;
+  a.sig_offsets = s.d_sig_offsets;
+  ScnCompactArgs scan = c;  // the scan kernel as it is, on the signal counts
+  scan.counts = s.d_sig_counts;
+  scan.offsets = s.d_sig_offsets;
+  hipStream_t side = topup_stream_of(p, s);  // (nothing queued there: pending slots are not disturbed)
+  SCN_HIP(scn_launch_signal_count(a, side));
+  SCN_HIP(scn_launch_hit_scan(scan, side));
+  uint32_t total = 0;
+  SCN_HIP(hipMemcpyAsync(&total, s.d_sig_offsets + s.n_buffers, sizeof(uint32_t), hipMemcpyDeviceToHost, side));
+  SCN_HIP(hipStreamSynchronize(side));
+  *n_signals = total;
+  const uint32_t want = first < total ? std::min(cap, total - first) : 0u;
+  if (want) {
+    if (s.d_sig_window_cap < want) {
+      if (s.d_sig_window) (void)hipFree(s.d_sig_window);
+      s.d_sig_window = nullptr;
+      s.d_sig_window_cap = 0;
+      SCN_HIP(hipMalloc(&s.d_sig_window, sizeof(scn_signal) * (size_t)want));
+      s.d_sig_window_cap = want;
+    }
+    a.out = s.d_sig_window;
+    a.first = first;
+    a.out_cap = want;  // (first + want <= total <= the hits' total < 2^31: no wrap)
+    SCN_HIP(scn_launch_signal_build(a, side));
+    SCN_HIP(hipMemcpyAsync(signals, s.d_sig_window, sizeof(scn_signal) * (size_t)want, hipMemcpyDeviceToHost, side));
+    SCN_HIP(hipStreamSynchronize(side));
+  }
+  if ((uint64_t)first + cap < total)
+    return fail(SCN_E_TRUNCATED, "%u signals, records [%u, %u) returned: call again with a later first", total, first, first + want);
+  return SCN_OK;
+}
+
+int scn_signals_from_hits(const scn_hit *hits, uint64_t n_hits, uint32_t n, uint32_t sample_rate, uint32_t max_gap, scn_signal *signals,
+                          uint64_t cap, uint64_t *n_signals) {
+  if (!n_signals) return fail(SCN_E_INVALID, "null argument");
+  *n_signals = 0;
+  if ((!hits && n_hits) || (!signals && cap)) return fail(SCN_E_INVALID, "null argument");
+  if (n == 0) return fail(SCN_E_INVALID, "n = 0");
+  const uint32_t bin_step = sample_rate / n;  // process.cpp:39 (truncating)
+  uint64_t total = 0;
+  scn_signal cur = {};
+  for (uint64_t k = 0; k < n_hits; k++) {
+    const scn_hit &h = hits[k];
+    const bool start = k == 0 || h.seq_id != hits[k - 1].seq_id || h.i <= hits[k - 1].i ||  // a new unit
+                       (uint64_t)h.i - hits[k - 1].i > (uint64_t)max_gap + 1u;
+    if (start) {
+      if (k && total <= cap) signals[total - 1] = cur;
+      total++;
+      cur.seq_id = h.seq_id;
+      cur.first_i = cur.peak_i = h.i;
+      cur.peak_power_db = h.power_db;
+      cur.peak_freq_hz = h.freq_hz;
+      cur.n_hits = 0;
+    } else if (h.power_db > cur.peak_power_db) {  // (equal powers: the lowest i stays)
+      cur.peak_i = h.i;
+      cur.peak_power_db = h.power_db;
+      cur.peak_freq_hz = h.freq_hz;
+    }
+    cur.last_i = h.i;
+    cur.n_hits++;
+    cur.bandwidth_hz = (cur.last_i - cur.first_i + 1u) * bin_step;
+  }
+  if (total && total <= cap) signals[total - 1] = cur;
+  *n_signals = total;
+  if (total > cap) return fail(SCN_E_TRUNCATED, "%llu signals, the first %llu returned", (unsigned long long)total, (unsigned long long)cap);
   return SCN_OK;
 }
 

@@ -20,6 +20,9 @@
 // running FFT launch ~30 us, in its shadow either way, so a collect call is an event wait plus a copy out of pinned
 // memory.  The output window [first, first + out_cap) lets a caller with a small buffer walk an arbitrarily long list
 // (scn_collect_more) -- nothing is ever dropped on the device.
+//
+// The same bitmap, one step further, merges runs of nearby hits into signal records (scn_collect_signals): the second half of
+// this file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -220,6 +223,192 @@ __global__ __launch_bounds__(kTotalThreads) void scn_hit_total_kernel(const uint
   }
 }
 
+// ---- Signals: runs of nearby hits merged into one record each (scanner_hip.h, "Signals") --------------------------------------
+// The same ingredients as the ordered list -- a unit's hit bitmap in LDS, built from its region whatever max_hits is, and the
+// scan above -- taken one step further.  A set bit STARTS a signal when the max_gap + 1 bits below it are clear; the number of
+// start bits at or below a hit's bin is the hit's signal.  Two kernels around scn_hit_scan_kernel, one wave per unit with hits:
+//   scn_signal_count_kernel  bitmap -> start bits -> the unit's number of signals
+//   (scn_hit_scan_kernel on those counts: the unit's first signal in the batch's list, and the total)
+//   scn_signal_build_kernel  bitmap and start bits again, a prefix of the start bits per word; every record of the region is
+//                            folded into its signal's LDS state with integer atomics (a 64-bit key for the peak: the power's
+//                            bits in float order, then the inverted bin, so that equal powers leave the lowest bin; the count;
+//                            the lowest and highest bin), and the lanes write the completed 40-byte records of the window.
+// No float arithmetic and no float atomics: the result does not depend on the order of the records inside a region.  A unit of
+// N bins can hold N/2 signals, more than fits beside the bitmap at the large sizes, so the per-signal state covers a CHUNK of
+// consecutive signals at a time and a unit with more signals than that walks its region once per chunk (only the chunks inside
+// the output window); the launcher trades waves per workgroup for chunk size inside 48 KiB of LDS, the room a resident
+// 4096-point FFT launch leaves (above).
+
+// a bitmap word's start bits.  g1 = max_gap + 1 >= 1; dist = positions from the last set bit BEFORE this word up to the word's
+// bit 0 (1: bit 31 of the word before; 0xffffffff: there is none)
+__device__ __forceinline__ uint32_t scn_start_bits(uint32_t word, uint32_t g1, uint32_t dist) {
+  uint32_t covered;  // bits that have a set bit of this word among the g1 positions below them
+  if (g1 >= 32u) {   // everything above the word's lowest set bit
+    const uint32_t low = word & (0u - word);
+    covered = ~(low | (low - 1u));
+  } else {           // the set bits smeared over shifts 1 .. g1, doubling
+    uint32_t cov = 1u;
+    covered = word << 1;
+    while (cov * 2u <= g1) {
+      covered |= covered << cov;
+      cov *= 2u;
+    }
+    covered |= covered << (g1 - cov);
+  }
+  if (dist <= g1) {  // ... or the last set bit of the words before: it reaches bits 0 .. g1 - dist
+    const uint32_t reach = g1 - dist + 1u;
+    covered |= reach >= 32u ? 0xffffffffu : (1u << reach) - 1u;
+  }
+  return word & ~covered;
+}
+
+// One wave: the unit's hit bitmap, its start bits per word (sbits) and the start bits in the words before each word (sbelow), all
+// in LDS; returns the unit's number of signals in every lane.  The lanes own contiguous runs of words, as in the compaction.
+__device__ __forceinline__ uint32_t scn_unit_signals(const ScnDevHit *region, uint32_t stored, uint32_t n, uint32_t words, uint32_t g1,
+                                                     uint32_t lane, uint32_t *bits, uint32_t *sbits, uint32_t *sbelow) {
+  const uint32_t per_lane = (words + 63u) / 64u;
+  for (uint32_t w = lane; w < words; w += 64u) bits[w] = 0u;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  for (uint32_t k = lane; k < stored; k += 64u) {
+    const uint32_t i = region[k].i;
+    if (i < n) atomicOr(&bits[i >> 5], 1u << (i & 31u));
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // the last set bit before each lane's run of words: position + 1 (0: none), an exclusive max-scan over the lanes
+  uint32_t top = 0;
+  for (uint32_t k = 0; k < per_lane; k++) {
+    const uint32_t w = lane * per_lane + k;
+    if (w < words && bits[w]) top = w * 32u + 32u - (uint32_t)__clz(bits[w]);
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t v = __shfl_up(top, off, 64);
+    if (lane >= (uint32_t)off && v > top) top = v;
+  }
+  uint32_t last1 = __shfl_up(top, 1, 64);
+  if (lane == 0) last1 = 0;
+  uint32_t mine = 0;
+  for (uint32_t k = 0; k < per_lane; k++) {
+    const uint32_t w = lane * per_lane + k;
+    if (w < words) {
+      const uint32_t word = bits[w];
+      const uint32_t sb = scn_start_bits(word, g1, last1 ? w * 32u + 1u - last1 : 0xffffffffu);
+      sbits[w] = sb;
+      mine += (uint32_t)__popc(sb);
+      if (word) last1 = w * 32u + 32u - (uint32_t)__clz(word);
+    }
+  }
+  uint32_t incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t v = __shfl_up(incl, off, 64);
+    if (lane >= (uint32_t)off) incl += v;
+  }
+  uint32_t run = incl - mine;
+  for (uint32_t k = 0; k < per_lane; k++) {
+    const uint32_t w = lane * per_lane + k;
+    if (w < words) {
+      sbelow[w] = run;
+      run += (uint32_t)__popc(sbits[w]);
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  return (uint32_t)__shfl(incl, 63, 64);
+}
+
+// (workgroups of 64 .. 256 threads, no s_setprio: as the kernels above, these run beside the next FFT launch)
+__global__ __launch_bounds__(256) void scn_signal_count_kernel(ScnSignalArgs a) {
+  extern __shared__ uint32_t smem[];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  const uint32_t words = (a.n + 31u) / 32u;
+  uint32_t *const bits = smem + (size_t)wave * a.wave_words;
+  const uint32_t g1 = (a.max_gap < 65536u ? a.max_gap : 65536u) + 1u;  // (a gap of n bins or more bridges everything)
+  for (uint32_t b = blockIdx.x * waves + wave; b < a.n_buffers; b += gridDim.x * waves) {
+    const uint32_t o0 = a.offsets[b], o1 = a.offsets[b + 1u];
+    const uint32_t c = o1 - o0;
+    uint32_t signals = 0;
+    if (c) signals = scn_unit_signals(a.regions + (size_t)b * a.hit_region, c < a.hit_region ? c : a.hit_region, a.n, words, g1, lane, bits,
+                                      bits + words, bits + 2u * words);
+    if (lane == 0) a.sig_counts[b] = signals;
+  }
+}
+
+__global__ __launch_bounds__(256) void scn_signal_build_kernel(ScnSignalArgs a) {
+  extern __shared__ uint32_t smem[];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  const uint32_t words = (a.n + 31u) / 32u;
+  uint32_t *const bits = smem + (size_t)wave * a.wave_words;  // (wave_words and map_words are even: the keys are 8-byte aligned)
+  uint32_t *const sbits = bits + words, *const sbelow = sbits + words;
+  unsigned long long *const key = reinterpret_cast<unsigned long long *>(bits + a.map_words);  // [chunk] per-signal state
+  uint32_t *const cnt = bits + a.map_words + 2u * a.chunk, *const lo = cnt + a.chunk, *const hi = lo + a.chunk;
+  const uint32_t g1 = (a.max_gap < 65536u ? a.max_gap : 65536u) + 1u;
+  const uint32_t bin_step = a.sample_rate / a.n;  // process.cpp:39 (truncating)
+  const uint32_t last = a.first + a.out_cap;      // exclusive (no wrap: checked by the caller)
+  scn_signal *const out = static_cast<scn_signal *>(a.out);
+  for (uint32_t b = blockIdx.x * waves + wave; b < a.n_buffers; b += gridDim.x * waves) {
+    const uint32_t s0 = a.sig_offsets[b], s1 = a.sig_offsets[b + 1u];
+    if (s1 == s0 || s0 >= last || s1 <= a.first) continue;  // no signals, or none of this unit's inside the window
+    const uint32_t o0 = a.offsets[b], o1 = a.offsets[b + 1u];
+    const double fc = a.center_freq[a.table_count ? (uint32_t)(((uint64_t)a.table_first + b) % a.table_count) : b];
+    const uint64_t seq = a.seq_id ? a.seq_id[b] : (uint64_t)b;
+    const ScnDevHit *const region = a.regions + (size_t)b * a.hit_region;
+    const uint32_t c = o1 - o0, stored = c < a.hit_region ? c : a.hit_region;
+    scn_unit_signals(region, stored, a.n, words, g1, lane, bits, sbits, sbelow);
+    const double start_frequency = fc - (double)(a.sample_rate / 2u);  // process.cpp:38 (uint32 division)
+    // the unit's signals inside the window, [from, to) counted from the unit's first, a chunk at a time
+    const uint32_t from = (a.first > s0 ? a.first : s0) - s0, to = (last < s1 ? last : s1) - s0;
+    for (uint32_t base = from; base < to; base += a.chunk) {
+      const uint32_t nc = to - base < a.chunk ? to - base : a.chunk;
+      for (uint32_t j = lane; j < nc; j += 64u) {
+        key[j] = 0ull;
+        cnt[j] = 0u;
+        lo[j] = 0xffffffffu;
+        hi[j] = 0u;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      for (uint32_t k = lane; k < stored; k += 64u) {
+        const ScnDevHit h = region[k];
+        if (h.i >= a.n) continue;
+        const uint32_t w = h.i >> 5, bit = h.i & 31u;
+        const uint32_t j = sbelow[w] + (uint32_t)__popc(sbits[w] & (0xffffffffu >> (31u - bit))) - 1u - base;  // its signal, in this chunk
+        if (j >= nc) continue;
+        // the power's bits in float order (-0.0 ranks as +0.0, which it equals, and is marked so that it comes back as it was)
+        uint32_t u = __float_as_uint(h.power_db);
+        const uint32_t neg_zero = u == 0x80000000u ? 1u : 0u;
+        if (neg_zero) u = 0u;
+        const uint32_t ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        atomicMax(&key[j], ((unsigned long long)ord << 32) | ((unsigned long long)(0xffffu - h.i) << 16) | neg_zero);
+        atomicAdd(&cnt[j], 1u);
+        atomicMin(&lo[j], h.i);
+        atomicMax(&hi[j], h.i);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      for (uint32_t j = lane; j < nc; j += 64u) {
+        const unsigned long long kk = key[j];
+        const uint32_t ord = (uint32_t)(kk >> 32), peak_i = 0xffffu - ((uint32_t)(kk >> 16) & 0xffffu);
+        const uint32_t u = (kk & 1ull) ? 0x80000000u : (ord & 0x80000000u) ? (ord ^ 0x80000000u) : ~ord;
+        const double frequency = start_frequency + (double)(uint32_t)(peak_i * bin_step);  // process.cpp:55
+        scn_signal r;
+        r.seq_id = seq;
+        r.peak_freq_hz = to_u64_like_x86(frequency);  // process.cpp:57
+        r.first_i = lo[j];
+        r.last_i = hi[j];
+        r.peak_i = peak_i;
+        r.n_hits = cnt[j];
+        r.peak_power_db = __uint_as_float(u);
+        r.bandwidth_hz = (hi[j] - lo[j] + 1u) * bin_step;
+        out[s0 + base + j - a.first] = r;
+      }
+      __builtin_amdgcn_wave_barrier();  // the state is reused by the next chunk, the maps by this wave's next unit
+    }
+  }
+}
+
 }  // namespace
 
 hipError_t scn_launch_hit_total(const uint32_t *counts, uint32_t n_buffers, uint32_t trigger_count, unsigned long long *acc, unsigned long long *host_total,
@@ -241,5 +430,48 @@ hipError_t scn_launch_hit_compact(const ScnCompactArgs &a, hipStream_t stream) {
   uint32_t blocks = (a.n_buffers + 3u) / 4u;
   if (blocks > 8192u) blocks = 8192u;
   hipLaunchKernelGGL(scn_hit_compact_kernel, dim3(blocks), dim3(256), lds, stream, a);
+  return hipGetLastError();
+}
+
+// waves per workgroup, signals per chunk and LDS of the signal kernels for n-point units: the most waves (4, 2, 1) whose share of
+// 48 KiB holds the three maps and at least 256 signals' state (20 bytes each); no more state than the unit can have signals
+static void signal_geometry(ScnSignalArgs &a, uint32_t *waves, size_t *lds) {
+  const uint32_t words = (a.n + 31u) / 32u;
+  a.map_words = (3u * words + 1u) & ~1u;
+  const uint32_t most = (((a.n + 1u) / 2u) + 63u) & ~63u;  // signals a unit can have, in whole waves of lanes
+  uint32_t w = 4u, chunk = 0;
+  for (;; w >>= 1) {
+    const uint32_t budget = (48u * 1024u / 4u) / w;  // words per wave
+    chunk = budget > a.map_words ? ((budget - a.map_words) / 5u) & ~63u : 0u;
+    if (chunk >= (most < 256u ? most : 256u) || w == 1u) break;
+  }
+  a.chunk = chunk < most ? chunk : most;
+  a.wave_words = a.map_words + 5u * a.chunk;
+  *waves = w;
+  *lds = (size_t)w * a.wave_words * sizeof(uint32_t);
+}
+
+hipError_t scn_launch_signal_count(const ScnSignalArgs &args, hipStream_t stream) {
+  if (args.n_buffers == 0) return hipSuccess;
+  ScnSignalArgs a = args;
+  uint32_t waves;
+  size_t lds;
+  signal_geometry(a, &waves, &lds);
+  uint32_t blocks = (a.n_buffers + waves - 1u) / waves;
+  if (blocks > 8192u) blocks = 8192u;
+  hipLaunchKernelGGL(scn_signal_count_kernel, dim3(blocks), dim3(64u * waves), lds, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t scn_launch_signal_build(const ScnSignalArgs &args, hipStream_t stream) {
+  if (args.n_buffers == 0 || args.out_cap == 0) return hipSuccess;
+  ScnSignalArgs a = args;
+  uint32_t waves;
+  size_t lds;
+  signal_geometry(a, &waves, &lds);
+  if (a.chunk == 0) return hipErrorInvalidValue;
+  uint32_t blocks = (a.n_buffers + waves - 1u) / waves;
+  if (blocks > 8192u) blocks = 8192u;
+  hipLaunchKernelGGL(scn_signal_build_kernel, dim3(blocks), dim3(64u * waves), lds, stream, a);
   return hipGetLastError();
 }

@@ -116,6 +116,27 @@ struct ScnCompactArgs {
 };
 hipError_t scn_launch_hit_scan(const ScnCompactArgs &args, hipStream_t stream);
 hipError_t scn_launch_hit_compact(const ScnCompactArgs &args, hipStream_t stream);
+// Signals (scn_hits.hip): the units' hits, where the FFT kernels and the scan above left them, merged into one scn_signal per run
+// of hits no more than max_gap non-hit bins apart.  scn_launch_signal_count writes each unit's number of signals,
+// scn_launch_hit_scan (counts = sig_counts, offsets = sig_offsets) turns them into offsets and the total, and
+// scn_launch_signal_build writes the records [first, first + out_cap) of the batch's ordered signal list to `out`.
+struct ScnSignalArgs {
+  const ScnDevHit *regions;    // as ScnCompactArgs: regions, the hits' offsets (the scan's output) and the submit's header fields
+  uint32_t hit_region;
+  const uint32_t *offsets;     // [n_buffers + 1]
+  const double *center_freq;
+  const uint64_t *seq_id;
+  uint32_t table_count, table_first;
+  uint32_t n_buffers, n, sample_rate;
+  uint32_t max_gap;
+  uint32_t *sig_counts;        // [n_buffers] signals per unit (the count kernel's output)
+  const uint32_t *sig_offsets; // [n_buffers + 1] their exclusive prefix sums, the total last (the build kernel's input)
+  void *out;                   // scn_signal[out_cap]
+  uint32_t first, out_cap;     // first + out_cap must not wrap
+  uint32_t map_words, chunk, wave_words;  // LDS layout per wave, filled in by the launchers
+};
+hipError_t scn_launch_signal_count(const ScnSignalArgs &args, hipStream_t stream);
+hipError_t scn_launch_signal_build(const ScnSignalArgs &args, hipStream_t stream);
 // sum of counts[0, n_buffers) -> *host_total (pinned host memory); acc: two zeroed device words the kernel leaves zeroed
 hipError_t scn_launch_hit_total(const uint32_t *counts, uint32_t n_buffers, uint32_t trigger_count, unsigned long long *acc, unsigned long long *host_total,
                                 uint32_t *trigger_bits, hipStream_t stream);

@@ -232,6 +232,25 @@ class Plan:
             done += got.value
         return out[:done]
 
+    def collect_signals(self, slot, max_gap=0, first=0, cap=None):
+        """scn_collect_signals: the hits of the slot's last collected submit merged into signals on the GPU (SIGNAL_DTYPE array,
+        ordered by (buffer, first_i); every hit takes part, however many the plan's max_hits keeps).  A run of hits no more
+        than max_gap non-hit bins apart is one signal.  cap=None returns records [first, end) (one call for the total, one for
+        the records); with an explicit cap the C-ABI's own behaviour shows: ScannerError(E_TRUNCATED) when first + cap falls
+        short of the total."""
+        total = C.c_uint32()
+        if cap is None:
+            st = self._L.scn_collect_signals(self._h, slot, int(max_gap), int(first), None, 0, C.byref(total))
+            if st != capi.E_TRUNCATED:
+                capi.check(st, "scn_collect_signals")
+            cap = max(0, total.value - int(first))
+        out = np.zeros(cap, capi.SIGNAL_DTYPE)
+        if cap:
+            capi.check(self._L.scn_collect_signals(self._h, slot, int(max_gap), int(first), out.ctypes.data_as(C.c_void_p), cap,
+                                                   C.byref(total)), "scn_collect_signals")
+        self.last_n_signals = total.value
+        return out[: max(0, min(cap, total.value - int(first)))]
+
     def hits_view(self, slot):
         """Zero-copy numpy view of the plan's pinned ordered hit list (valid until the slot's next submit)."""
         ptr, n = C.c_void_p(), C.c_uint32()
