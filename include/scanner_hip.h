@@ -40,7 +40,9 @@ extern "C" {
                              6: scn_plan_desc.average / average_layout (carved out of its reserved words: same size, zero = the
                              version-5 behaviour), SCN_AVG_*, scn_plan_average_parts;
                              still 6 (additions only, nothing existing changes): scn_signal, scn_collect_signals,
-                             scn_signals_from_hits */
+                             scn_signals_from_hits; scn_plan_desc.detect / floor_permille (carved out of its reserved words: same
+                             size, zero = the fixed threshold), SCN_DETECT_*, SCN_FLOOR_MIN, scn_collect_floor,
+                             scn_floor_from_spectrum */
 
 /* status codes */
 enum {
@@ -133,7 +135,9 @@ typedef struct scn_plan_desc {
   int32_t device_id;       /* HIP device ordinal */
   uint32_t average;        /* 0 -> 1.  K > 1: average K buffers per centre frequency before detection (below) */
   uint32_t average_layout; /* 0 -> SCN_AVG_DWELL: which buffers of a submit form a group */
-  uint32_t reserved[3];
+  uint32_t detect;         /* SCN_DETECT_*; 0 -> SCN_DETECT_FIXED: power_db > threshold */
+  uint32_t floor_permille; /* SCN_DETECT_FLOOR only: the rank of the floor among the evaluated bins, in permille (below) */
+  uint32_t reserved[1];
 } scn_plan_desc;
 
 /* Averaged plans (average = K > 1; Bartlett's method: no overlap, whole buffers).  A submit of n_buffers = K*G buffers forms G
@@ -152,6 +156,29 @@ enum {
   SCN_AVG_DWELL = 0,  /* group g = buffers g*K ... g*K + K - 1: K buffers of one centre back to back (a dwell) */
   SCN_AVG_SWEEPS = 1  /* group g = buffers g, g + G, ..., g + (K-1)*G: K whole sweeps of a G-centre table back to back */
 };
+
+/* Floor detector (detect = SCN_DETECT_FLOOR): the threshold rides on each unit's own noise floor.  A unit is a buffer (for an
+ * averaged plan: the group).  For a unit u let E be the natural bins j the mask of process.cpp:46-52 lets through (M = |E| > 0; a
+ * plan whose mask lets no bin through is SCN_E_INVALID at create).  Order the values power_db[u][j], j in E, by the unsigned key of
+ * their bits, key = (bits & 0x80000000) ? ~bits : bits | 0x80000000 -- the usual float order, with -inf lowest and -0.0 below
+ * +0.0; where a NaN falls is whatever the key gives and is not otherwise specified.  Then
+ *   r = (uint64)floor_permille * (M - 1) / 1000 in integer arithmetic, floor_db[u] = the value of rank r (permille 0 asks for the
+ *   default, 500: the median; 1000 is the maximum, SCN_FLOOR_MIN the minimum, rank 0; 1 ... 1000 are taken as they are, anything
+ *   else is SCN_E_INVALID),
+ *   cut[u] = floor_db[u] + threshold: ONE float addition -- in this mode `threshold` is an offset in the plan's own dB scale
+ *   (10*log10|X|: 10 units are 20 dB of power) --, and bin j in E is a hit iff power_db[u][j] > cut[u], strictly as everywhere
+ *   else.  A floor of -inf gives a cut of -inf, and bins at -inf are not hits.
+ * An order statistic involves no float sum, so the floor, the cut and the hit list are exact: the same bits on every run and on
+ * every route.  Records, their power_db, freq_hz, seq_id, their order and trigger (count > trigger_count) are those of a
+ * fixed-threshold plan with that cut.  Frequency-domain plans with SCN_OUT_HITS only (SCN_E_INVALID at create otherwise); every
+ * size scn_size_path supports, and averaged plans.  The transform runs as the spectrum-only plan's does and one detect kernel
+ * follows it on the spectrum it stored (a hits-only plan keeps that spectrum in a buffer of its own); scn_collect_more,
+ * scn_hits_view, scn_collect_signals and the gathers work as on any plan.  scn_collect_floor returns floor_db. */
+enum {
+  SCN_DETECT_FIXED = 0, /* power_db > threshold, one level for every unit */
+  SCN_DETECT_FLOOR = 1  /* power_db > floor_db[unit] + threshold */
+};
+#define SCN_FLOOR_MIN 0xffffffffu /* floor_permille: rank 0, the minimum (0 itself asks for the default, as SCN_DC_IGNORE_NONE) */
 
 /* Signals (scn_collect_signals, scn_signals_from_hits): runs of nearby hits merged into one record each.  A plan's buffer is
  * its unit of output (for an averaged plan: the group).  The hits of one unit, in increasing i, are split into signals: a hit
@@ -278,6 +305,18 @@ SCN_API int scn_collect_signals(scn_plan *plan, int slot, uint32_t max_gap, uint
  * SCN_E_TRUNCATED when cap < total; signals may be NULL with cap 0. */
 SCN_API int scn_signals_from_hits(const scn_hit *hits, uint64_t n_hits, uint32_t n, uint32_t sample_rate,
                                   uint32_t max_gap, scn_signal *signals, uint64_t cap, uint64_t *n_signals);
+
+/* Floor-detector plans: floor_db[u] of every unit of the slot's last COLLECTED submit (one float per buffer; per group on an
+ * averaged plan), valid as scn_collect_signals' input is: until the slot's next submit / scn_plan_set_table (SCN_E_STATE for a
+ * pending slot or one never collected).  A plan that is not in floor mode: SCN_E_INVALID. */
+SCN_API int scn_collect_floor(scn_plan *plan, int slot, float *floor_db);
+
+/* The same definition on ONE unit's host spectrum (n floats, natural bin order), with the descriptor's zero defaults for
+ * dc_ignore_bins, use_bandwidth and floor_permille: *floor_db = the value of that rank among the evaluated bins.  Needs no
+ * device; the definition the GPU form is held to.  A mask that lets no bin through, or a permille outside the descriptor's
+ * values, is SCN_E_INVALID. */
+SCN_API int scn_floor_from_spectrum(const float *power_db, uint32_t n, uint32_t dc_ignore_bins, double use_bandwidth,
+                                    uint32_t floor_permille, float *floor_db);
 
 /* Time-domain plans (mode = SCN_MODE_TIME_DOMAIN; ProcessSamples::DoTimeDomainThresholding,
  * process.cpp:203-237): wait for the slot's submit and fetch, per buffer, the maximum and

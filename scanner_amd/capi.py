@@ -23,6 +23,8 @@ DC_IGNORE_NONE = 0xFFFFFFFF
 NUM_SLOTS = 4
 ABI_VERSION = 6
 AVG_DWELL, AVG_SWEEPS = 0, 1  # scn_plan_desc.average_layout
+DETECT_FIXED, DETECT_FLOOR = 0, 1  # scn_plan_desc.detect
+FLOOR_MIN = 0xFFFFFFFF  # scn_plan_desc.floor_permille: rank 0 (0 itself asks for the default, the median)
 PATH_UNSUPPORTED, PATH_FUSED, PATH_FOUR_STEP, PATH_STAGED, PATH_BLUESTEIN = range(5)
 COMM_ID_BYTES = 128
 GATHER_TICKETS = 4
@@ -59,7 +61,9 @@ class PlanDesc(C.Structure):
         ("device_id", C.c_int32),
         ("average", C.c_uint32),
         ("average_layout", C.c_uint32),
-        ("reserved", C.c_uint32 * 3),
+        ("detect", C.c_uint32),
+        ("floor_permille", C.c_uint32),
+        ("reserved", C.c_uint32 * 1),
     ]
 
 
@@ -102,6 +106,8 @@ SYMBOLS = {
     "scn_hits_view": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_uint32)]),
     "scn_collect_signals": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.POINTER(C.c_uint32)]),
     "scn_signals_from_hits": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "scn_collect_floor": (C.c_int, [_vp, C.c_int, _vp]),
+    "scn_floor_from_spectrum": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_float)]),
     "scn_collect_time_domain": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "scn_convert_raw": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "scn_wait": (C.c_int, [_vp, C.c_int]),
@@ -216,6 +222,16 @@ def signals_from_hits(hits, n, sample_rate, max_gap=0):
         check(L.scn_signals_from_hits(hits.ctypes.data_as(_vp), hits.size, int(n), int(sample_rate), int(max_gap),
                                       out.ctypes.data_as(_vp), out.size, C.byref(total)), "scn_signals_from_hits")
     return out
+
+
+def floor_from_spectrum(power_db, dc_ignore_bins=4, use_bandwidth=0.75, floor_permille=0):
+    """scn_floor_from_spectrum: the floor detector's floor_db (np.float32) of ONE unit's dB spectrum (natural bin order) -- the value
+    of rank floor_permille * (M - 1) // 1000 among the M evaluated bins (0: the median, FLOOR_MIN: the minimum).  Needs no device."""
+    power_db = np.ascontiguousarray(power_db, np.float32).reshape(-1)
+    out = C.c_float()
+    check(lib().scn_floor_from_spectrum(power_db.ctypes.data_as(_vp), power_db.size, DC_IGNORE_NONE if dc_ignore_bins == 0 else int(dc_ignore_bins),
+                                        float(use_bandwidth), int(floor_permille), C.byref(out)), "scn_floor_from_spectrum")
+    return np.frombuffer(bytes(out), np.float32)[0]  # (the bits as they are: no detour through a Python float)
 
 
 def hackrf_sweep_fixup(transfer, scan_offset_hz=0):

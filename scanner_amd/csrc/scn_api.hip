@@ -112,6 +112,12 @@ struct Slot {
   uint32_t *d_sig_counts = nullptr, *d_sig_offsets = nullptr;
   scn_signal *d_sig_window = nullptr;
   uint32_t d_sig_window_cap = 0;
+  // floor-detector plans (scn_floor.hip): floor_db of the pending / last submit's units, kernel-written device memory and the pinned
+  // copy a DMA behind the counts' brings (scn_collect_floor reads it).  ONE generation of each is enough, unlike the regions and
+  // counts: the only reader of d_floor is that DMA, which is complete when `done` is -- and a slot is not submitted again before
+  // its collect has waited for `done` --, and h_floor is promised only until the slot's next submit.
+  float *d_floor = nullptr, *h_floor = nullptr;  // [max_batch] each
+  float *d_floor_power = nullptr;   // [max_batch][N] the spectrum the detect kernel reads when the caller keeps none (hits-only floor plans)
   hipEvent_t done = nullptr;
   bool pending = false;
   uint32_t n_buffers = 0;
@@ -171,6 +177,8 @@ struct scn_plan {
   bool direct_counts = false;
   Path path = Path::Unsupported;
   uint32_t avg = 1, avg_layout = SCN_AVG_DWELL;  // scn_plan_desc.average / average_layout with the defaults applied
+  bool floor = false;       // scn_plan_desc.detect == SCN_DETECT_FLOOR: the transform stores the spectrum only, scn_floor.hip detects on it
+  uint32_t floor_rank = 0;  // ... and the floor is the value of this rank among the hit_region evaluated bins
   uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
   double *d_twiddle64 = nullptr;     // four-step: [256][2] W_256^k; Bluestein: [fft_m][2] W_m^k; in double
   double *d_table = nullptr;         // [table_count] the plan's frequency table (scn_plan_set_table), read by the compaction kernel
@@ -370,6 +378,31 @@ hipError_t build_tables(scn_plan *p) {
   }
 }
 
+// scn_plan_desc.floor_permille with its default applied (0 -> 500, SCN_FLOOR_MIN -> 0); false for a value outside the descriptor's
+bool floor_permille_of(uint32_t given, uint32_t *permille) {
+  if (given == SCN_FLOOR_MIN) *permille = 0;
+  else if (given == 0) *permille = 500;
+  else if (given <= 1000u) *permille = given;
+  else return false;
+  return true;
+}
+
+// The mask of process.cpp:46-52 exactly as the kernels apply it (uint32 arithmetic), with the descriptor's defaults already
+// applied: i_lo / i_hi, and the number of natural bins it lets through
+uint32_t evaluated_bins(uint32_t n, uint32_t dc_ignore, double use_bandwidth, uint32_t *i_lo, uint32_t *i_hi) {
+  // process.cpp:85 m_useWindow = uint32_t(useBandWidth * numSamples / 2.0); :51 bounds in uint32
+  const uint32_t use_window = (uint32_t)(use_bandwidth * n / 2.0);
+  const struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {dc_ignore, n / 2 - use_window, n / 2 + use_window};
+  uint32_t kept = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t j = (i + n / 2) % n;
+    kept += scn_bin_evaluated(j, i, n, mask);
+  }
+  if (i_lo) *i_lo = mask.i_lo;
+  if (i_hi) *i_hi = mask.i_hi;
+  return kept;
+}
+
 int check_slot(scn_plan *p, int slot) {
   if (!p) return fail(SCN_E_INVALID, "null plan");
   if (slot < 0 || slot >= SCN_NUM_SLOTS) return fail(SCN_E_INVALID, "slot %d out of range", slot);
@@ -415,6 +448,10 @@ int ensure_slot_outputs(scn_plan *p, Slot &s, uint32_t gen) {
     if (!s.d_list) SCN_HIP(hipMalloc(&s.d_list, sizeof(scn_hit) * (size_t)p->d.max_hits));
     if (!s.h_list) SCN_HIP(hipHostMalloc(&s.h_list, sizeof(scn_hit) * (size_t)p->d.max_hits, hipHostMallocDefault));
     if (!s.kernel_done) SCN_HIP(hipEventCreateWithFlags(&s.kernel_done, hipEventDisableTiming));
+    if (p->floor) {
+      if (!s.d_floor) SCN_HIP(hipMalloc(&s.d_floor, sizeof(float) * mb));
+      if (!s.h_floor) SCN_HIP(hipHostMalloc(&s.h_floor, sizeof(float) * mb, hipHostMallocDefault));
+    }
   }
   return SCN_OK;
 }
@@ -522,7 +559,8 @@ void set_common_args(A &a, const scn_plan *p, const Slot &s, const void *d_raw, 
 int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float *d_power, uint32_t *host_hits, hipEvent_t stop) {
   const uint32_t n = p->d.n;
   const int kind = (int)p->d.sample_kind;
-  const bool hits = (p->d.flags & SCN_OUT_HITS) != 0, dc = p->d.correct_dc != 0;
+  // (a floor plan's transform reports the spectrum only: its hits come from the detect kernel behind it, launch_floor)
+  const bool hits = (p->d.flags & SCN_OUT_HITS) != 0 && !p->floor, dc = p->d.correct_dc != 0;
   if (p->avg > 1u) {  // nb buffers = nb / K groups (scn_average.hip)
     const uint32_t ng = nb / p->avg;
     if (ng && !s.d_avg_partial)
@@ -610,6 +648,26 @@ int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float
   }
 }
 
+// Floor plans: the detect kernel on the spectrum the transform has just stored, behind it on the slot's stream; nu units
+int launch_floor(scn_plan *p, Slot &s, const float *d_power, uint32_t nu) {
+  ScnFloorArgs a;
+  memset(&a, 0, sizeof(a));
+  a.power_db = d_power;
+  a.n = p->d.n;
+  a.n_units = nu;
+  a.rank = p->floor_rank;
+  a.threshold = p->d.threshold;
+  a.dc_ignore = p->d.dc_ignore_bins;
+  a.i_lo = p->i_lo;
+  a.i_hi = p->i_hi;
+  a.hits = s.d_hits[s.gen];
+  a.hit_region = p->hit_region;
+  a.counts = s.d_buf_hits[s.gen];
+  a.floor_db = s.d_floor;
+  SCN_HIP(scn_launch_floor(a, p->num_cus, s.stream));
+  return SCN_OK;
+}
+
 // Averaged plans: a submit's arguments alone decide whether it can run -- checked before any copy or kernel is queued
 int check_average(const scn_plan *p, uint32_t nb, const double *fc) {
   if (p->avg <= 1u) return SCN_OK;
@@ -679,7 +737,11 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
     if (!s.d_power) SCN_HIP(hipMalloc(&s.d_power, sizeof(float) * (size_t)n * p->d.max_batch));
     d_power = s.d_power;
   }
-  s.cur_power = d_power;
+  s.cur_power = d_power;  // (what the caller may collect)
+  if (p->floor && !d_power && nb) {  // a hits-only floor plan: the same spectrum-only transform, into a buffer the caller never sees
+    if (!s.d_floor_power) SCN_HIP(hipMalloc(&s.d_floor_power, sizeof(float) * (size_t)n * p->d.max_batch));
+    d_power = s.d_floor_power;
+  }
   s.n_buffers = nb;
   s.list_valid = false;
   const bool hits = (p->d.flags & SCN_OUT_HITS) != 0;
@@ -719,7 +781,9 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   // on that stream against 73 us of FFT; records read in place, three in flight: 373 .. 403 -> 429 Gsamples/s).  So the kernel
   // stores the counts itself when the launch has few buffers or the list follows eagerly, and a DMA carries them otherwise.
   const bool eager = hits && nb && (p->records_wanted || p->device_list_wanted);
-  const bool fused = (p->path == Path::FusedPow2 || p->path == Path::FusedMixed) && p->avg == 1u;
+  // (floor plans take the route of the paths that are not fused: the detect kernel, not the transform, is the submit's last kernel,
+  //  and it stores the counts to device memory only -- counts by DMA or scn_hit_total_kernel, a marker event behind it)
+  const bool fused = (p->path == Path::FusedPow2 || p->path == Path::FusedMixed) && p->avg == 1u && !p->floor;
   const bool direct = fused && (p->direct_counts || nb <= 4096u || eager);
   // What follows the kernel: the counts (a DMA on the d2h stream: needs no CU -- or nothing, when the kernel stores them to
   // pinned memory itself) and, when the caller is known to want records, the ordered list (two small kernels + a DMA on
@@ -743,6 +807,7 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   const bool in_packet = after && fused && (uint64_t)nb * n >= (1u << 25);
   st = launch_transform(p, s, d_raw, n_raw, d_power, (hits && direct) ? s.h_buf_hits : nullptr, in_packet ? after : nullptr);
   if (st) return st;
+  if (p->floor && nb && (st = launch_floor(p, s, d_power, nb))) return st;
   if (hits && nb) {
     if (after && !in_packet) SCN_HIP(hipEventRecord(after, s.stream));
     if (cnt != s.stream) SCN_HIP(hipStreamWaitEvent(cnt, after, 0));
@@ -759,6 +824,7 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
     } else if (!direct) {
       SCN_HIP(hipMemcpyAsync(s.h_buf_hits, s.d_buf_hits[s.gen], sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, cnt));
     }
+    if (p->floor) SCN_HIP(hipMemcpyAsync(s.h_floor, s.d_floor, sizeof(float) * nb, hipMemcpyDeviceToHost, cnt));  // the way the counts go
     if (!(after_is_done && after)) SCN_HIP(hipEventRecord(s.done, cnt));
     if (eager) {
       int st2 = build_list(p, s, p->records_wanted);  // (the prefetch to pinned memory only for a caller that reads the records on the host)
@@ -778,6 +844,9 @@ void free_slot(Slot &s) {
   if (s.h_raw) (void)hipHostFree(s.h_raw);
   if (s.d_raw) (void)hipFree(s.d_raw);
   if (s.d_power) (void)hipFree(s.d_power);
+  if (s.d_floor_power) (void)hipFree(s.d_floor_power);
+  if (s.d_floor) (void)hipFree(s.d_floor);
+  if (s.h_floor) (void)hipHostFree(s.h_floor);
   if (s.h_buf_hits) (void)hipHostFree(s.h_buf_hits);
   if (s.d_total_acc) (void)hipFree(s.d_total_acc);
   for (int g = 0; g < 2; g++) {
@@ -884,6 +953,16 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
     if (d.average_layout != SCN_AVG_DWELL && d.average_layout != SCN_AVG_SWEEPS)
       return fail(SCN_E_INVALID, "unknown average_layout %u", d.average_layout);
   }
+  uint32_t i_lo = 0, i_hi = 0, floor_permille = 0;
+  const uint32_t kept = evaluated_bins(d.n, d.dc_ignore_bins, d.use_bandwidth, &i_lo, &i_hi);
+  if (d.detect != SCN_DETECT_FIXED && d.detect != SCN_DETECT_FLOOR) return fail(SCN_E_INVALID, "unknown detect %u", d.detect);
+  if (d.detect == SCN_DETECT_FLOOR) {  // (as the average's: properties of the descriptor alone)
+    if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR needs a frequency-domain plan");
+    if (!(d.flags & SCN_OUT_HITS)) return fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR needs SCN_OUT_HITS");
+    if (!floor_permille_of(d.floor_permille, &floor_permille))
+      return fail(SCN_E_INVALID, "floor_permille %u: 0 (the median), 1 ... 1000 or SCN_FLOOR_MIN", d.floor_permille);
+    if (!kept) return fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR: the mask (dc_ignore_bins, use_bandwidth) lets no bin through");
+  }
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SCN_E_NO_DEVICE, "no HIP device visible");
@@ -898,19 +977,11 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   p->avg_layout = avg > 1u ? d.average_layout : (uint32_t)SCN_AVG_DWELL;
   p->buf_bytes = bytes_per_sample(d.sample_kind) * d.n;
   p->scale = convert_scale(d.sample_kind, d.enob);
-  // process.cpp:85 m_useWindow = uint32_t(useBandWidth * numSamples / 2.0); :51 bounds in uint32
-  uint32_t use_window = (uint32_t)(d.use_bandwidth * d.n / 2.0);
-  p->i_lo = d.n / 2 - use_window;
-  p->i_hi = d.n / 2 + use_window;
-  {  // the mask exactly as the kernels apply it (process.cpp:46-52, uint32 arithmetic)
-    const struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {d.dc_ignore_bins, p->i_lo, p->i_hi};
-    uint32_t kept = 0;
-    for (uint32_t i = 0; i < d.n; i++) {
-      const uint32_t j = (i + d.n / 2) % d.n;
-      kept += scn_bin_evaluated(j, i, d.n, mask);
-    }
-    p->hit_region = std::max<uint32_t>(kept, 1u);
-  }
+  p->i_lo = i_lo;
+  p->i_hi = i_hi;
+  p->hit_region = std::max<uint32_t>(kept, 1u);
+  p->floor = d.detect == SCN_DETECT_FLOOR;
+  if (p->floor) p->floor_rank = (uint32_t)((uint64_t)floor_permille * (kept - 1u) / 1000u);
   build_window(d.window_type, d.n, p->h_window);
 
   hipDeviceProp_t prop;
@@ -1361,6 +1432,46 @@ int scn_signals_from_hits(const scn_hit *hits, uint64_t n_hits, uint32_t n, uint
   if (total && total <= cap) signals[total - 1] = cur;
   *n_signals = total;
   if (total > cap) return fail(SCN_E_TRUNCATED, "%llu signals, the first %llu returned", (unsigned long long)total, (unsigned long long)cap);
+  return SCN_OK;
+}
+
+int scn_collect_floor(scn_plan *p, int slot, float *floor_db) {
+  int st = check_slot(p, slot);
+  if (st) return st;
+  if (!floor_db) return fail(SCN_E_INVALID, "null argument");
+  if (!p->floor) return fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_FLOOR");
+  Slot &s = p->slot[slot];
+  if (s.pending || !s.list_valid) return fail(SCN_E_STATE, "slot %d: no collected submit whose floor is still available", slot);
+  if (s.n_buffers) memcpy(floor_db, s.h_floor, sizeof(float) * s.n_buffers);  // (in pinned memory since `done`: scn_collect waited for it)
+  return SCN_OK;
+}
+
+int scn_floor_from_spectrum(const float *power_db, uint32_t n, uint32_t dc_ignore_bins, double use_bandwidth, uint32_t floor_permille,
+                            float *floor_db) {
+  if (!power_db || !floor_db) return fail(SCN_E_INVALID, "null argument");
+  if (n == 0 || n > (1u << 24)) return fail(SCN_E_INVALID, "bad bin count %u", n);
+  uint32_t permille = 0;
+  if (!floor_permille_of(floor_permille, &permille))
+    return fail(SCN_E_INVALID, "floor_permille %u: 0 (the median), 1 ... 1000 or SCN_FLOOR_MIN", floor_permille);
+  if (!dc_ignore_bins) dc_ignore_bins = 4;  // the descriptor's defaults (scn_plan_create)
+  if (dc_ignore_bins == SCN_DC_IGNORE_NONE) dc_ignore_bins = 0;
+  if (use_bandwidth == 0.0) use_bandwidth = 0.75;
+  struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {dc_ignore_bins, 0, 0};
+  evaluated_bins(n, dc_ignore_bins, use_bandwidth, &mask.i_lo, &mask.i_hi);
+  std::vector<uint32_t> keys;
+  keys.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t j = (i + n / 2) % n;
+    if (!scn_bin_evaluated(j, i, n, mask)) continue;
+    uint32_t bits;
+    memcpy(&bits, power_db + j, sizeof(bits));
+    keys.push_back((bits & 0x80000000u) ? ~bits : (bits | 0x80000000u));
+  }
+  if (keys.empty()) return fail(SCN_E_INVALID, "the mask (dc_ignore_bins, use_bandwidth) lets no bin through");
+  const size_t r = (size_t)((uint64_t)permille * (keys.size() - 1u) / 1000u);
+  std::nth_element(keys.begin(), keys.begin() + (ptrdiff_t)r, keys.end());
+  const uint32_t key = keys[r], bits = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;
+  memcpy(floor_db, &bits, sizeof(bits));
   return SCN_OK;
 }
 

@@ -141,6 +141,23 @@ hipError_t scn_launch_signal_build(const ScnSignalArgs &args, hipStream_t stream
 hipError_t scn_launch_hit_total(const uint32_t *counts, uint32_t n_buffers, uint32_t trigger_count, unsigned long long *acc, unsigned long long *host_total,
                                 uint32_t *trigger_bits, hipStream_t stream);
 
+// The floor detector (scn_floor.hip, scn_plan_desc.detect = SCN_DETECT_FLOOR): behind the transform, on the dB spectrum it stored.
+// Per unit: the value of rank `rank` among the evaluated bins (floor_db[u]), the cut floor_db[u] + threshold in one float
+// addition, and every evaluated bin strictly above the cut as a record of the unit's region, with the unit's count -- regions and
+// counts as the FFT kernels' hit paths leave them.  Every unit's count and floor are written (nothing to zero beforehand).
+struct ScnFloorArgs {
+  const float *power_db;      // [n_units][n], natural bin order
+  uint32_t n, n_units;
+  uint32_t rank;              // floor_permille * (hit_region - 1) / 1000, < hit_region
+  float threshold;            // the offset above the floor, in the plan's dB scale
+  uint32_t dc_ignore, i_lo, i_hi;
+  ScnDevHit *hits;            // [n_units][hit_region]
+  uint32_t hit_region;        // = the number of evaluated bins M
+  uint32_t *counts;           // [n_units]
+  float *floor_db;            // [n_units] (device memory)
+};
+hipError_t scn_launch_floor(const ScnFloorArgs &args, int num_cus, hipStream_t stream);
+
 // The same path for the sizes without a fused or four-step kernel (scn_generic.hip): Bluestein, through HBM, stage by stage
 struct ScnGenericArgs {
   const void *raw;            // n_buffers raw buffers back to back

@@ -16,8 +16,11 @@ class Plan:
                  correct_dc=False, max_batch=1, use_bandwidth=0.75, dc_ignore_bins=4, trigger_count=1047,
                  max_hits=0, flags=capi.OUT_SPECTRUM | capi.OUT_HITS, device_id=0,
                  window_type=capi.WIN_BLACKMAN_HARRIS, mode=capi.MODE_FREQUENCY_DOMAIN, average=1,
-                 average_layout=capi.AVG_DWELL):
-        """average = K > 1: every K buffers of a submit form a group (average_layout: capi.AVG_DWELL, buffers gK ... gK+K-1,
+                 average_layout=capi.AVG_DWELL, detect=capi.DETECT_FIXED, floor_permille=0):
+        """detect = capi.DETECT_FLOOR: a bin is a hit when it exceeds its own unit's floor -- the value of rank floor_permille
+        (0: the median, capi.FLOOR_MIN: the minimum, 1000: the maximum) among the unit's evaluated bins -- by more than
+        `threshold`, then an offset in the plan's dB scale; collect_floor returns the floors (scanner_hip.h, "Floor detector").
+        average = K > 1: every K buffers of a submit form a group (average_layout: capi.AVG_DWELL, buffers gK ... gK+K-1,
         or capi.AVG_SWEEPS, buffers g, g+G, ...) whose mean power spectrum is what the plan reports and detects on; the
         outputs of collect are then per group (scanner_hip.h)."""
         self._L = capi.lib()
@@ -40,6 +43,8 @@ class Plan:
         d.device_id = device_id
         d.average = average
         d.average_layout = average_layout
+        d.detect = detect
+        d.floor_permille = floor_permille
         self.average, self.average_layout = max(1, int(average)), average_layout
         self.n, self.kind, self.max_batch, self.flags, self.device_id = n, kind, max_batch, flags, device_id
         self.sample_rate = int(sample_rate)
@@ -250,6 +255,13 @@ class Plan:
                                                    C.byref(total)), "scn_collect_signals")
         self.last_n_signals = total.value
         return out[: max(0, min(cap, total.value - int(first)))]
+
+    def collect_floor(self, slot):
+        """scn_collect_floor: floor_db float32[B] of the slot's last collected submit, one per buffer (per group on an averaged
+        plan).  Floor-detector plans only (detect=capi.DETECT_FLOOR)."""
+        out = np.empty(self._nb[slot] // self.average, np.float32)
+        capi.check(self._L.scn_collect_floor(self._h, slot, out.ctypes.data_as(C.c_void_p)), "scn_collect_floor")
+        return out
 
     def hits_view(self, slot):
         """Zero-copy numpy view of the plan's pinned ordered hit list (valid until the slot's next submit)."""
