@@ -22,12 +22,8 @@
 #include <new>
 #include <vector>
 
-#include "../../include/scanner_hip.h"
 #include "scn_gather_protocol.h"
-
-int scn_set_last_error(int status, const char *fmt, ...);  // scn_api.hip
-// scn_api.hip: the collected slot's ordered list in device memory (built if it was not yet), without a host copy
-int scn_plan_device_hits(scn_plan *p, int slot, const scn_hit **d_list, uint32_t *n, int *device_id, void **list_ready = nullptr);
+#include "scn_plan.h"  // scn_fail, SCN_HIP, the resource holders; scn_plan_device_hits: a collected slot's list where it lies
 
 namespace {
 
@@ -76,11 +72,11 @@ RcclApi &rccl() {
 // scn_gather_post / scn_gather_wait: a ring of posts in flight (scn_gather_protocol.h, the steady-state form)
 struct StreamGather {
   uint32_t cap = 0;                  // records per rank per message (the buffers below are sized for it)
-  scn_hit *d_msg = nullptr;          // [SCN_GATHER_TICKETS][cap + 1]: this rank's outgoing messages (header + records)
-  scn_hit *d_ring = nullptr;         // root: [SCN_GATHER_TICKETS][world][cap + 1]: the messages as they arrive
-  scn_hit *h_list = nullptr;         // root: pinned [SCN_GATHER_TICKETS][world * cap]: the compacted, rank-major lists
-  ScnStreamHeader *h_head = nullptr; // root: pinned [SCN_GATHER_TICKETS][world]: the headers, for scn_gather_wait
-  hipEvent_t done[SCN_GATHER_TICKETS] = {};
+  ScnDeviceMem<scn_hit> d_msg;       // [SCN_GATHER_TICKETS][cap + 1]: this rank's outgoing messages (header + records)
+  ScnDeviceMem<scn_hit> d_ring;      // root: [SCN_GATHER_TICKETS][world][cap + 1]: the messages as they arrive
+  ScnPinnedMem<scn_hit> h_list;      // root: pinned [SCN_GATHER_TICKETS][world * cap]: the compacted, rank-major lists
+  ScnPinnedMem<ScnStreamHeader> h_head;  // root: pinned [SCN_GATHER_TICKETS][world]: the headers, for scn_gather_wait
+  ScnEvent done[SCN_GATHER_TICKETS];
   bool posted[SCN_GATHER_TICKETS] = {};
   bool as_root[SCN_GATHER_TICKETS] = {};
   uint64_t seq_of[SCN_GATHER_TICKETS] = {};
@@ -88,44 +84,32 @@ struct StreamGather {
 };
 
 struct scn_comm {
+  ScnStream stream;  // (first: destroyed after the memory and the events used on it)
   StreamGather sg;
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1, device = 0;
-  hipStream_t stream = nullptr;
-  uint32_t *d_counts = nullptr;  // [2 * world + 2]: the gathered {count, status} pairs, then this rank's own pair
-  void *d_send = nullptr, *d_recv = nullptr;
-  size_t send_cap = 0, recv_cap = 0;
+  ScnDeviceMem<uint32_t> d_counts;  // [2 * world + 2]: the gathered {count, status} pairs, then this rank's own pair
+  ScnDeviceMem<scn_hit> d_send, d_recv;  // grown on demand
   uint64_t gathered = 0;     // records of the last successful gather held in d_recv (root only)
   bool gather_root = false;  // this rank was the root of the last successful gather
 };
 
-#define SCN_G_HIP(call)                                                                                       \
-  do {                                                                                                        \
-    hipError_t e_ = (call);                                                                                   \
-    if (e_ != hipSuccess)                                                                                     \
-      return scn_set_last_error(e_ == hipErrorOutOfMemory ? SCN_E_NOMEM : SCN_E_HIP, "%s failed: %s", #call, \
-                                hipGetErrorString(e_));                                                       \
-  } while (0)
 #define SCN_G_NCCL(call)                                                                                   \
   do {                                                                                                     \
     ncclResult_t r_ = (call);                                                                              \
-    if (r_ != ncclSuccess) return scn_set_last_error(SCN_E_COMM, "%s failed: %s", #call, api.GetErrorString(r_)); \
+    if (r_ != ncclSuccess) return scn_fail(SCN_E_COMM, "%s failed: %s", #call, api.GetErrorString(r_)); \
   } while (0)
 
-static int grow(void **buf, size_t *cap, size_t bytes) {
-  if (*cap >= bytes) return SCN_OK;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *cap = 0;
-  SCN_G_HIP(hipMalloc(buf, bytes));
-  *cap = bytes;
+// a buffer of records grown on demand
+static int room_for(ScnDeviceMem<scn_hit> &buf, size_t records) {
+  if (buf.capacity() < records) SCN_HIP(buf.grow(records));
   return SCN_OK;
 }
 
 extern "C" {
 
 int scn_gather_layout(const uint32_t *per_rank, uint32_t world_size, uint64_t *offsets) {
-  if (!per_rank || !offsets || world_size == 0) return scn_set_last_error(SCN_E_INVALID, "bad arguments");
+  if (!per_rank || !offsets || world_size == 0) return scn_fail(SCN_E_INVALID, "bad arguments");
   uint64_t run = 0;
   for (uint32_t r = 0; r < world_size; r++) {
     offsets[r] = run;
@@ -136,9 +120,9 @@ int scn_gather_layout(const uint32_t *per_rank, uint32_t world_size, uint64_t *o
 }
 
 int scn_comm_unique_id(void *id) {
-  if (!id) return scn_set_last_error(SCN_E_INVALID, "null argument");
+  if (!id) return scn_fail(SCN_E_INVALID, "null argument");
   RcclApi &api = rccl();
-  if (!api.ok) return scn_set_last_error(SCN_E_COMM, "RCCL (librccl.so.1) could not be loaded: %s", dlerror());
+  if (!api.ok) return scn_fail(SCN_E_COMM, "RCCL (librccl.so.1) could not be loaded: %s", dlerror());
   static_assert(SCN_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "id size");
   ncclUniqueId uid;
   SCN_G_NCCL(api.GetUniqueId(&uid));
@@ -147,13 +131,13 @@ int scn_comm_unique_id(void *id) {
 }
 
 int scn_comm_create(const void *id, int rank, int world_size, int device_id, scn_comm **out) {
-  if (!id || !out || world_size < 1 || rank < 0 || rank >= world_size) return scn_set_last_error(SCN_E_INVALID, "bad arguments");
+  if (!id || !out || world_size < 1 || rank < 0 || rank >= world_size) return scn_fail(SCN_E_INVALID, "bad arguments");
   *out = nullptr;
   RcclApi &api = rccl();
-  if (!api.ok) return scn_set_last_error(SCN_E_COMM, "RCCL (librccl.so.1) could not be loaded: %s", dlerror());
-  SCN_G_HIP(hipSetDevice(device_id));
+  if (!api.ok) return scn_fail(SCN_E_COMM, "RCCL (librccl.so.1) could not be loaded: %s", dlerror());
+  SCN_HIP(hipSetDevice(device_id));
   scn_comm *c = new (std::nothrow) scn_comm();
-  if (!c) return scn_set_last_error(SCN_E_NOMEM, "out of host memory");
+  if (!c) return scn_fail(SCN_E_NOMEM, "out of host memory");
   c->rank = rank;
   c->world = world_size;
   c->device = device_id;
@@ -161,17 +145,17 @@ int scn_comm_create(const void *id, int rank, int world_size, int device_id, scn
   memcpy(uid.internal, id, SCN_COMM_ID_BYTES);
   int st = SCN_OK;
   do {
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&c->d_counts, sizeof(uint32_t) * (2u * (size_t)world_size + 2u));
-    if (e == hipSuccess) e = hipMemset(c->d_counts, 0xff, sizeof(uint32_t) * (2u * (size_t)world_size + 2u));  // the announce slot's poison (SCN_GATHER_POISON)
+    hipError_t e = c->stream.create();
+    if (e == hipSuccess) e = c->d_counts.alloc(2u * (size_t)world_size + 2u);
+    if (e == hipSuccess) e = hipMemset(c->d_counts.get(), 0xff, sizeof(uint32_t) * (2u * (size_t)world_size + 2u));  // the announce slot's poison (SCN_GATHER_POISON)
     if (e != hipSuccess) {
-      st = scn_set_last_error(SCN_E_HIP, "scn_comm_create: %s", hipGetErrorString(e));
+      st = scn_fail(SCN_E_HIP, "scn_comm_create: %s", hipGetErrorString(e));
       break;
     }
     ncclResult_t r = api.CommInitRank(&c->comm, world_size, uid, rank);
     if (r != ncclSuccess) {
       c->comm = nullptr;
-      st = scn_set_last_error(SCN_E_COMM, "ncclCommInitRank failed: %s", api.GetErrorString(r));
+      st = scn_fail(SCN_E_COMM, "ncclCommInitRank failed: %s", api.GetErrorString(r));
     }
   } while (0);
   if (st != SCN_OK) {
@@ -184,19 +168,9 @@ int scn_comm_create(const void *id, int rank, int world_size, int device_id, scn
 
 int scn_comm_destroy(scn_comm *c) {
   if (!c) return SCN_OK;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  (void)hipSetDevice(c->device);  // the members are released with the communicator's device current, nothing still running
+  c->stream.sync();
   if (c->comm) (void)rccl().CommDestroy(c->comm);
-  if (c->d_counts) (void)hipFree(c->d_counts);
-  if (c->d_send) (void)hipFree(c->d_send);
-  if (c->d_recv) (void)hipFree(c->d_recv);
-  if (c->sg.d_msg) (void)hipFree(c->sg.d_msg);
-  if (c->sg.d_ring) (void)hipFree(c->sg.d_ring);
-  if (c->sg.h_list) (void)hipHostFree(c->sg.h_list);
-  if (c->sg.h_head) (void)hipHostFree(c->sg.h_head);
-  for (int k = 0; k < SCN_GATHER_TICKETS; k++)
-    if (c->sg.done[k]) (void)hipEventDestroy(c->sg.done[k]);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return SCN_OK;
 }
@@ -219,17 +193,17 @@ struct RcclTransport {
   uint32_t world() const { return (uint32_t)c->world; }
 
   ScnAnnounce announce(const uint32_t *words, uint32_t n_words, uint32_t *all) {
-    uint32_t *slot = c->d_counts + 2u * world();
-    hipError_t e = hipMemcpyAsync(slot, words, sizeof(uint32_t) * n_words, hipMemcpyHostToDevice, c->stream);
+    uint32_t *slot = c->d_counts.get() + 2u * world();
+    hipError_t e = hipMemcpyAsync(slot, words, sizeof(uint32_t) * n_words, hipMemcpyHostToDevice, c->stream.get());
     if (e != hipSuccess && hip_err == hipSuccess) hip_err = e;  // (the slot keeps its poison: the peers read "not OK")
-    const ncclResult_t r = api.AllGather(slot, c->d_counts, n_words, ncclUint32, c->comm, c->stream);
+    const ncclResult_t r = api.AllGather(slot, c->d_counts.get(), n_words, ncclUint32, c->comm, c->stream.get());
     if (r != ncclSuccess) {
       nccl_err = r;
       return SCN_ANNOUNCE_BROKEN;
     }
-    e = hipMemcpyAsync(all, c->d_counts, sizeof(uint32_t) * n_words * world(), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipMemsetAsync(slot, 0xff, sizeof(uint32_t) * 2u, c->stream);  // poison again for the next announce
+    e = hipMemcpyAsync(all, c->d_counts.get(), sizeof(uint32_t) * n_words * world(), hipMemcpyDeviceToHost, c->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
+    (void)hipMemsetAsync(slot, 0xff, sizeof(uint32_t) * 2u, c->stream.get());  // poison again for the next announce
     if (e != hipSuccess) {
       if (hip_err == hipSuccess) hip_err = e;
       return SCN_ANNOUNCE_VIEW_LOST;
@@ -237,7 +211,7 @@ struct RcclTransport {
     return SCN_ANNOUNCE_OK;
   }
 
-  int make_room(uint64_t records) { return grow(&c->d_recv, &c->recv_cap, (size_t)(records ? records : 1) * sizeof(scn_hit)); }
+  int make_room(uint64_t records) { return room_for(c->d_recv, (size_t)(records ? records : 1)); }
 
   // ONE group: the root posts a receive per peer straight into its place of the rank-major list, peers send.  Every call
   // between ncclGroupStart and ncclGroupEnd is attempted-or-skipped, never returned out of: the group is always closed, the
@@ -248,24 +222,24 @@ struct RcclTransport {
     ncclResult_t first_err = ncclSuccess;
     hipError_t copy_err = hipSuccess;
     if (is_root && n_local)
-      copy_err = hipMemcpyAsync(static_cast<char *>(c->d_recv) + offsets[root] * rec, d_local, rec * n_local, hipMemcpyDeviceToDevice, c->stream);
+      copy_err = hipMemcpyAsync(c->d_recv.get() + offsets[root], d_local, rec * n_local, hipMemcpyDeviceToDevice, c->stream.get());
     const ncclResult_t r0 = api.GroupStart();
     if (r0 == ncclSuccess) {
       if (is_root) {
         for (uint32_t r = 0; r < world(); r++)
           if (r != root && counts[r]) {
-            const ncclResult_t e = api.Recv(static_cast<char *>(c->d_recv) + offsets[r] * rec, rec * counts[r], ncclUint8, (int)r, c->comm, c->stream);
+            const ncclResult_t e = api.Recv(c->d_recv.get() + offsets[r], rec * counts[r], ncclUint8, (int)r, c->comm, c->stream.get());
             if (e != ncclSuccess && first_err == ncclSuccess) first_err = e;  // keep posting: the peers' sends are coming
           }
       } else if (n_local) {
-        first_err = api.Send(d_local, rec * n_local, ncclUint8, (int)root, c->comm, c->stream);
+        first_err = api.Send(d_local, rec * n_local, ncclUint8, (int)root, c->comm, c->stream.get());
       }
       const ncclResult_t e = api.GroupEnd();  // always closed
       if (e != ncclSuccess && first_err == ncclSuccess) first_err = e;
     } else {
       first_err = r0;
     }
-    const hipError_t sync_err = hipStreamSynchronize(c->stream);
+    const hipError_t sync_err = hipStreamSynchronize(c->stream.get());
     if (first_err != ncclSuccess) {
       nccl_err = first_err;
       return SCN_E_COMM;
@@ -295,88 +269,79 @@ static int gather_core(scn_comm *c, const void *d_local, uint32_t n_local, int l
     return SCN_OK;
   }
   if (o.bad_rank == c->rank && local_status != SCN_OK) return local_status;  // (the caller has set the message)
-  if (t.nccl_err != ncclSuccess) return scn_set_last_error(SCN_E_COMM, "gather step %d failed: %s", o.step, api.GetErrorString(t.nccl_err));
+  if (t.nccl_err != ncclSuccess) return scn_fail(SCN_E_COMM, "gather step %d failed: %s", o.step, api.GetErrorString(t.nccl_err));
   if (o.bad_rank >= 0 && o.bad_rank != c->rank)
-    return scn_set_last_error(SCN_E_COMM, "rank %d %s (status %u): nothing was exchanged", o.bad_rank,
+    return scn_fail(SCN_E_COMM, "rank %d %s (status %u): nothing was exchanged", o.bad_rank,
                               o.step == 1 ? "could not prepare its part of the gather" : "was not ready for the transfers (the root: no room for the list)", o.bad_status);
   if (t.hip_err != hipSuccess)
-    return scn_set_last_error(o.status == SCN_E_NOMEM ? SCN_E_NOMEM : SCN_E_HIP, "gather step %d: %s", o.step, hipGetErrorString(t.hip_err));
-  return scn_set_last_error(o.status, "gather step %d failed on this rank (status %d)", o.step, o.status);
+    return scn_fail(o.status == SCN_E_NOMEM ? SCN_E_NOMEM : SCN_E_HIP, "gather step %d: %s", o.step, hipGetErrorString(t.hip_err));
+  return scn_fail(o.status, "gather step %d failed on this rank (status %d)", o.step, o.status);
 }
 
 extern "C" {
 
 int scn_gather_fetch(scn_comm *c, uint64_t first, scn_hit *out, uint64_t cap, uint64_t *n_written) {
-  if (!c || !n_written || (cap && !out)) return scn_set_last_error(SCN_E_INVALID, "bad arguments");
+  if (!c || !n_written || (cap && !out)) return scn_fail(SCN_E_INVALID, "bad arguments");
   *n_written = 0;
-  if (!c->gather_root) return scn_set_last_error(SCN_E_STATE, "no gathered list on this rank (not the root of the last gather, or it failed)");
+  if (!c->gather_root) return scn_fail(SCN_E_STATE, "no gathered list on this rank (not the root of the last gather, or it failed)");
   if (first >= c->gathered || cap == 0) return SCN_OK;
-  SCN_G_HIP(hipSetDevice(c->device));
+  SCN_HIP(hipSetDevice(c->device));
   const uint64_t n = c->gathered - first < cap ? c->gathered - first : cap;
-  SCN_G_HIP(hipMemcpyAsync(out, static_cast<const scn_hit *>(c->d_recv) + first, sizeof(scn_hit) * n, hipMemcpyDeviceToHost, c->stream));
-  SCN_G_HIP(hipStreamSynchronize(c->stream));
+  SCN_HIP(hipMemcpyAsync(out, c->d_recv.get() + first, sizeof(scn_hit) * n, hipMemcpyDeviceToHost, c->stream.get()));
+  SCN_HIP(hipStreamSynchronize(c->stream.get()));
   *n_written = n;
   return SCN_OK;
 }
 
-// copy-out shared by the two collective forms: min(total, all_cap) records on the root, SCN_E_TRUNCATED if not all (the rest
-// stays fetchable: scn_gather_fetch)
-static int gather_copy_out(scn_comm *c, scn_hit *all, uint64_t all_cap, uint64_t total) {
-  if (!c->gather_root || !all) return SCN_OK;
-  uint64_t got = 0;
-  if (int st = scn_gather_fetch(c, 0, all, all_cap, &got)) return st;
+// shared by the two collective forms: the collective, then min(total, all_cap) records copied out on the root, SCN_E_TRUNCATED if
+// not all (the rest stays fetchable: scn_gather_fetch)
+static int gather_and_copy(scn_comm *c, const void *d_local, uint32_t n_local, int status, uint32_t root, scn_hit *all, uint64_t all_cap,
+                           uint64_t *n_total, uint32_t *per_rank) {
+  uint64_t total = 0, got = 0;
+  const int st = gather_core(c, d_local, status == SCN_OK ? n_local : 0u, status, root, &total, per_rank);
+  if (n_total) *n_total = total;
+  if (st || !c->gather_root || !all) return st;
+  if (int st2 = scn_gather_fetch(c, 0, all, all_cap, &got)) return st2;
   if (got < total)
-    return scn_set_last_error(SCN_E_TRUNCATED, "%llu hits gathered, room for %llu: scn_gather_fetch reads the rest from the root's device copy",
-                              (unsigned long long)total, (unsigned long long)all_cap);
+    return scn_fail(SCN_E_TRUNCATED, "%llu hits gathered, room for %llu: scn_gather_fetch reads the rest from the root's device copy",
+                    (unsigned long long)total, (unsigned long long)all_cap);
   return SCN_OK;
 }
 
 int scn_gather_hits(scn_comm *c, const scn_hit *local, uint32_t n_local, uint32_t root, scn_hit *all, uint64_t all_cap,
                     uint64_t *n_total, uint32_t *per_rank) {
-  if (!c) return scn_set_last_error(SCN_E_INVALID, "null communicator");  // (nothing to take part with)
+  if (!c) return scn_fail(SCN_E_INVALID, "null communicator");  // (nothing to take part with)
   // whatever goes wrong on this rank from here on is ANNOUNCED in the exchange, not returned before it
   int status = SCN_OK;
   if (root >= (uint32_t)c->world) {
-    status = scn_set_last_error(SCN_E_INVALID, "root %u out of range (world size %d)", root, c->world);
+    status = scn_fail(SCN_E_INVALID, "root %u out of range (world size %d)", root, c->world);
     root = 0;
   }
-  if (status == SCN_OK && hipSetDevice(c->device) != hipSuccess) status = scn_set_last_error(SCN_E_HIP, "hipSetDevice(%d) failed", c->device);
-  if (status == SCN_OK && n_local && !local) status = scn_set_last_error(SCN_E_INVALID, "n_local > 0 with a null list");
+  if (status == SCN_OK && hipSetDevice(c->device) != hipSuccess) status = scn_fail(SCN_E_HIP, "hipSetDevice(%d) failed", c->device);
+  if (status == SCN_OK && n_local && !local) status = scn_fail(SCN_E_INVALID, "n_local > 0 with a null list");
   if (status == SCN_OK && n_local) {
-    status = grow(&c->d_send, &c->send_cap, sizeof(scn_hit) * (size_t)n_local);
-    if (status == SCN_OK && hipMemcpyAsync(c->d_send, local, sizeof(scn_hit) * (size_t)n_local, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-      status = scn_set_last_error(SCN_E_HIP, "staging the local hit list failed: %s", hipGetErrorString(hipGetLastError()));
+    status = room_for(c->d_send, n_local);
+    if (status == SCN_OK && hipMemcpyAsync(c->d_send.get(), local, sizeof(scn_hit) * (size_t)n_local, hipMemcpyHostToDevice, c->stream.get()) != hipSuccess)
+      status = scn_fail(SCN_E_HIP, "staging the local hit list failed: %s", hipGetErrorString(hipGetLastError()));
   }
-  uint64_t total = 0;
-  if (int st = gather_core(c, c->d_send, status == SCN_OK ? n_local : 0u, status, root, &total, per_rank)) {
-    if (n_total) *n_total = total;
-    return st;
-  }
-  if (n_total) *n_total = total;
-  return gather_copy_out(c, all, all_cap, total);
+  return gather_and_copy(c, c->d_send.get(), n_local, status, root, all, all_cap, n_total, per_rank);
 }
 
 int scn_gather_hits_device(scn_comm *c, scn_plan *plan, int slot, uint32_t root, scn_hit *all, uint64_t all_cap, uint64_t *n_total,
                            uint32_t *per_rank) {
-  if (!c) return scn_set_last_error(SCN_E_INVALID, "null communicator");
+  if (!c) return scn_fail(SCN_E_INVALID, "null communicator");
   const scn_hit *d_list = nullptr;
   uint32_t n_local = 0;
   int dev = c->device;
-  int status = plan ? scn_plan_device_hits(plan, slot, &d_list, &n_local, &dev) : scn_set_last_error(SCN_E_INVALID, "null plan");
+  int status = plan ? scn_plan_device_hits(plan, slot, &d_list, &n_local, &dev) : scn_fail(SCN_E_INVALID, "null plan");
   if (status == SCN_OK && dev != c->device)
-    status = scn_set_last_error(SCN_E_INVALID, "the plan lives on device %d, the communicator on device %d", dev, c->device);
+    status = scn_fail(SCN_E_INVALID, "the plan lives on device %d, the communicator on device %d", dev, c->device);
   if (root >= (uint32_t)c->world) {
-    status = scn_set_last_error(SCN_E_INVALID, "root %u out of range (world size %d)", root, c->world);
+    status = scn_fail(SCN_E_INVALID, "root %u out of range (world size %d)", root, c->world);
     root = 0;
   }
-  if (hipSetDevice(c->device) != hipSuccess && status == SCN_OK) status = scn_set_last_error(SCN_E_HIP, "hipSetDevice(%d) failed", c->device);
-  uint64_t total = 0;
-  if (int st = gather_core(c, d_list, status == SCN_OK ? n_local : 0u, status, root, &total, per_rank)) {
-    if (n_total) *n_total = total;
-    return st;
-  }
-  if (n_total) *n_total = total;
-  return gather_copy_out(c, all, all_cap, total);
+  if (hipSetDevice(c->device) != hipSuccess && status == SCN_OK) status = scn_fail(SCN_E_HIP, "hipSetDevice(%d) failed", c->device);
+  return gather_and_copy(c, d_list, n_local, status, root, all, all_cap, n_total, per_rank);
 }
 
 }  // extern "C"
@@ -419,23 +384,20 @@ int stream_buffers(scn_comm *c, uint32_t cap, bool root) {
   StreamGather &g = c->sg;
   if (g.cap != cap) {
     for (int k = 0; k < SCN_GATHER_TICKETS; k++)
-      if (g.posted[k]) return scn_set_last_error(SCN_E_STATE, "cap_per_rank changed (%u -> %u) while a post is in flight", g.cap, cap);
-    if (g.d_msg) (void)hipFree(g.d_msg);
-    if (g.d_ring) (void)hipFree(g.d_ring);
-    if (g.h_list) (void)hipHostFree(g.h_list);
-    if (g.h_head) (void)hipHostFree(g.h_head);
-    g.d_msg = g.d_ring = g.h_list = nullptr;
-    g.h_head = nullptr;
+      if (g.posted[k]) return scn_fail(SCN_E_STATE, "cap_per_rank changed (%u -> %u) while a post is in flight", g.cap, cap);
+    g.d_msg.reset();
+    g.d_ring.reset();
+    g.h_list.reset();
+    g.h_head.reset();
     g.cap = cap;
   }
   const size_t msg = (size_t)cap + 1u;
-  if (!g.d_msg) SCN_G_HIP(hipMalloc(&g.d_msg, sizeof(scn_hit) * msg * SCN_GATHER_TICKETS));
-  for (int k = 0; k < SCN_GATHER_TICKETS; k++)
-    if (!g.done[k]) SCN_G_HIP(hipEventCreateWithFlags(&g.done[k], hipEventDisableTiming));
+  SCN_HIP(g.d_msg.alloc(msg * SCN_GATHER_TICKETS));
+  for (int k = 0; k < SCN_GATHER_TICKETS; k++) SCN_HIP(g.done[k].create());
   if (root) {
-    if (!g.d_ring) SCN_G_HIP(hipMalloc(&g.d_ring, sizeof(scn_hit) * msg * (size_t)c->world * SCN_GATHER_TICKETS));
-    if (!g.h_list) SCN_G_HIP(hipHostMalloc(&g.h_list, sizeof(scn_hit) * std::max<size_t>((size_t)cap * c->world, 1u) * SCN_GATHER_TICKETS, hipHostMallocDefault));
-    if (!g.h_head) SCN_G_HIP(hipHostMalloc(&g.h_head, sizeof(ScnStreamHeader) * (size_t)c->world * SCN_GATHER_TICKETS, hipHostMallocDefault));
+    SCN_HIP(g.d_ring.alloc(msg * (size_t)c->world * SCN_GATHER_TICKETS));
+    SCN_HIP(g.h_list.alloc(std::max<size_t>((size_t)cap * c->world, 1u) * SCN_GATHER_TICKETS));
+    SCN_HIP(g.h_head.alloc((size_t)c->world * SCN_GATHER_TICKETS));
   }
   return SCN_OK;
 }
@@ -444,13 +406,13 @@ int stream_buffers(scn_comm *c, uint32_t cap, bool root) {
 extern "C" {
 
 int scn_gather_post(scn_comm *c, scn_plan *plan, int slot, uint32_t root, uint32_t cap_per_rank, uint32_t *ticket) {
-  if (!c || !ticket) return scn_set_last_error(SCN_E_INVALID, "null argument");
-  if (root >= (uint32_t)c->world || cap_per_rank == 0) return scn_set_last_error(SCN_E_INVALID, "root %u / cap_per_rank %u out of range", root, cap_per_rank);
+  if (!c || !ticket) return scn_fail(SCN_E_INVALID, "null argument");
+  if (root >= (uint32_t)c->world || cap_per_rank == 0) return scn_fail(SCN_E_INVALID, "root %u / cap_per_rank %u out of range", root, cap_per_rank);
   RcclApi &api = rccl();
   StreamGather &g = c->sg;
   const uint32_t tk = (uint32_t)(g.next_seq % SCN_GATHER_TICKETS);
-  if (g.posted[tk]) return scn_set_last_error(SCN_E_STATE, "%d posts in flight: scn_gather_wait the oldest (ticket %u) first", SCN_GATHER_TICKETS, tk);
-  SCN_G_HIP(hipSetDevice(c->device));
+  if (g.posted[tk]) return scn_fail(SCN_E_STATE, "%d posts in flight: scn_gather_wait the oldest (ticket %u) first", SCN_GATHER_TICKETS, tk);
+  SCN_HIP(hipSetDevice(c->device));
   const bool is_root = (uint32_t)c->rank == root;
   if (int st = stream_buffers(c, cap_per_rank, is_root)) return st;  // (nothing has been enqueued: the peers see a post that never came, like any rank that never calls)
   // this rank's part: whatever goes wrong from here on travels in the header, the message still goes out
@@ -458,10 +420,10 @@ int scn_gather_post(scn_comm *c, scn_plan *plan, int slot, uint32_t root, uint32
   uint32_t n_local = 0;
   int dev = c->device;
   void *list_ready = nullptr;  // the list kernels' event: the communicator's stream waits for it, the host does not
-  int status = plan ? scn_plan_device_hits(plan, slot, &d_list, &n_local, &dev, &list_ready) : scn_set_last_error(SCN_E_INVALID, "null plan");
-  if (status == SCN_OK && dev != c->device) status = scn_set_last_error(SCN_E_INVALID, "the plan lives on device %d, the communicator on device %d", dev, c->device);
-  if (status == SCN_OK && list_ready && hipStreamWaitEvent(c->stream, (hipEvent_t)list_ready, 0) != hipSuccess)
-    status = scn_set_last_error(SCN_E_HIP, "hipStreamWaitEvent failed: %s", hipGetErrorString(hipGetLastError()));
+  int status = plan ? scn_plan_device_hits(plan, slot, &d_list, &n_local, &dev, &list_ready) : scn_fail(SCN_E_INVALID, "null plan");
+  if (status == SCN_OK && dev != c->device) status = scn_fail(SCN_E_INVALID, "the plan lives on device %d, the communicator on device %d", dev, c->device);
+  if (status == SCN_OK && list_ready && hipStreamWaitEvent(c->stream.get(), (hipEvent_t)list_ready, 0) != hipSuccess)
+    status = scn_fail(SCN_E_HIP, "hipStreamWaitEvent failed: %s", hipGetErrorString(hipGetLastError()));
   if (status != SCN_OK) n_local = 0;
   ScnStreamHeader h;
   h.count = n_local;
@@ -470,64 +432,64 @@ int scn_gather_post(scn_comm *c, scn_plan *plan, int slot, uint32_t root, uint32
   h.magic = SCN_STREAM_MAGIC;
   h.seq = g.next_seq;
   const size_t msg = (size_t)cap_per_rank + 1u;
-  scn_hit *out = is_root ? g.d_ring + ((size_t)tk * c->world + c->rank) * msg : g.d_msg + (size_t)tk * msg;
+  scn_hit *out = is_root ? g.d_ring.get() + ((size_t)tk * c->world + c->rank) * msg : g.d_msg.get() + (size_t)tk * msg;
   const uint32_t blocks = h.sent ? std::min<uint32_t>((h.sent * 3u + 255u) / 256u, 64u) : 1u;
-  hipLaunchKernelGGL(scn_gather_pack_kernel, dim3(blocks), dim3(256), 0, c->stream, d_list, h, out);
-  SCN_G_HIP(hipGetLastError());
+  hipLaunchKernelGGL(scn_gather_pack_kernel, dim3(blocks), dim3(256), 0, c->stream.get(), d_list, h, out);
+  SCN_HIP(hipGetLastError());
   if (c->world > 1) {
     ncclResult_t first_err = api.GroupStart();
     if (first_err == ncclSuccess) {
       if (is_root) {
         for (int r = 0; r < c->world; r++)
           if (r != c->rank) {
-            const ncclResult_t e = api.Recv(g.d_ring + ((size_t)tk * c->world + r) * msg, sizeof(scn_hit) * msg, ncclUint8, r, c->comm, c->stream);
+            const ncclResult_t e = api.Recv(g.d_ring.get() + ((size_t)tk * c->world + r) * msg, sizeof(scn_hit) * msg, ncclUint8, r, c->comm, c->stream.get());
             if (e != ncclSuccess && first_err == ncclSuccess) first_err = e;  // keep posting: the peers' sends are coming
           }
       } else {
-        first_err = api.Send(out, sizeof(scn_hit) * msg, ncclUint8, (int)root, c->comm, c->stream);
+        first_err = api.Send(out, sizeof(scn_hit) * msg, ncclUint8, (int)root, c->comm, c->stream.get());
       }
       const ncclResult_t e = api.GroupEnd();  // always closed
       if (e != ncclSuccess && first_err == ncclSuccess) first_err = e;
     }
-    if (first_err != ncclSuccess) return scn_set_last_error(SCN_E_COMM, "scn_gather_post: %s", api.GetErrorString(first_err));
+    if (first_err != ncclSuccess) return scn_fail(SCN_E_COMM, "scn_gather_post: %s", api.GetErrorString(first_err));
   }
   if (is_root) {
     const uint32_t chunks = std::max<uint32_t>(1u, std::min<uint32_t>((cap_per_rank * 3u + 2047u) / 2048u, 16u));
-    hipLaunchKernelGGL(scn_gather_compact_kernel, dim3((uint32_t)c->world * chunks), dim3(256), 0, c->stream, g.d_ring + (size_t)tk * c->world * msg,
-                       (uint32_t)c->world, cap_per_rank, h.seq, g.h_list + (size_t)tk * cap_per_rank * c->world, g.h_head + (size_t)tk * c->world);
-    SCN_G_HIP(hipGetLastError());
+    hipLaunchKernelGGL(scn_gather_compact_kernel, dim3((uint32_t)c->world * chunks), dim3(256), 0, c->stream.get(), g.d_ring.get() + (size_t)tk * c->world * msg,
+                       (uint32_t)c->world, cap_per_rank, h.seq, g.h_list.get() + (size_t)tk * cap_per_rank * c->world, g.h_head.get() + (size_t)tk * c->world);
+    SCN_HIP(hipGetLastError());
   }
-  SCN_G_HIP(hipEventRecord(g.done[tk], c->stream));
+  SCN_HIP(hipEventRecord(g.done[tk].get(), c->stream.get()));
   g.posted[tk] = true;
   g.as_root[tk] = is_root;
   g.seq_of[tk] = h.seq;
   g.next_seq++;
   *ticket = tk;
   return status == SCN_OK && h.sent < n_local
-             ? scn_set_last_error(SCN_E_TRUNCATED, "slot %d holds %u hits, a message %u (cap_per_rank): the first %u went out", slot, n_local, cap_per_rank, h.sent)
+             ? scn_fail(SCN_E_TRUNCATED, "slot %d holds %u hits, a message %u (cap_per_rank): the first %u went out", slot, n_local, cap_per_rank, h.sent)
              : status;
 }
 
 int scn_gather_wait(scn_comm *c, uint32_t ticket, const scn_hit **list, uint64_t *n_total, uint32_t *per_rank) {
-  if (!c) return scn_set_last_error(SCN_E_INVALID, "null communicator");
+  if (!c) return scn_fail(SCN_E_INVALID, "null communicator");
   if (list) *list = nullptr;
   if (n_total) *n_total = 0;
   StreamGather &g = c->sg;
-  if (ticket >= SCN_GATHER_TICKETS || !g.posted[ticket]) return scn_set_last_error(SCN_E_STATE, "ticket %u is not in flight", ticket);
-  SCN_G_HIP(hipSetDevice(c->device));
-  const hipError_t e = hipEventSynchronize(g.done[ticket]);
+  if (ticket >= SCN_GATHER_TICKETS || !g.posted[ticket]) return scn_fail(SCN_E_STATE, "ticket %u is not in flight", ticket);
+  SCN_HIP(hipSetDevice(c->device));
+  const hipError_t e = hipEventSynchronize(g.done[ticket].get());
   g.posted[ticket] = false;
-  if (e != hipSuccess) return scn_set_last_error(SCN_E_HIP, "scn_gather_wait: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return scn_fail(SCN_E_HIP, "scn_gather_wait: %s", hipGetErrorString(e));
   if (!g.as_root[ticket]) return SCN_OK;
-  const ScnGatherOutcome o = scn_stream_outcome(g.h_head + (size_t)ticket * c->world, (uint32_t)c->world, g.cap, g.seq_of[ticket]);
+  const ScnGatherOutcome o = scn_stream_outcome(g.h_head.get() + (size_t)ticket * c->world, (uint32_t)c->world, g.cap, g.seq_of[ticket]);
   if (per_rank) memcpy(per_rank, o.counts.data(), sizeof(uint32_t) * (size_t)c->world);
   if (n_total) *n_total = o.total;
-  if (list) *list = g.h_list + (size_t)ticket * g.cap * c->world;
+  if (list) *list = g.h_list.get() + (size_t)ticket * g.cap * c->world;
   if (o.status == SCN_OK) return SCN_OK;
   if (o.status == SCN_E_TRUNCATED)
-    return scn_set_last_error(SCN_E_TRUNCATED, "rank %d holds %u hits, its message %u (cap_per_rank): the list has the first %u of them", o.bad_rank,
+    return scn_fail(SCN_E_TRUNCATED, "rank %d holds %u hits, its message %u (cap_per_rank): the list has the first %u of them", o.bad_rank,
                               o.counts[o.bad_rank], g.cap, g.cap);
-  return scn_set_last_error(SCN_E_COMM, o.step == 1 ? "rank %d could not prepare its part of the gather (status %u)"
+  return scn_fail(SCN_E_COMM, o.step == 1 ? "rank %d could not prepare its part of the gather (status %u)"
                                                     : "the message of rank %d does not belong to this post (status %u): the ranks' posts are out of step",
                             o.bad_rank, o.bad_status);
 }

@@ -16,7 +16,7 @@
 // Both are byte work on a few KB..MB (L2-latency bound, no roofline of their own): the C2 batch has ~69 k hits
 // = 0.5 MB of records in, 1.6 MB out.  The list is written to DEVICE memory (writing it straight into pinned host
 // memory stalled the FFT launch running beside it: 76 -> 100 us) and a DMA of the predicted size follows it on the same
-// stream (scn_api.hip, build_list / fetch_list); alone on the GPU the kernel takes ~4.5 us for a C2 batch, beside a
+// stream (scn_collect.hip, build_list / fetch_list); alone on the GPU the kernel takes ~4.5 us for a C2 batch, beside a
 // running FFT launch ~30 us, in its shadow either way, so a collect call is an event wait plus a copy out of pinned
 // memory.  The output window [first, first + out_cap) lets a caller with a small buffer walk an arbitrarily long list
 // (scn_collect_more) -- nothing is ever dropped on the device.
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void scn_hit_compact_kernel(ScnCompactArgs a) 
 // of nb / 8 bytes (64 KB) do.  Partial sums meet in a device word; the last workgroup to arrive stores the total for the host and
 // leaves both words zero for the next launch.  A lane handles four counts (one 16-byte load); the eight lanes of a bitmap word
 // meet in three cross-lane steps.
-// (scn_api.hip launches it from 2^18 buffers per launch, on the launch's own stream: below, the ~6 us it takes there cost more than the counts' DMA.)
+// (scn_submit.hip launches it from 2^18 buffers per launch, on the launch's own stream: below, the ~6 us it takes there cost more than the counts' DMA.)
 constexpr uint32_t kTotalThreads = 256, kTotalBlocks = 128;
 
 __global__ __launch_bounds__(kTotalThreads) void scn_hit_total_kernel(const uint32_t *counts, uint32_t nb, uint32_t trigger_count, unsigned long long *acc,

@@ -1,0 +1,37 @@
+// scn_host.h -- the C-ABI layer's arithmetic that never touches HIP (scn_host.hip).  Plain C++: tests/cpp/test_plan_math.cpp
+// compiles the unit with g++ and no HIP header on the include path.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/scanner_hip.h"
+#include "scn_mask.h"
+
+// The layer's one error setter: formats the text scn_last_error returns (one thread_local for the whole library), returns `status`
+int scn_fail(int status, const char *fmt, ...);
+
+size_t bytes_per_sample(uint32_t kind);  // 0: unknown kind
+float convert_scale(uint32_t kind, uint32_t enob);
+bool build_window(uint32_t type, uint32_t n, std::vector<float> &w);  // false: unknown type
+void host_fft(std::vector<double> &re, std::vector<double> &im);
+// W_m^k = exp(-2 pi i k / m), k < m, as (re, im) pairs, evaluated in double (T: float or double)
+template <class T>
+std::vector<T> twiddles(uint32_t m);
+
+// What a Bluestein plan of n points reads, in double: m = 2^log2m >= 2n - 1; twiddle [m][2], chirp [n][2], bfilter [m][2]
+struct ScnBluesteinTables {
+  uint32_t m = 0, log2m = 0;
+  std::vector<double> twiddle, chirp, bfilter;
+};
+ScnBluesteinTables bluestein_tables(uint32_t n);
+
+bool floor_permille_of(uint32_t given, uint32_t *permille);
+uint32_t evaluated_bins(uint32_t n, uint32_t dc_ignore, double use_bandwidth, uint32_t *i_lo, uint32_t *i_hi);
+
+// Averaged plans (k = average > 1; sweeps: SCN_AVG_SWEEPS, else SCN_AVG_DWELL).  group_headers redirects fc / seq to the groups'
+// (held in group_fc / group_seq) where the submit gave them or the compaction kernel's default would be wrong; returns the groups
+int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc);
+uint32_t group_headers(uint32_t k, bool sweeps, uint32_t nb, const double *&fc, const uint64_t *&seq, std::vector<double> &group_fc,
+                       std::vector<uint64_t> &group_seq);

@@ -1,0 +1,351 @@
+// scn_host.hip -- the part of the C-ABI layer that never touches HIP: the error text, the arithmetic behind a plan, the entry
+// points that are host arithmetic only.  Plain C++17: no HIP header here or in scn_host.h (tests/cpp/test_plan_math.cpp builds the
+// unit with g++ under the sanitizers); the .hip suffix only puts it through the same compiler as the rest of the library.
+#include "scn_host.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+static thread_local std::string g_last_error;
+
+int scn_fail(int status, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  g_last_error = buf;
+  return status;
+}
+
+size_t bytes_per_sample(uint32_t kind) {
+  switch (kind) {
+    case SCN_KIND_BYTE_COMPLEX: return 2;
+    case SCN_KIND_SHORT:
+    case SCN_KIND_SHORT_COMPLEX: return 4;
+    case SCN_KIND_FLOAT_COMPLEX: return 8;
+    default: return 0;
+  }
+}
+
+// `int16_t max = 1 << (enob - 1); float onebymax = float(1.0/max);` (utility.cpp:64-65,
+// :16-17) and the int8_t flavour (utility.cpp:40-41), including the narrowing wrap that
+// makes enob == width give a negative scale.
+float convert_scale(uint32_t kind, uint32_t enob) {
+  uint32_t one = 1u << ((enob - 1u) & 31u);
+  if (kind == SCN_KIND_BYTE_COMPLEX) return (float)(1.0 / (double)(int8_t)(uint8_t)one);
+  if (kind == SCN_KIND_SHORT || kind == SCN_KIND_SHORT_COMPLEX) return (float)(1.0 / (double)(int16_t)(uint16_t)one);
+  return 1.0f;
+}
+
+// gr::fft::window::build(type, N, 0.0) as process.cpp:18 calls it ([3P], GNU Radio 3.7 / 3.8): the published definitions --
+// cosine sums with the symmetric denominator N - 1 (Hamming 0.54 / 0.46, Hann 0.5 / 0.5, Blackman 0.42 / 0.5 / 0.08, 4-term
+// Blackman-Harris 0.35875 / 0.48829 / 0.14128 / 0.01168, flat-top 1 / 1.93 / 1.29 / 0.388 / 0.028 over 4.63867), the triangular
+// Bartlett window, Kaiser with the beta the call passes (0.0: I0(0) / I0(0) = 1 everywhere) -- evaluated in double, stored float.
+// scan.cpp:215 only ever asks for Blackman-Harris.
+bool build_window(uint32_t type, uint32_t n, std::vector<float> &w) {
+  w.resize(n);
+  const double pi = 3.14159265358979323846, m = (double)n - 1.0, flat = 4.63867;
+  double c[5] = {0, 0, 0, 0, 0};
+  switch (type) {
+    case SCN_WIN_HAMMING: c[0] = 0.54; c[1] = 0.46; break;
+    case SCN_WIN_HANN: c[0] = 0.5; c[1] = 0.5; break;
+    case SCN_WIN_BLACKMAN: c[0] = 0.42; c[1] = 0.5; c[2] = 0.08; break;
+    case SCN_WIN_RECTANGULAR:
+    case SCN_WIN_KAISER:
+      std::fill(w.begin(), w.end(), 1.0f);
+      return true;
+    case SCN_WIN_BLACKMAN_HARRIS: c[0] = 0.35875; c[1] = 0.48829; c[2] = 0.14128; c[3] = 0.01168; break;
+    case SCN_WIN_BARTLETT:
+      for (uint32_t i = 0; i < n; i++) w[i] = (float)(i < n / 2 ? 2.0 * (double)i / m : 2.0 - 2.0 * (double)i / m);
+      return true;
+    case SCN_WIN_FLATTOP: c[0] = 1.0 / flat; c[1] = 1.93 / flat; c[2] = 1.29 / flat; c[3] = 0.388 / flat; c[4] = 0.028 / flat; break;
+    default: return false;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const double x = (double)i / m;
+    w[i] = (float)(c[0] - c[1] * std::cos(2.0 * pi * x) + c[2] * std::cos(4.0 * pi * x) - c[3] * std::cos(6.0 * pi * x) + c[4] * std::cos(8.0 * pi * x));
+  }
+  return true;
+}
+
+// In-place forward DFT of a power-of-two length in double (plan creation only: the Bluestein filter's transform).
+void host_fft(std::vector<double> &re, std::vector<double> &im) {
+  const size_t n = re.size();
+  for (size_t i = 1, j = 0; i < n; i++) {  // bit reversal
+    size_t bit = n >> 1;
+    for (; j & bit; bit >>= 1) j ^= bit;
+    j ^= bit;
+    if (i < j) {
+      std::swap(re[i], re[j]);
+      std::swap(im[i], im[j]);
+    }
+  }
+  const double pi = 3.14159265358979323846;
+  for (size_t len = 2; len <= n; len <<= 1) {
+    for (size_t k = 0; k < len / 2; k++) {
+      const double a = -2.0 * pi * (double)k / (double)len, wr = std::cos(a), wi = std::sin(a);
+      for (size_t i = k; i < n; i += len) {
+        const size_t j = i + len / 2;
+        const double xr = re[j] * wr - im[j] * wi, xi = re[j] * wi + im[j] * wr;
+        re[j] = re[i] - xr;
+        im[j] = im[i] - xi;
+        re[i] += xr;
+        im[i] += xi;
+      }
+    }
+  }
+}
+
+template <class T>
+std::vector<T> twiddles(uint32_t m) {
+  std::vector<T> tw(2 * (size_t)m);
+  const double pi = 3.14159265358979323846;
+  for (uint32_t k = 0; k < m; k++) {
+    const double a = -2.0 * pi * (double)k / (double)m;
+    tw[2 * k] = (T)std::cos(a);
+    tw[2 * k + 1] = (T)std::sin(a);
+  }
+  return tw;
+}
+template std::vector<float> twiddles<float>(uint32_t);
+template std::vector<double> twiddles<double>(uint32_t);
+
+// The tables of a Bluestein plan.  The transform length m: the power of two >= 2n - 1; w[i] = exp(-i pi i^2 / n) with i^2 reduced
+// mod 2n in integers; the filter b[k] = conj(w[|k|]) laid out cyclically over m points, transformed here in double (m <= 131072)
+// and scaled by 1/m (the second device transform is an inverse one up to conjugations, which needs that factor)
+ScnBluesteinTables bluestein_tables(uint32_t n) {
+  ScnBluesteinTables t;
+  for (t.log2m = 0; (1u << t.log2m) < 2u * n - 1u; t.log2m++) {
+  }
+  const uint32_t m = t.m = 1u << t.log2m;
+  const double pi = 3.14159265358979323846;
+  std::vector<double> br(m, 0.0), bi(m, 0.0);
+  t.chirp.resize(2 * (size_t)n);
+  for (uint32_t i = 0; i < n; i++) {
+    const double a = -pi * (double)(((uint64_t)i * i) % (2ull * n)) / (double)n;
+    t.chirp[2 * i] = std::cos(a);
+    t.chirp[2 * i + 1] = std::sin(a);
+    br[i] = std::cos(a);
+    bi[i] = -std::sin(a);
+    if (i) {
+      br[m - i] = br[i];
+      bi[m - i] = bi[i];
+    }
+  }
+  host_fft(br, bi);
+  t.bfilter.resize(2 * (size_t)m);
+  for (uint32_t k = 0; k < m; k++) {
+    t.bfilter[2 * k] = br[k] / (double)m;
+    t.bfilter[2 * k + 1] = bi[k] / (double)m;
+  }
+  t.twiddle = twiddles<double>(m);
+  return t;
+}
+
+// scn_plan_desc.floor_permille with its default applied (0 -> 500, SCN_FLOOR_MIN -> 0); false for a value outside the descriptor's
+bool floor_permille_of(uint32_t given, uint32_t *permille) {
+  if (given == SCN_FLOOR_MIN) *permille = 0;
+  else if (given == 0) *permille = 500;
+  else if (given <= 1000u) *permille = given;
+  else return false;
+  return true;
+}
+
+// The mask of process.cpp:46-52 exactly as the kernels apply it (uint32 arithmetic), with the descriptor's defaults already
+// applied: i_lo / i_hi, and the number of natural bins it lets through
+uint32_t evaluated_bins(uint32_t n, uint32_t dc_ignore, double use_bandwidth, uint32_t *i_lo, uint32_t *i_hi) {
+  // process.cpp:85 m_useWindow = uint32_t(useBandWidth * numSamples / 2.0); :51 bounds in uint32
+  const uint32_t use_window = (uint32_t)(use_bandwidth * n / 2.0);
+  const struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {dc_ignore, n / 2 - use_window, n / 2 + use_window};
+  uint32_t kept = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t j = (i + n / 2) % n;
+    kept += scn_bin_evaluated(j, i, n, mask);
+  }
+  if (i_lo) *i_lo = mask.i_lo;
+  if (i_hi) *i_hi = mask.i_hi;
+  return kept;
+}
+
+// Averaged plans: a submit's arguments alone decide whether it can run -- checked before any copy or kernel is queued
+int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc) {
+  if (nb % k) return scn_fail(SCN_E_INVALID, "n_buffers %u is not a multiple of average %u", nb, k);
+  if (!fc) return SCN_OK;
+  const uint32_t ng = nb / k;
+  for (uint32_t g = 0; g < ng; g++) {
+    const size_t b0 = sweeps ? g : (size_t)g * k;
+    for (uint32_t b = 1; b < k; b++) {
+      const size_t bb = sweeps ? g + (size_t)b * ng : (size_t)g * k + b;
+      if (!(fc[bb] == fc[b0]))
+        return scn_fail(SCN_E_INVALID, "center_freqs differ inside group %u (buffer %zu: %.17g, its first buffer: %.17g)", g, bb, fc[bb],
+                        fc[b0]);
+    }
+  }
+  return SCN_OK;
+}
+
+// (the arguments were checked by check_average before anything was queued)
+uint32_t group_headers(uint32_t k, bool sweeps, uint32_t nb, const double *&fc, const uint64_t *&seq, std::vector<double> &group_fc,
+                       std::vector<uint64_t> &group_seq) {
+  const uint32_t ng = nb / k;
+  auto buffer_of = [&](uint32_t g, uint32_t b) -> size_t { return sweeps ? g + (size_t)b * ng : (size_t)g * k + b; };
+  if (fc) {
+    group_fc.resize(ng);
+    for (uint32_t g = 0; g < ng; g++) group_fc[g] = fc[buffer_of(g, 0)];
+    fc = group_fc.data();
+  }
+  if (seq || !sweeps) {  // (sweeps without seq_ids: group g's first buffer is buffer g, the compaction kernel's default)
+    group_seq.resize(ng);
+    for (uint32_t g = 0; g < ng; g++) group_seq[g] = seq ? seq[buffer_of(g, 0)] : (uint64_t)buffer_of(g, 0);
+    seq = group_seq.data();
+  }
+  return ng;
+}
+
+extern "C" {
+
+const char *scn_error_name(int status) {
+  switch (status) {
+    case SCN_OK: return "SCN_OK";
+    case SCN_E_INVALID: return "SCN_E_INVALID";
+    case SCN_E_HIP: return "SCN_E_HIP";
+    case SCN_E_NOMEM: return "SCN_E_NOMEM";
+    case SCN_E_STATE: return "SCN_E_STATE";
+    case SCN_E_TRUNCATED: return "SCN_E_TRUNCATED";
+    case SCN_E_NO_DEVICE: return "SCN_E_NO_DEVICE";
+    case SCN_E_COMM: return "SCN_E_COMM";
+    default: return "SCN_E_UNKNOWN";
+  }
+}
+
+const char *scn_last_error(void) { return g_last_error.c_str(); }
+
+uint32_t scn_abi_version(void) { return SCN_ABI_VERSION; }
+
+int scn_signals_from_hits(const scn_hit *hits, uint64_t n_hits, uint32_t n, uint32_t sample_rate, uint32_t max_gap, scn_signal *signals,
+                          uint64_t cap, uint64_t *n_signals) {
+  if (!n_signals) return scn_fail(SCN_E_INVALID, "null argument");
+  *n_signals = 0;
+  if ((!hits && n_hits) || (!signals && cap)) return scn_fail(SCN_E_INVALID, "null argument");
+  if (n == 0) return scn_fail(SCN_E_INVALID, "n = 0");
+  const uint32_t bin_step = sample_rate / n;  // process.cpp:39 (truncating)
+  uint64_t total = 0;
+  scn_signal cur = {};
+  for (uint64_t k = 0; k < n_hits; k++) {
+    const scn_hit &h = hits[k];
+    const bool start = k == 0 || h.seq_id != hits[k - 1].seq_id || h.i <= hits[k - 1].i ||  // a new unit
+                       (uint64_t)h.i - hits[k - 1].i > (uint64_t)max_gap + 1u;
+    if (start) {
+      if (k && total <= cap) signals[total - 1] = cur;
+      total++;
+      cur.seq_id = h.seq_id;
+      cur.first_i = cur.peak_i = h.i;
+      cur.peak_power_db = h.power_db;
+      cur.peak_freq_hz = h.freq_hz;
+      cur.n_hits = 0;
+    } else if (h.power_db > cur.peak_power_db) {  // (equal powers: the lowest i stays)
+      cur.peak_i = h.i;
+      cur.peak_power_db = h.power_db;
+      cur.peak_freq_hz = h.freq_hz;
+    }
+    cur.last_i = h.i;
+    cur.n_hits++;
+    cur.bandwidth_hz = (cur.last_i - cur.first_i + 1u) * bin_step;
+  }
+  if (total && total <= cap) signals[total - 1] = cur;
+  *n_signals = total;
+  if (total > cap) return scn_fail(SCN_E_TRUNCATED, "%llu signals, the first %llu returned", (unsigned long long)total, (unsigned long long)cap);
+  return SCN_OK;
+}
+
+int scn_floor_from_spectrum(const float *power_db, uint32_t n, uint32_t dc_ignore_bins, double use_bandwidth, uint32_t floor_permille,
+                            float *floor_db) {
+  if (!power_db || !floor_db) return scn_fail(SCN_E_INVALID, "null argument");
+  if (n == 0 || n > (1u << 24)) return scn_fail(SCN_E_INVALID, "bad bin count %u", n);
+  uint32_t permille = 0;
+  if (!floor_permille_of(floor_permille, &permille))
+    return scn_fail(SCN_E_INVALID, "floor_permille %u: 0 (the median), 1 ... 1000 or SCN_FLOOR_MIN", floor_permille);
+  if (!dc_ignore_bins) dc_ignore_bins = 4;  // the descriptor's defaults (scn_plan_create)
+  if (dc_ignore_bins == SCN_DC_IGNORE_NONE) dc_ignore_bins = 0;
+  if (use_bandwidth == 0.0) use_bandwidth = 0.75;
+  struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {dc_ignore_bins, 0, 0};
+  evaluated_bins(n, dc_ignore_bins, use_bandwidth, &mask.i_lo, &mask.i_hi);
+  std::vector<uint32_t> keys;
+  keys.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t j = (i + n / 2) % n;
+    if (!scn_bin_evaluated(j, i, n, mask)) continue;
+    uint32_t bits;
+    memcpy(&bits, power_db + j, sizeof(bits));
+    keys.push_back((bits & 0x80000000u) ? ~bits : (bits | 0x80000000u));
+  }
+  if (keys.empty()) return scn_fail(SCN_E_INVALID, "the mask (dc_ignore_bins, use_bandwidth) lets no bin through");
+  const size_t r = (size_t)((uint64_t)permille * (keys.size() - 1u) / 1000u);
+  std::nth_element(keys.begin(), keys.begin() + (ptrdiff_t)r, keys.end());
+  const uint32_t key = keys[r], bits = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;
+  memcpy(floor_db, &bits, sizeof(bits));
+  return SCN_OK;
+}
+
+int scn_frequency_table(uint32_t sample_rate, double start, double stop, double use_bandwidth,
+                        double dc_ignore_width, uint32_t shard, uint32_t n_shards, double *out, uint32_t cap,
+                        uint32_t *count, uint32_t *first) {
+  if (!count || n_shards == 0 || shard >= n_shards) return scn_fail(SCN_E_INVALID, "bad shard arguments");
+  // frequencyTable.cpp:17-29
+  double f1 = start + use_bandwidth / 2 * sample_rate;
+  double step = use_bandwidth;
+  if (dc_ignore_width > 0) step = (use_bandwidth - dc_ignore_width) / 2;
+  uint32_t total = 0;
+  if (stop == 0.0) {
+    total = 1;
+  } else {
+    if (!(step * (double)sample_rate > 0)) return scn_fail(SCN_E_INVALID, "frequency step must be positive");
+    while (f1 + total * step * (double)sample_rate < stop) total++;
+  }
+  // contiguous index range [lo, hi) of this shard
+  uint32_t lo = (uint32_t)((uint64_t)total * shard / n_shards);
+  uint32_t hi = (uint32_t)((uint64_t)total * (shard + 1) / n_shards);
+  if (first) *first = lo;
+  *count = hi - lo;
+  if (out)
+    for (uint32_t i = lo; i < hi && i - lo < cap; i++) out[i - lo] = f1 + i * step * (double)sample_rate;  // :33
+  return SCN_OK;
+}
+
+int scn_hackrf_sweep_fixup(void *transfer, uint32_t valid_length, uint32_t scan_offset_hz,
+                           double *center_frequency, uint32_t *n_mismatch) {
+  if (!transfer || !center_frequency) return scn_fail(SCN_E_INVALID, "null argument");
+  if (valid_length < 12) return scn_fail(SCN_E_INVALID, "a sweep transfer holds at least 6 samples");
+  uint8_t *head = static_cast<uint8_t *>(transfer);
+  const int8_t *samples = static_cast<const int8_t *>(transfer);
+  const uint32_t n_samples = valid_length / 2;  // :188
+  uint64_t tuned = 0;
+  uint32_t mismatches = 0;
+  // one pass per 8192-sample block, every pass looking at the head of the transfer (:191-192)
+  for (uint32_t first = 0; first < n_samples; first += 8192) {
+    if (head[0] != 0x7F || head[1] != 0x7F) continue;
+    uint64_t f = 0;
+    for (int k = 7; k >= 0; k--) f = (f << 8) | head[2 + k];  // :194-201
+    if (tuned != 0 && tuned != f) mismatches++;               // :202-206
+    tuned = f;
+    int8_t fill_i = (int8_t)head[10], fill_q = (int8_t)head[11];
+    if (first > 0) {  // :209-212, int arithmetic, truncating division, narrowed back to int8
+      fill_i = (int8_t)((fill_i + samples[2 * (first - 1)]) / 2);
+      fill_q = (int8_t)((fill_q + samples[2 * (first - 1) + 1]) / 2);
+    }
+    for (int j = 0; j < 5; j++) {
+      head[2 * j] = (uint8_t)fill_i;
+      head[2 * j + 1] = (uint8_t)fill_q;
+    }
+  }
+  *center_frequency = (double)(tuned + scan_offset_hz);  // u64 + u32, then to double (:221)
+  if (n_mismatch) *n_mismatch = mismatches;
+  return SCN_OK;
+}
+
+}  // extern "C"

@@ -1,8 +1,11 @@
-// scn_kernels.h -- internal interface between the C-ABI layer (scn_api.hip) and the
+// scn_kernels.h -- internal interface between the C-ABI layer (scn_plan.hip, scn_submit.hip,
+// scn_collect.hip, scn_welch_plan.hip) and the
 // kernels (scn_kernels.hip).  Not installed; the public surface is include/scanner_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "scn_mask.h"  // scn_bin_evaluated: K5's mask, shared with the host arithmetic
 
 // same numbering as messageQueue.h:31-37 / SCN_KIND_*
 #define SCN_K_BYTE_COMPLEX 1
@@ -44,19 +47,13 @@ struct ScnFftArgs {
   uint32_t hit_region;
   uint32_t *per_buffer_hits;  // [n_buffers] total hits of each buffer (device memory)
   uint32_t *host_hits;        // optional second copy of the same counts in pinned HOST memory, written by the kernel (see
-                              // scn_plan::direct_counts in scn_api.hip for when that beats a copy behind the kernel)
+                              // scn_plan::direct_counts in scn_plan.h for when that beats a copy behind the kernel)
   // buffer queue of the persistent workgroups: 8 heads, 32 words (one 128-byte line) apart, never reset; head x
   // serves the buffers b = 8 j + x; work_base[x] is its value before this launch and a launch adds exactly the
   // number of such buffers (scn_work_shard_count) to it
   uint32_t *work_counter;
   uint32_t work_base[8];
 };
-// K5's mask (process.cpp:46-52, uint32 arithmetic): is bin j of an n-point spectrum, fftshift index i = (j + n/2) % n, held
-// against the threshold?  `a` carries dc_ignore, i_lo and i_hi (the argument structs of every path; the host sizes hit_region by it)
-template <class A>
-__host__ __device__ __forceinline__ bool scn_bin_evaluated(uint32_t j, uint32_t i, uint32_t n, const A &a) {
-  return !(j < a.dc_ignore || (n - j) < a.dc_ignore) && !(i < a.i_lo || i > a.i_hi);
-}
 // which wire formats pull their buffers from the queue (the compute-bound integer ones; the float path is
 // memory-bound and measurably better off with the static assignment)
 // ... and only from 4096 points up: a launch of the same sample count makes 4x / 2x as many dequeues at 1024 / 2048

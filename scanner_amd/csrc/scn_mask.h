@@ -1,0 +1,17 @@
+// scn_mask.h -- K5's mask, the one piece of kernel-side arithmetic the host restates: shared by the kernels (through
+// scn_kernels.h) and by the plan arithmetic of scn_host.hip, which a plain C++ compiler builds without a HIP header in sight.
+#pragma once
+#include <stdint.h>
+
+#ifdef __HIPCC__  // (spelled out: what __forceinline__ stands for, since a unit without the HIP runtime header includes this too)
+#define SCN_HOST_DEVICE __host__ __device__ inline __attribute__((always_inline))
+#else
+#define SCN_HOST_DEVICE inline
+#endif
+
+// K5's mask (process.cpp:46-52, uint32 arithmetic): is bin j of an n-point spectrum, fftshift index i = (j + n/2) % n, held
+// against the threshold?  `a` carries dc_ignore, i_lo and i_hi (the argument structs of every path; the host sizes hit_region by it)
+template <class A>
+SCN_HOST_DEVICE bool scn_bin_evaluated(uint32_t j, uint32_t i, uint32_t n, const A &a) {
+  return !(j < a.dc_ignore || (n - j) < a.dc_ignore) && !(i < a.i_lo || i > a.i_hi);
+}

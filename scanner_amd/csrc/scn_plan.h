@@ -1,0 +1,175 @@
+// scn_plan.h -- what the units of the C-ABI layer share: the plan and its slots, and the helpers more than one of them calls.
+// scn_host.hip: arithmetic and entry points that never touch HIP; scn_plan.hip: create, tables, first-use allocation, destroy,
+// getters; scn_submit.hip / scn_collect.hip: the two sides of a slot; scn_welch_plan.hip: the Welch plan.
+//
+// A plan owns: one HIP stream, the window and twiddle tables, and SCN_NUM_SLOTS independent result slots (double buffering:
+// the host fills / drains one slot while the GPU works on the other -- the replacement for the reference's MemoryPool + bounded
+// queue, memoryPool.h:32-77 / messageQueue.h:65-91).  No call blocks on the GPU except scn_collect / scn_wait / scn_plan_destroy.
+// Ownership is in the types: a ScnDeviceMem / ScnPinnedMem / ScnEvent / ScnStream member (scn_resource.h) owns what it holds
+// and releases it with the plan; a raw pointer or hipStream_t borrows.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "scn_host.h"
+#include "scn_kernels.h"
+#include "scn_resource.h"
+
+#define SCN_HIP(call)                                                                              \
+  do {                                                                                             \
+    hipError_t e_ = (call);                                                                        \
+    if (e_ != hipSuccess)                                                                          \
+      return scn_fail(e_ == hipErrorOutOfMemory ? SCN_E_NOMEM : SCN_E_HIP, "%s failed: %s", #call, \
+                      hipGetErrorString(e_));                                                      \
+  } while (0)
+
+struct Slot {
+  ScnStream owned_stream;           // SCN_PLAN_OVERLAP_SLOTS, slots 1 ... : `stream` below when own_stream (first: destroyed last)
+  ScnDeviceMem<char> d_gen_work[2];  // scratch of the four-step and Bluestein paths (launch_transform)
+  ScnDeviceMem<float> d_avg_partial;  // averaged plans: the partial power sums between the two kernels of scn_average.hip
+  ScnPinnedMem<char> h_raw;         // pinned staging, max_batch raw buffers
+  ScnDeviceMem<char> d_raw;         // device copy of the staging slot
+  ScnDeviceMem<float> d_power;      // [max_batch][N] dB spectra (plan-owned destination)
+  float *cur_power = nullptr;       // destination of the pending submit (d_power, d_floor_power or the caller's)
+  ScnPinnedMem<float> h_td;         // time-domain mode: [2][max_batch] max / min dB, pinned, kernel-written
+  // [max_batch] hits per buffer.  The kernel writes device memory; a 4*n_buffers-byte D2H copy on
+  // the plan's d2h stream (ordered behind the kernel by an event) brings them to the pinned copy,
+  // so the compute stream carries nothing but the kernel.  (Letting the kernel store to pinned
+  // host memory directly was measured: the PCIe acknowledgements delay every kernel's completion
+  // by ~4 us, 5 % of a C2 launch.)
+  // Everything the FFT kernel writes for the hit list has TWO generations per slot, alternating per submit: the
+  // compaction of submit k may still be running (beside launch k+1) when launch k+2 starts writing -- with a
+  // generation of its own nothing has to wait, neither the host at submit nor the compute stream behind a barrier
+  // packet (measured: ~10 us per launch even when the barrier is already satisfied, ~16 us when it is not).
+  uint32_t gen = 0;                 // generation of the pending / last submit
+  ScnDeviceMem<uint32_t> d_buf_hits[2];
+  ScnPinnedMem<uint32_t> h_buf_hits;
+  unsigned long long *h_total = nullptr;  // pinned (the tail of h_buf_hits): the batch's total, stored by scn_hit_total_kernel
+  ScnDeviceMem<unsigned long long> d_total_acc;  // its two device words
+  bool total_ready = false;         // the pending / last submit's total is (going to be) in *h_total and its trigger flags, one bit per buffer, in the
+                                    // front of h_buf_hits: the counts themselves stayed on the GPU and scn_collect walks nothing
+  ScnEvent kernel_done, staged;
+  hipStream_t stream = nullptr;     // where this slot's kernels run: the plan's compute stream, or its own (SCN_PLAN_OVERLAP_SLOTS)
+  // buffer-queue heads of the persistent workgroups (ScnFftArgs::work_counter; 8 heads, never reset) and their values
+  // before the next launch (host-tracked).  Per slot: with overlapped slots two launches pull concurrently.
+  ScnDeviceMem<uint32_t> d_work_counter;
+  uint32_t work_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  bool own_stream = false;
+  ScnDeviceMem<ScnDevHit> d_hits[2];  // [max_batch][hit_region] per-buffer hit regions (unordered, scn_kernels.hip)
+  // the ordered list (scn_hits.hip): offsets = exclusive scan of the counts; h_meta = the submit's MessageHeader
+  // fields, pinned, read by the compaction kernel in place; d_list = the first max_hits completed records; h_list =
+  // their pinned host copy (prefetched of them are there); d_window = where scn_collect_more re-runs the compaction
+  // for a window beyond max_hits
+  ScnDeviceMem<uint32_t> d_offsets;
+  ScnPinnedMem<double> h_meta;      // pinned, two generations of {[max_batch] doubles, [max_batch] u64}
+  ScnDeviceMem<scn_hit> d_list;     // device [max_hits]
+  ScnPinnedMem<scn_hit> h_list;     // pinned [max_hits]
+  uint32_t prefetched = 0;          // leading records of the current list that are (being) copied to h_list
+  ScnEvent list_done[2];                         // per generation: scan + compaction (+ prefetch) finished
+  bool list_used[2] = {false, false};            // ... and whether that event has ever been recorded
+  bool seq_given[2] = {false, false};            // per generation: the submit came with sequence ids (else: the buffer's index)
+  int64_t table_first[2] = {-1, -1};             // per generation: the submit named a range of the plan's frequency table (else -1: its own centres in h_meta)
+  bool list_valid = false;          // regions, counts and offsets of the last collected submit are still on the device
+  bool list_built = false;          // the scan + compaction of the pending / last submit have been enqueued
+  uint32_t total_hits = 0;          // of the last collected submit
+  ScnDeviceMem<scn_hit> d_window;   // scratch of scn_collect_more, grown on demand
+  // scn_collect_signals: signals per unit and their exclusive scan ([max_batch], [max_batch + 1]; allocated at the first call),
+  // and the window of records the build kernel writes before they are copied out (grown on demand, like d_window)
+  ScnDeviceMem<uint32_t> d_sig_counts, d_sig_offsets;
+  ScnDeviceMem<scn_signal> d_sig_window;
+  // floor-detector plans (scn_floor.hip): floor_db of the pending / last submit's units, kernel-written device memory and the pinned
+  // copy a DMA behind the counts' brings (scn_collect_floor reads it).  ONE generation of each is enough, unlike the regions and
+  // counts: the only reader of d_floor is that DMA, which is complete when `done` is -- and a slot is not submitted again before
+  // its collect has waited for `done` --, and h_floor is promised only until the slot's next submit.
+  ScnDeviceMem<float> d_floor;      // [max_batch]
+  ScnPinnedMem<float> h_floor;      // [max_batch]
+  ScnDeviceMem<float> d_floor_power;  // [max_batch][N] the spectrum the detect kernel reads when the caller keeps none (hits-only floor plans)
+  ScnEvent done;
+  bool pending = false;
+  uint32_t n_buffers = 0;
+};
+
+// How a plan computes its spectrum: decided once, by path_of, and read by everything that depends on it
+enum class Path { TimeDomain, FusedPow2, FusedMixed, FourStep, Bluestein, Unsupported };
+
+// Where the ordered hit list of a submit is built: behind the kernel on the list stream, overlapping the next launch (plus a
+// DMA of the expected number of records to pinned host memory), IF the plan's previous collect asked for records; otherwise
+// on demand, when a collect call asks -- callers that only want counts / trigger flags pay nothing.  (Measured alternatives,
+// profiles/r02_compact_modes5.txt: always in order on the compute stream costs 60 us per step; always on demand puts the
+// list on the caller's critical path.)
+struct scn_plan {
+  // (the streams first: destroyed after the slots, the memory and the events that were used on them)
+  ScnStream stream;       // compute
+  ScnStream h2d_stream;   // staging copies of scn_submit (overlap the other slot's kernel)
+  ScnStream d2h_stream;   // per-buffer hit counts back to the host
+  ScnStream list_stream;  // the ordered hit list: scan + compaction kernels, the list's DMA
+  scn_plan_desc d;
+  int num_cus = 0;
+  bool records_wanted = false;  // does the caller take hit records? (decides where the next list is built: scn_collect sets it)
+  // Callers that read the records in place (scn_collect for the counts, then scn_hits_view -- only when there ARE hits) never
+  // pass scn_collect a record buffer: the view marks the plan, and the mark wears off after four collects in a row that had
+  // hits and were not followed by a view.  (Until round 5 every scn_collect without a buffer cleared records_wanted, so after
+  // any batch without a detection the next submit was not eager and the first batch with hits built its list on demand, on
+  // the consumer's critical path.)
+  uint32_t view_age = 0xffffffffu;  // collects with hits since the last scn_hits_view (saturating; "never" at first)
+  uint32_t device_list_age = 0xffffffffu;  // ... since the last scn_gather_hits_device / scn_gather_post took a slot's list where it lies
+  bool device_list_wanted = false;         // the ordered list is built behind every launch, without the prefetch to pinned memory
+  uint32_t predict = 0;         // records the next list is expected to hold (last total + a margin, scn_collect): the prefetch size
+  uint32_t last_total = 0;      // the total before that: the margin grows with the change between consecutive batches
+  // How the per-buffer counts reach the host.  false: a 4*n_buffers-byte copy on the d2h stream behind the kernel -- on
+  // this ROCm a blit KERNEL, which runs beside the next launch when that leaves it room (up to 4096 points: yes, ~6 us)
+  // and otherwise waits until that launch drains (8192 points: 254 VGPRs x 2 waves per SIMD; the copy took 46 us, the
+  // host learned the counts late and submitted the launch after next ~10 us late, every other launch).  true: the FFT
+  // kernel stores each count to pinned host memory as well (one 4-byte PCIe write per buffer; costs a 4096-point launch
+  // ~4 us of completion latency, measured in round 1, and the 8192-point ones less than the late copy did).
+  bool direct_counts = false;
+  Path path = Path::Unsupported;
+  uint32_t avg = 1, avg_layout = SCN_AVG_DWELL;  // scn_plan_desc.average / average_layout with the defaults applied
+  bool floor = false;       // scn_plan_desc.detect == SCN_DETECT_FLOOR: the transform stores the spectrum only, scn_floor.hip detects on it
+  uint32_t floor_rank = 0;  // ... and the floor is the value of this rank among the hit_region evaluated bins
+  uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
+  ScnDeviceMem<double> d_twiddle64;  // four-step: [256][2] W_256^k; Bluestein: [fft_m][2] W_m^k; in double
+  ScnDeviceMem<double> d_table;      // the plan's frequency table (scn_plan_set_table), read by the compaction kernel; grown on demand
+  uint32_t table_count = 0;          // entries in use
+  ScnDeviceMem<double> d_chirp;      // Bluestein: [n][2], w[i] = exp(-i pi i^2 / n)
+  ScnDeviceMem<double> d_bfilter;    // Bluestein: [fft_m][2], FFT_m of the chirp filter / m
+  size_t buf_bytes = 0;
+  float scale = 1.0f;
+  uint32_t i_lo = 0, i_hi = 0;
+  uint32_t hit_region = 0;  // hit slots each buffer owns = the bins the mask of process.cpp:46-52 evaluates (cannot overflow)
+  std::vector<float> h_window;
+  ScnDeviceMem<float> d_window;
+  ScnDeviceMem<scn_v2f> d_twiddle;
+  ScnDeviceMem<scn_v2f> d_tw1_table;  // [15][n/16], ScnFftArgs::tw1_table
+  ScnDeviceMem<scn_v2f> d_avg_tw1;    // averaged 8192-point plans: ScnAvgArgs::tw1_half ([15][256], W_4096^(t p))
+  ScnDeviceMem<double> d_avg_tw;      // ... and ScnAvgArgs::tw_half ([4096][2], W_8192^k in double)
+  // scn_convert_raw's device staging (the capture writer calls it per record): plan-owned, grown on demand, never per call
+  ScnDeviceMem<char> d_conv_in;
+  ScnDeviceMem<scn_v2f> d_conv_out;
+  Slot slot[SCN_NUM_SLOTS];
+};
+
+// `count` elements of D in device memory, filled from v (a synchronous copy: plan creation only)
+template <class D, class T>
+hipError_t upload(ScnDeviceMem<D> &dst, const std::vector<T> &v) {
+  const hipError_t e = dst.alloc(v.size() * sizeof(T) / sizeof(D));
+  return e != hipSuccess ? e : hipMemcpy(dst.get(), v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+}
+
+// scn_plan.hip
+int check_slot(scn_plan *p, int slot);
+int ensure_slot_stream(scn_plan *p, Slot &s);
+int ensure_slot_outputs(scn_plan *p, Slot &s, uint32_t gen);
+
+// scn_collect.hip
+ScnCompactArgs compact_args(const scn_plan *p, const Slot &s, uint32_t first, uint32_t cap, void *out);
+int build_list(scn_plan *p, Slot &s, bool prefetch);
+// (for scn_gather.hip) the collected slot's ordered list where the compaction kernel left it, in device memory.
+// list_ready == nullptr: the call returns when the list is complete (the host waits for the list kernels).  Otherwise *list_ready
+// receives the event that marks its completion (nullptr when there is nothing to wait for) and the caller orders its own stream
+// behind it (hipStreamWaitEvent): nothing waits on the host -- what scn_gather_post needs to stay out of the sweep loop's way.
+int scn_plan_device_hits(scn_plan *p, int slot, const scn_hit **d_list, uint32_t *n, int *device_id, void **list_ready = nullptr);
+
+// the stream the slot's ordered list is built and fetched on
+inline hipStream_t list_stream_of(const scn_plan *p, const Slot &s) { return s.own_stream ? s.stream : p->list_stream.get(); }

@@ -1,0 +1,399 @@
+// scn_submit.hip -- the submit side of the C-ABI: the transform's launch on the slot's stream and what follows it there and on
+// the side streams (counts, total, floor, the eager list), the frequency table, and K1 alone for the capture path.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "scn_plan.h"
+
+namespace {
+
+// Buffers per launch from which the batch's total and its trigger flags come from a reduction on the GPU (scn_hit_total_kernel, on the
+// launch's own stream, storing into pinned memory) instead of the counts crossing PCIe and the host walking them.  The reduction takes
+// ~6 us of the compute stream per launch; the counts' DMA it replaces runs beside the next launch but costs three more host calls and
+// 4 bytes per buffer of PCIe.  Measured on one box (profiles/r06_total_ab.txt, us per step of the spectrum + hits leg, counts by DMA ->
+// reduction): 524288 x 16 points 56.5 -> 37.1, 262144 x 64: 74.0 -> 51.5, 262144 x 128: 88.1 -> 82.6, but 131072 x 256: 75.0 -> 81.8,
+// 65536 x 512: 75.0 -> 80.9, 32768 x 1024: 74.8 -> 81.9 -- it pays from 2^18 buffers per launch.  (Round 5's form -- the reduction on
+// a side stream behind an event, the flags still by DMA -- paid only from 2^19: profiles/r05_table_ab.txt.)
+#ifndef SCN_TOTAL_KERNEL_FROM
+#define SCN_TOTAL_KERNEL_FROM (1u << 18)
+#endif
+constexpr uint32_t kTotalKernelFrom = SCN_TOTAL_KERNEL_FROM;
+
+// The input, the window and the K4 / K5 epilogue: the fields every transform's argument struct carries under the same names
+template <class A>
+void set_common_args(A &a, const scn_plan *p, const Slot &s, const void *d_raw, uint32_t nb, float *d_power) {
+  a.raw = d_raw;
+  a.window = p->d_window.get();
+  a.power_db = d_power;
+  a.n_buffers = nb;
+  a.scale = p->scale;
+  a.threshold = p->d.threshold;
+  a.dc_ignore = p->d.dc_ignore_bins;
+  a.i_lo = p->i_lo;
+  a.i_hi = p->i_hi;
+  a.hits = s.d_hits[s.gen].get();
+  a.hit_region = p->hit_region;
+  a.per_buffer_hits = s.d_buf_hits[s.gen].get();
+}
+
+// The transform of a submit on the slot's stream: the only code that knows which launcher and which argument struct a path
+// uses.  host_hits: where a fused kernel stores the counts as well (or nullptr); stop: an event a fused kernel's own
+// dispatch packet completes (or nullptr)
+int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float *d_power, uint32_t *host_hits, hipEvent_t stop) {
+  const uint32_t n = p->d.n;
+  const int kind = (int)p->d.sample_kind;
+  // (a floor plan's transform reports the spectrum only: its hits come from the detect kernel behind it, launch_floor)
+  const bool hits = (p->d.flags & SCN_OUT_HITS) != 0 && !p->floor, dc = p->d.correct_dc != 0;
+  if (p->avg > 1u) {  // nb buffers = nb / K groups (scn_average.hip)
+    const uint32_t ng = nb / p->avg;
+    if (ng) SCN_HIP(s.d_avg_partial.alloc(scn_avg_partial_floats(n, p->d.max_batch / p->avg, p->num_cus)));
+    ScnAvgArgs a;
+    memset(&a, 0, sizeof(a));
+    a.raw = d_raw;
+    a.window = p->d_window.get();
+    a.twiddle = p->d_twiddle.get();
+    a.tw1_table = p->d_tw1_table.get();
+    a.tw1_half = p->d_avg_tw1.get();
+    a.tw_half = reinterpret_cast<const double2_scn *>(p->d_avg_tw.get());
+    a.partial = s.d_avg_partial.get();
+    a.power_db = d_power;
+    a.n = n;
+    a.n_groups = ng;
+    a.k = p->avg;
+    a.parts = scn_avg_parts(n, ng, p->avg, p->num_cus);
+    a.layout = p->avg_layout == SCN_AVG_SWEEPS ? SCN_AVG_L_SWEEPS : SCN_AVG_L_DWELL;
+    a.scale = p->scale;
+    a.threshold = p->d.threshold;
+    a.p_lo = scn_hit_prefilter(p->d.threshold);
+    a.dc_ignore = p->d.dc_ignore_bins;
+    a.i_lo = p->i_lo;
+    a.i_hi = p->i_hi;
+    a.hits = s.d_hits[s.gen].get();
+    a.hit_region = p->hit_region;
+    a.per_group_hits = s.d_buf_hits[s.gen].get();
+    SCN_HIP(scn_launch_average(kind, dc && kind != SCN_KIND_FLOAT_COMPLEX, hits, d_power != nullptr, a, p->num_cus, s.stream));
+    return SCN_OK;
+  }
+  switch (p->path) {
+    case Path::FusedPow2:
+    case Path::FusedMixed: {
+      ScnFftArgs a;
+      memset(&a, 0, sizeof(a));
+      set_common_args(a, p, s, d_raw, nb, d_power);
+      a.twiddle = p->d_twiddle.get();
+      a.tw1_table = p->d_tw1_table.get();
+      a.p_lo = scn_hit_prefilter(p->d.threshold);
+      a.host_hits = host_hits;
+      a.work_counter = s.d_work_counter.get();
+      for (uint32_t x = 0; x < 8; x++) a.work_base[x] = s.work_base[x];
+      if (p->path == Path::FusedMixed) {
+        SCN_HIP(scn_launch_mixed(n, kind, dc, hits, d_power != nullptr, a, p->num_cus, s.stream, stop));
+        return SCN_OK;
+      }
+      // (a hits-only plan handed a caller's spectrum destination runs the full kernel)
+      SCN_HIP(scn_launch_fft(n, kind, dc, hits, d_power != nullptr, a, p->num_cus, s.stream, stop));
+      if (scn_uses_queue(kind, n))
+        for (uint32_t x = 0; x < 8; x++) s.work_base[x] += scn_work_shard_count(nb, x);  // what this launch adds (wrapping, like the device side)
+      return SCN_OK;
+    }
+    case Path::FourStep: {
+      if (nb) SCN_HIP(s.d_gen_work[0].alloc(sizeof(float) * 2 * (size_t)n * p->d.max_batch));
+      ScnBigArgs a;
+      set_common_args(a, p, s, d_raw, nb, d_power);
+      a.twiddle = p->d_twiddle.get();
+      a.work = s.d_gen_work[0].get();
+      a.tw256 = reinterpret_cast<const double2_scn *>(p->d_twiddle64.get());
+      a.p_lo = scn_hit_prefilter(p->d.threshold);
+      const bool int_dc = dc && p->d.sample_kind != SCN_KIND_FLOAT_COMPLEX;
+      if (nb && int_dc) SCN_HIP(s.d_gen_work[1].alloc(sizeof(int) * 2 * (size_t)p->d.max_batch));
+      a.dc_sums = int_dc ? reinterpret_cast<int *>(s.d_gen_work[1].get()) : nullptr;
+      SCN_HIP(scn_launch_big(n, kind, int_dc, hits, d_power != nullptr, a, p->num_cus, s.stream));
+      return SCN_OK;
+    }
+    case Path::Bluestein: {
+      for (int g = 0; g < 2 && nb; g++)
+        SCN_HIP(s.d_gen_work[g].alloc(2u * sizeof(double) * (size_t)p->fft_m * p->d.max_batch));
+      ScnGenericArgs a;
+      set_common_args(a, p, s, d_raw, nb, d_power);
+      a.twiddle = p->d_twiddle64.get();
+      a.work0 = s.d_gen_work[0].get();
+      a.work1 = s.d_gen_work[1].get();
+      a.n = n;
+      a.m = p->fft_m;
+      a.log2m = p->log2m;
+      a.chirp = p->d_chirp.get();
+      a.bfilter = p->d_bfilter.get();
+      SCN_HIP(scn_launch_generic(kind, dc, hits, a, p->num_cus, s.stream));
+      return SCN_OK;
+    }
+    default: return scn_fail(SCN_E_STATE, "the plan has no transform");
+  }
+}
+
+// Floor plans: the detect kernel on the spectrum the transform has just stored, behind it on the slot's stream; nu units
+int launch_floor(scn_plan *p, Slot &s, const float *d_power, uint32_t nu) {
+  ScnFloorArgs a;
+  memset(&a, 0, sizeof(a));
+  a.power_db = d_power;
+  a.n = p->d.n;
+  a.n_units = nu;
+  a.rank = p->floor_rank;
+  a.threshold = p->d.threshold;
+  a.dc_ignore = p->d.dc_ignore_bins;
+  a.i_lo = p->i_lo;
+  a.i_hi = p->i_hi;
+  a.hits = s.d_hits[s.gen].get();
+  a.hit_region = p->hit_region;
+  a.counts = s.d_buf_hits[s.gen].get();
+  a.floor_db = s.d_floor.get();
+  SCN_HIP(scn_launch_floor(a, p->num_cus, s.stream));
+  return SCN_OK;
+}
+
+// fc == nullptr: the buffers carry entries table_first, table_first + 1, ... (wrapping) of the plan's frequency table
+int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const double *fc, const uint64_t *seq,
+                  float *d_power, uint32_t table_first = 0) {
+  // Averaged plans: from here on nb counts GROUPS -- the outputs, the records' headers, the counts and triggers are per group --
+  // and only the transform sees the buffers.  A group's header is that of its first buffer.
+  const uint32_t n_raw = nb;
+  std::vector<double> group_fc;
+  std::vector<uint64_t> group_seq;
+  if (p->avg > 1u) nb = group_headers(p->avg, p->avg_layout == SCN_AVG_SWEEPS, nb, fc, seq, group_fc, group_seq);
+  const bool will_flip = p->d.mode != SCN_MODE_TIME_DOMAIN && (p->d.flags & SCN_OUT_HITS) != 0 && nb != 0;
+  int st = ensure_slot_outputs(p, s, will_flip ? s.gen ^ 1u : s.gen);
+  if (st) return st;
+  const uint32_t n = p->d.n;
+  if (p->d.mode == SCN_MODE_TIME_DOMAIN) {
+    s.cur_power = nullptr;
+    s.n_buffers = nb;
+    ScnTdArgs a;
+    a.raw = d_raw;
+    a.n = n;
+    a.n_buffers = nb;
+    a.scale = p->scale;
+    a.max_db = s.h_td.get();
+    a.min_db = s.h_td.get() + p->d.max_batch;
+    SCN_HIP(scn_launch_time_domain((int)p->d.sample_kind, p->d.correct_dc != 0, a, p->num_cus, s.stream));
+    SCN_HIP(hipEventRecord(s.done.get(), s.stream));
+    s.pending = true;
+    return SCN_OK;
+  }
+  if (!d_power && (p->d.flags & SCN_OUT_SPECTRUM)) {
+    SCN_HIP(s.d_power.alloc((size_t)n * p->d.max_batch));
+    d_power = s.d_power.get();
+  }
+  s.cur_power = d_power;  // (what the caller may collect)
+  if (p->floor && !d_power && nb) {  // a hits-only floor plan: the same spectrum-only transform, into a buffer the caller never sees
+    SCN_HIP(s.d_floor_power.alloc((size_t)n * p->d.max_batch));
+    d_power = s.d_floor_power.get();
+  }
+  s.n_buffers = nb;
+  s.list_valid = false;
+  const bool hits = (p->d.flags & SCN_OUT_HITS) != 0;
+  s.list_built = false;
+  s.total_ready = false;
+  if (hits && nb) {
+    // this submit's generation; the only thing that can still be using it is the list (compaction + copy) of the submit TWO
+    // submits back ON THIS SLOT -- 2 x (slots in use) launches back on the plan -- wait for it on the host, where it never
+    // blocks in practice
+    // -- and the list of the submit before this one on this slot, whose compaction output (d_list) and pinned copy (h_list)
+    // exist once per slot: its prefetch DMA rides the D2H stream, which nothing on the list stream is ordered behind, so the
+    // next compaction must not start while it may still be reading d_list (a caller that collected counts only has not
+    // waited for it).  Both waits are host-side queries of events that completed long ago in any steady loop.
+    s.gen ^= 1u;
+    for (uint32_t g = 0; g < 2; g++)
+      if (s.list_used[g] && hipEventQuery(s.list_done[g].get()) != hipSuccess) SCN_HIP(hipEventSynchronize(s.list_done[g].get()));
+    // the header fields: read by the compaction kernel in place, over PCIe (two 8-byte reads per buffer that has hits;
+    // staging copies cost ~7 us each plus ~10 us of cross-engine hand-off, on the list's critical path)
+    double *h_fc = s.h_meta.get() + (size_t)2u * p->d.max_batch * s.gen;
+    uint64_t *h_seq = reinterpret_cast<uint64_t *>(h_fc + p->d.max_batch);
+    // the centres: copied when given; a submit that names a range of the plan's device-resident table writes none (the other
+    // 8 header bytes per buffer: 2 MB per launch of 262144 128-point buffers, written and then read back over PCIe)
+    s.table_first[s.gen] = fc ? -1 : (int64_t)table_first;
+    if (fc) memcpy(h_fc, fc, sizeof(double) * nb);
+    // sequence ids: copied when given; otherwise a buffer's id is its index and the compaction kernel computes it -- 8 of the
+    // 16 header bytes per buffer that made the 16 .. 128-point steps host-bound (524288 buffers per launch: 4 MB less to write)
+    s.seq_given[s.gen] = seq != nullptr;
+    if (seq) memcpy(h_seq, seq, sizeof(uint64_t) * nb);
+  }
+
+  // The per-buffer counts reach the host either by a DMA behind the kernel or by the kernel's own stores to pinned memory.
+  // Both have a price (profiles/r04_experiments.md section 10).  A store over PCIe holds its wave's in-order memory returns up:
+  // ~0.4 ns per buffer on the launch (8192 buffers: 73.5 -> 76.7 us; 32768 1024-point buffers: 75 -> 96 us).  A DMA that waits
+  // for a kernel or for another DMA starts ~20 us after it (the runtime resolves the dependency on the host): nothing in a
+  // steady loop of long launches, but the whole difference for short ones (2048 buffers per launch, three in flight: 25.5
+  // -> 19.3 us per step), and fatal when the ordered list's DMA shares the D2H stream with it (two per submit: 92 us per submit
+  // on that stream against 73 us of FFT; records read in place, three in flight: 373 .. 403 -> 429 Gsamples/s).  So the kernel
+  // stores the counts itself when the launch has few buffers or the list follows eagerly, and a DMA carries them otherwise.
+  const bool eager = hits && nb && (p->records_wanted || p->device_list_wanted);
+  // (floor plans take the route of the paths that are not fused: the detect kernel, not the transform, is the submit's last kernel,
+  //  and it stores the counts to device memory only -- counts by DMA or scn_hit_total_kernel, a marker event behind it)
+  const bool fused = (p->path == Path::FusedPow2 || p->path == Path::FusedMixed) && p->avg == 1u && !p->floor;
+  const bool direct = fused && (p->direct_counts || nb <= 4096u || eager);
+  // What follows the kernel: the counts (a DMA on the d2h stream: needs no CU -- or nothing, when the kernel stores them to
+  // pinned memory itself) and, when the caller is known to want records, the ordered list (two small kernels + a DMA on
+  // the list stream, beside the next launch).  With overlapped slots both follow the kernel on the slot's own stream --
+  // its next kernel is two submits away, and fewer streams keep both compute streams on hardware queues of their own
+  // (HIP maps streams onto 4 queues by default; with a fifth active stream the two compute streams ended up sharing one).
+  // launches of very many small buffers (total_path): the counts stay on the GPU -- a reduction behind the kernel, ON ITS STREAM, leaves the
+  // batch's total and one trigger bit per buffer in pinned memory (below)
+  const bool total_path = hits && !direct && nb >= kTotalKernelFrom;
+  hipStream_t cnt = (s.own_stream || direct || total_path) ? s.stream : p->d2h_stream.get();
+  hipStream_t lst = list_stream_of(p, s);
+  const bool fork_list = eager && lst != s.stream;
+  // ONE event marks the kernel's end for whoever waits for it: the host (`done`, when nothing else follows on the compute
+  // stream: counts stored by the kernel) or the side streams (`kernel_done`).  For LARGE launches it is completed by the
+  // kernel's own dispatch packet (hipExtLaunchKernel's stopEvent), otherwise by a marker packet behind the kernel.
+  // Measured (scripts/stop_event_check.sh, profiles/r02_stop_event.txt), us per step marker -> in-packet: 33.5 M-sample
+  // launches 75.6 -> 73.1 (4096-pt cfloat), 77 -> 74.5 (2048-pt), 60.2 -> 59.3 (int16); 67 M samples 144.5 -> 140.8; but
+  // 16.8 M samples 44 -> 46..58 and 8.4 M 31 -> 29..56 (erratic: short kernels that carry an event get serialised).
+  const bool after_is_done = cnt == s.stream && !s.own_stream;  // direct counts on the plan's stream
+  hipEvent_t after = (!nb || s.own_stream || total_path) ? nullptr : !hits ? s.done.get() : after_is_done ? s.done.get() : s.kernel_done.get();
+  const bool in_packet = after && fused && (uint64_t)nb * n >= (1u << 25);
+  st = launch_transform(p, s, d_raw, n_raw, d_power, (hits && direct) ? s.h_buf_hits.get() : nullptr, in_packet ? after : nullptr);
+  if (st) return st;
+  if (p->floor && nb && (st = launch_floor(p, s, d_power, nb))) return st;
+  if (hits && nb) {
+    if (after && !in_packet) SCN_HIP(hipEventRecord(after, s.stream));
+    if (cnt != s.stream) SCN_HIP(hipStreamWaitEvent(cnt, after, 0));
+    if (fork_list) SCN_HIP(hipStreamWaitEvent(lst, after, 0));
+    // launches of very many small buffers: the total and the trigger flags (a bit per buffer) by themselves -- the counts stay on
+    // the GPU, where the list kernels read them: nb / 8 bytes cross PCIe instead of 4 nb, and a collect walks nothing.  The
+    // reduction runs on the launch's own stream and stores into pinned memory itself: such a step is bound by the HOST's calls
+    // (a 16-point launch of 524288 buffers takes 27 us on the GPU, every HIP call 4 .. 5 us in a torch process), and this way a
+    // submit is three of them -- kernel, reduction, event -- where the route over the side stream took six (event, wait, reduction,
+    // DMA, event: 72 -> 56 us per step, profiles/r06_experiments.md section 5)
+    s.total_ready = total_path;
+    if (total_path) {
+      SCN_HIP(scn_launch_hit_total(s.d_buf_hits[s.gen].get(), nb, p->d.trigger_count, s.d_total_acc.get(), s.h_total, s.h_buf_hits.get(), cnt));
+    } else if (!direct) {
+      SCN_HIP(hipMemcpyAsync(s.h_buf_hits.get(), s.d_buf_hits[s.gen].get(), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, cnt));
+    }
+    if (p->floor) SCN_HIP(hipMemcpyAsync(s.h_floor.get(), s.d_floor.get(), sizeof(float) * nb, hipMemcpyDeviceToHost, cnt));  // the way the counts go
+    if (!(after_is_done && after)) SCN_HIP(hipEventRecord(s.done.get(), cnt));
+    if (eager) {
+      int st2 = build_list(p, s, p->records_wanted);  // (the prefetch to pinned memory only for a caller that reads the records on the host)
+      if (st2) return st2;
+    }
+  } else if (!(after && in_packet)) {  // spectrum-only plans: `done` follows the kernel on its stream
+    SCN_HIP(hipEventRecord(s.done.get(), s.stream));
+  }
+  s.pending = true;
+  return SCN_OK;
+}
+
+// What every submit checks before anything is queued, in this order: the batch's size, the entry point's own pointers, the averaged
+// plan's grouping, the slot (free; `host`: its staging buffer exists) -- then the plan's device is current and the slot's stream exists
+int begin_submit(scn_plan *p, int slot, uint32_t nb, const double *fc, bool null_argument, bool host) {
+  Slot &s = p->slot[slot];
+  if (nb > p->d.max_batch) return scn_fail(SCN_E_INVALID, "n_buffers %u > max_batch %u", nb, p->d.max_batch);
+  if (null_argument) return scn_fail(SCN_E_INVALID, "null argument");
+  if (p->avg > 1u)
+    if (int st = check_average(p->avg, p->avg_layout == SCN_AVG_SWEEPS, nb, fc)) return st;
+  if (s.pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit", slot);
+  if (host && !s.h_raw) return scn_fail(SCN_E_STATE, "slot %d: scn_host_buffer was never called", slot);
+  SCN_HIP(hipSetDevice(p->d.device_id));
+  return ensure_slot_stream(p, s);
+}
+
+// the pinned slot's buffers -> the GPU -> the kernels; fc == nullptr: entries first_index ... of the plan's frequency table
+int submit_host(scn_plan *p, int slot, uint32_t nb, const double *fc, const uint64_t *seq, uint32_t first_index) {
+  if (int st = begin_submit(p, slot, nb, fc, false, true)) return st;
+  Slot &s = p->slot[slot];
+  SCN_HIP(s.d_raw.alloc(p->buf_bytes * p->d.max_batch));
+  if (nb) {
+    // stage on the h2d stream so this copy overlaps the other slot's kernel; the compute stream
+    // picks it up through an event
+    SCN_HIP(s.staged.create());
+    SCN_HIP(hipMemcpyAsync(s.d_raw.get(), s.h_raw.get(), p->buf_bytes * nb, hipMemcpyHostToDevice, p->h2d_stream.get()));
+    SCN_HIP(hipEventRecord(s.staged.get(), p->h2d_stream.get()));
+    SCN_HIP(hipStreamWaitEvent(s.stream, s.staged.get(), 0));
+  }
+  return submit_common(p, s, s.d_raw.get(), nb, fc, seq, nullptr, first_index);
+}
+
+int check_indexed(scn_plan *p, uint32_t nb, uint32_t first_index) {
+  if (p->d.mode == SCN_MODE_TIME_DOMAIN || !(p->d.flags & SCN_OUT_HITS)) return SCN_OK;  // no records: nothing reads the table
+  if (nb && !p->table_count) return scn_fail(SCN_E_STATE, "scn_plan_set_table was never called");
+  if (nb && first_index >= p->table_count) return scn_fail(SCN_E_INVALID, "first_index %u outside the table of %u entries", first_index, p->table_count);
+  return SCN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int scn_submit(scn_plan *p, int slot, uint32_t nb, const double *fc, const uint64_t *seq) {
+  if (int st = check_slot(p, slot)) return st;
+  if (nb && !fc) return scn_fail(SCN_E_INVALID, "center_freqs is null");
+  return submit_host(p, slot, nb, fc, seq, 0);
+}
+
+int scn_submit_device(scn_plan *p, int slot, const void *d_raw, uint32_t nb, const double *fc, const uint64_t *seq,
+                      float *d_power_db) {
+  int st = check_slot(p, slot);
+  if (st) return st;
+  if ((st = begin_submit(p, slot, nb, fc, nb && (!fc || !d_raw), false))) return st;
+  return submit_common(p, p->slot[slot], d_raw, nb, fc, seq, d_power_db);
+}
+
+int scn_submit_indexed(scn_plan *p, int slot, uint32_t nb, uint32_t first_index, const uint64_t *seq) {
+  int st = check_slot(p, slot);
+  if (st) return st;
+  if ((st = check_indexed(p, nb, first_index))) return st;
+  return submit_host(p, slot, nb, nullptr, seq, first_index);
+}
+
+int scn_submit_device_indexed(scn_plan *p, int slot, const void *d_raw, uint32_t nb, uint32_t first_index, const uint64_t *seq,
+                              float *d_power_db) {
+  int st = check_slot(p, slot);
+  if (st) return st;
+  if ((st = check_indexed(p, nb, first_index))) return st;
+  if ((st = begin_submit(p, slot, nb, nullptr, nb && !d_raw, false))) return st;
+  return submit_common(p, p->slot[slot], d_raw, nb, nullptr, seq, d_power_db, first_index);
+}
+
+int scn_plan_set_table(scn_plan *p, const double *fc, uint32_t count) {
+  if (!p) return scn_fail(SCN_E_INVALID, "null plan");
+  if (count && !fc) return scn_fail(SCN_E_INVALID, "center_freqs is null");
+  for (int i = 0; i < SCN_NUM_SLOTS; i++)
+    if (p->slot[i].pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit: its records still read the table", i);
+  SCN_HIP(hipSetDevice(p->d.device_id));
+  // (a list of an already collected submit may still be being completed -- the prefetch of scn_collect, scn_collect_more --
+  // from the OLD table: wait for what THIS plan has queued on the streams that read the table, then forget those lists.  Not a
+  // device-wide synchronisation: other plans' pipelines and the caller's own streams on this GPU go on undisturbed.)
+  SCN_HIP(hipStreamSynchronize(p->list_stream.get()));
+  SCN_HIP(hipStreamSynchronize(p->d2h_stream.get()));
+  SCN_HIP(hipStreamSynchronize(p->h2d_stream.get()));
+  for (int i = 0; i < SCN_NUM_SLOTS; i++)  // (a slot with a stream of its own builds its list there)
+    if (p->slot[i].own_stream && p->slot[i].stream) SCN_HIP(hipStreamSynchronize(p->slot[i].stream));
+  for (int i = 0; i < SCN_NUM_SLOTS; i++) p->slot[i].list_valid = false;
+  p->table_count = 0;
+  if (!count) return SCN_OK;
+  if (count > p->d_table.capacity()) SCN_HIP(p->d_table.grow(count));  // (a caller that re-tables between sweeps keeps its allocation)
+  SCN_HIP(hipMemcpyAsync(p->d_table.get(), fc, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, p->list_stream.get()));
+  SCN_HIP(hipStreamSynchronize(p->list_stream.get()));  // (fc is the caller's: done with it before returning; the list kernels run on this stream, after the copy)
+  p->table_count = count;
+  return SCN_OK;
+}
+
+int scn_convert_raw(scn_plan *p, const void *raw, uint32_t nb, float *out) {
+  if (!p || (nb && (!raw || !out))) return scn_fail(SCN_E_INVALID, "null argument");
+  if (!nb) return SCN_OK;
+  SCN_HIP(hipSetDevice(p->d.device_id));
+  const size_t in_bytes = p->buf_bytes * nb, out_bytes = sizeof(float) * 2 * (size_t)p->d.n * nb;
+  if (p->d_conv_out.capacity() < (size_t)p->d.n * nb) {  // grow the plan's staging pair (the capture writer converts one record per call: one
+    p->d_conv_in.reset();                                // allocation, ever); the output, allocated last, vouches for both
+    p->d_conv_out.reset();
+    SCN_HIP(p->d_conv_in.alloc(in_bytes));
+    SCN_HIP(p->d_conv_out.alloc((size_t)p->d.n * nb));
+  }
+  SCN_HIP(hipMemcpyAsync(p->d_conv_in.get(), raw, in_bytes, hipMemcpyHostToDevice, p->d2h_stream.get()));
+  SCN_HIP(scn_launch_convert((int)p->d.sample_kind, p->d.correct_dc != 0, p->d_conv_in.get(), p->d_conv_out.get(), p->d.n, nb, p->scale, p->d2h_stream.get()));
+  SCN_HIP(hipMemcpyAsync(out, p->d_conv_out.get(), out_bytes, hipMemcpyDeviceToHost, p->d2h_stream.get()));
+  SCN_HIP(hipStreamSynchronize(p->d2h_stream.get()));
+  return SCN_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """Every shipped kernel specialisation of the fused path, deterministically: the sizes the LIBRARY says it runs fused
-(scn_size_path, so this list cannot drift from scn_api.hip's dispatch) x the four wire formats x DC removal off / on x the
+(scn_size_path, so this list cannot drift from scn_plan.hip's dispatch) x the four wire formats x DC removal off / on x the
 three output modes (spectrum only, spectrum + hits, hits only), each against the oracle on a seeded batch that is large
 enough to take every workgroup of the persistent launch through more than one buffer (prefetch, buffer queue, ragged last
 iteration) and whose threshold -- guard-band-free on the oracle's spectra -- sits in the noise tail, so that thousands of

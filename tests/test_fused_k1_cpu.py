@@ -15,7 +15,7 @@ them for the record.  The one way the fold can fail is a tap whose product with 
 float32(d) * scale cannot): asserted absent for every window type, size and ENOB below; were one present the GPU module would have to
 exempt that window.
 
-ENOB: convert_scale (scn_api.hip) computes max = intN_t(1 << (enob - 1)); from enob = width + 1 up the narrowing leaves max = 0 and
+ENOB: convert_scale (scn_host.hip) computes max = intN_t(1 << (enob - 1)); from enob = width + 1 up the narrowing leaves max = 0 and
 the scale is 1 / 0 = inf -- no conversion at all -- so the values with a finite scale are 1 ... 16 for the int16 kinds and 1 ... 8 for
 int8, and those are walked, the wrapping extremes (enob = width: a NEGATIVE scale) included.
 
@@ -36,7 +36,7 @@ TINY = np.float32(np.finfo(np.float32).tiny)
 
 
 def scale_of(width, enob):
-    """convert_scale of scn_api.hip / scale_for_i16, scale_for_i8 of the oracle, restated: float(1.0 / intN_t(1 << (enob - 1)))"""
+    """convert_scale of scn_host.hip / scale_for_i16, scale_for_i8 of the oracle, restated: float(1.0 / intN_t(1 << (enob - 1)))"""
     one = (1 << ((enob - 1) & 31)) & ((1 << width) - 1)
     mx = one - (1 << width) if one >> (width - 1) else one
     assert mx != 0, "enob beyond the width: max wraps to 0, the scale is infinite"

@@ -98,6 +98,24 @@ def test_worker_slot_ring_against_a_fake_plan(host_build, tmp_path, san):
     assert "worker ring tests ok" in out.stdout
 
 
+@pytest.mark.parametrize("san", ["address,undefined", ""])
+def test_plan_arithmetic_stand_alone(tmp_path, san):
+    """The C-ABI layer's host arithmetic (scanner_amd/csrc/scn_host.hip: the window, the twiddle and Bluestein tables, K1's scale,
+    K5's mask, the averaged plans' group headers, the entry points that need no device) compiled by plain g++ as C++17 -- no HIP
+    header on the include path, nothing of HIP linked -- into tests/cpp/test_plan_math.cpp's own program, and run: under
+    ASan + UBSan, which must report nothing, and plain."""
+    csrc = os.path.join(ROOT, "scanner_amd", "csrc")
+    exe = tmp_path / "test_plan_math"
+    cmd = ["g++", "-x", "c++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer"] + ([f"-fsanitize={san}"] if san else []) + [
+        "-Wall", "-I", csrc, os.path.join(ROOT, "tests", "cpp", "test_plan_math.cpp"), os.path.join(csrc, "scn_host.hip"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
+    assert out.returncode == 0 and "plan math tests ok" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+    assert "runtime error" not in out.stderr and "Sanitizer" not in out.stderr, out.stderr[-3000:]
+
+
 def test_abi_bench_refuses_what_it_does_not_understand(host_build):
     """bench.py's C++ child (the records legs): an unknown option or a depth outside the plan's slots is an error before
     anything touches the GPU, and without a GPU it says so instead of printing a line."""

@@ -159,7 +159,7 @@ def test_hip_against_an_independent_float32_fft(torch_cuda, n):
 
 
 def test_one_slot_alternating_counts_only_and_records_collects(torch_cuda, oracle_mod):
-    """The ordered list and its pinned copy exist ONCE per slot while regions and counts have two generations (scn_api.hip): a
+    """The ordered list and its pinned copy exist ONCE per slot while regions and counts have two generations (scn_plan.h): a
     caller that collects counts only on one submit and reads records on the next -- through scn_collect, through scn_hits_view,
     with batches without any detection in between -- must always see the records of THAT submit (the ordering of the
     prefetch DMA against the slot's next compaction; the eager / on-demand decision across scn_collect and scn_hits_view)."""
@@ -949,7 +949,7 @@ def test_ragged_batches(torch_cuda, oracle_mod, nb):
 
 def test_counts_by_kernel_stores_and_by_dma_agree(torch_cuda, oracle_mod):
     """The per-buffer counts reach the host by the kernel's own stores to pinned memory for launches of up to 4096 buffers
-    (and whenever the ordered list follows eagerly) and by a DMA above (scn_api.hip, submit_common): both sides of that
+    (and whenever the ordered list follows eagerly) and by a DMA above (scn_submit.hip, submit_common): both sides of that
     line, on one plan, counts-only collects first (no eager list), then with records (eager list: stores again)."""
     n, nb = 1024, 4200
     x = synth.cfloat_batch(n, nb, seed=77, max_tones=2)

@@ -44,7 +44,7 @@ def prefilter(tmp_path_factory):
     d = tmp_path_factory.mktemp("prefilter")
     src, exe = d / "drv.cpp", d / "drv"
     src.write_text(DRIVER)
-    # the compiler that builds the library (scn_api.hip calls the function in its host pass), host pass only
+    # the compiler that builds the library (scn_submit.hip calls the function in its host pass), host pass only
     subprocess.check_call([build.hipcc(), "-x", "hip", "--offload-host-only", "-std=c++17", "-O2", "-I", build.CSRC, str(src),
                            "-o", str(exe)])
 
