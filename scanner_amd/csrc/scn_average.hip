@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "scn_device.h"
+#include "scn_dispatch.h"
 #include "scn_kernels.h"
 
 // Build-time split as in scn_kernels.hip: SCN_AVG_TU 0 .. 3 instantiate the kernels of one size (1024, 2048, 4096, 8192);
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(16 * M, H == 1 ? 3 : 2) void scn_avg_power_kernel(S
 
   // sample s = H (T a + t) + h of a buffer: a stride-H view for the half h (H = 1: the buffer itself)
   auto rsrc_of = [&](uint32_t buf, bool live) {
-    return make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)buf * L::kBufBytes(NT), live ? L::kBufBytes(NT) : 0u);
+    return make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)buf * (L::kBytes * NT), live ? L::kBytes * NT : 0u);
   };
   typename L::raw_t raw[16];
   {
@@ -385,59 +386,50 @@ __global__ __launch_bounds__(1024) void scn_avg_combine_kernel(ScnAvgArgs args) 
 }
 #endif
 
+// a launch of the power kernel on its way to the translation unit that holds the size's kernels
+struct ScnAvgLaunch {
+  int kind;
+  bool dc, split, hits, spec;  // split: partial sums go out (parts > 1); else the output mode
+  const ScnAvgArgs &a;
+  uint32_t grid;
+  hipStream_t s;
+};
+
 namespace {
 // resident workgroups per CU of the power kernel: 12 / 6 / 3 / 2 at 1024 / 2048 / 4096 / 8192 points
 uint32_t avg_wg_per_cu(uint32_t n) {
   return n == 1024 ? AvgGeo<4, 1>::WG_PER_CU : n == 2048 ? AvgGeo<8, 1>::WG_PER_CU : n == 4096 ? AvgGeo<16, 1>::WG_PER_CU : AvgGeo<16, 2>::WG_PER_CU;
 }
 
-template <int M, int H, int KIND, bool DC, int OUT>
-hipError_t launch_power(const ScnAvgArgs &a, uint32_t grid, hipStream_t s) {
-  typedef AvgGeo<M, H> G;
-  hipLaunchKernelGGL((scn_avg_power_kernel<M, H, KIND, DC, OUT>), dim3(grid), dim3(G::T), G::LDS_BYTES, s, a);
-  return hipGetLastError();
-}
-template <int M, int H, int KIND, bool DC>
-hipError_t launch_power_out(int out, const ScnAvgArgs &a, uint32_t grid, hipStream_t s) {
-  switch (out) {
-    case OUT_PARTIAL: return launch_power<M, H, KIND, DC, OUT_PARTIAL>(a, grid, s);
-    case OUT_SPEC: return launch_power<M, H, KIND, DC, OUT_SPEC>(a, grid, s);
-    case OUT_HITS: return launch_power<M, H, KIND, DC, OUT_HITS>(a, grid, s);
-    default: return launch_power<M, H, KIND, DC, OUT_BOTH>(a, grid, s);
-  }
-}
 template <int M, int H>
-hipError_t launch_power_kind(int kind, bool dc, int out, const ScnAvgArgs &a, uint32_t grid, hipStream_t s) {
-  switch (kind) {
-    case SCN_K_BYTE_COMPLEX:
-      return dc ? launch_power_out<M, H, SCN_K_BYTE_COMPLEX, true>(out, a, grid, s) : launch_power_out<M, H, SCN_K_BYTE_COMPLEX, false>(out, a, grid, s);
-    case SCN_K_SHORT:
-      return dc ? launch_power_out<M, H, SCN_K_SHORT, true>(out, a, grid, s) : launch_power_out<M, H, SCN_K_SHORT, false>(out, a, grid, s);
-    case SCN_K_SHORT_COMPLEX:
-      return dc ? launch_power_out<M, H, SCN_K_SHORT_COMPLEX, true>(out, a, grid, s) : launch_power_out<M, H, SCN_K_SHORT_COMPLEX, false>(out, a, grid, s);
-    case SCN_K_FLOAT_COMPLEX: return launch_power_out<M, H, SCN_K_FLOAT_COMPLEX, false>(out, a, grid, s);  // (K1 ignores correct_dc for floats)
-    default: return hipErrorInvalidValue;
-  }
+hipError_t launch_power(const ScnAvgLaunch &l) {
+  typedef AvgGeo<M, H> G;
+  return scn_with_kind(l.kind, l.dc, [&](auto kind, auto dc) {
+    auto launch = [&](auto out) {
+      hipLaunchKernelGGL((scn_avg_power_kernel<M, H, decltype(kind)::value, decltype(dc)::value, decltype(out)::value>), dim3(l.grid), dim3(G::T),
+                         G::LDS_BYTES, l.s, l.a);
+      return hipGetLastError();
+    };
+    if (l.split) return launch(std::integral_constant<int, OUT_PARTIAL>{});
+    return scn_with_mode(l.hits, l.spec, [&](auto hits, auto spec) {
+      return launch(std::integral_constant<int, (decltype(hits)::value ? OUT_HITS : 0) | (decltype(spec)::value ? OUT_SPEC : 0)>{});
+    });
+  });
 }
 }  // namespace
 
-#define SCN_AVG_LAUNCH_ARGS int kind, bool dc, int out, const ScnAvgArgs &a, uint32_t grid, hipStream_t s
-hipError_t scn_avg_launch_1024(SCN_AVG_LAUNCH_ARGS);
-hipError_t scn_avg_launch_2048(SCN_AVG_LAUNCH_ARGS);
-hipError_t scn_avg_launch_4096(SCN_AVG_LAUNCH_ARGS);
-hipError_t scn_avg_launch_8192(SCN_AVG_LAUNCH_ARGS);
-#if SCN_AVG_IN_TU(0)
-hipError_t scn_avg_launch_1024(SCN_AVG_LAUNCH_ARGS) { return launch_power_kind<4, 1>(kind, dc, out, a, grid, s); }
+// one launcher per translation unit, as scn_launch_fft_unit (scn_kernels.hip): unit u holds M = 4, 8, 16 and 16 with H = 2
+template <int TU>
+hipError_t scn_launch_avg_unit(const ScnAvgLaunch &l);
+#if SCN_AVG_TU == -1
+template <int TU>
+hipError_t scn_launch_avg_unit(const ScnAvgLaunch &l) { return launch_power<(TU < 3 ? 4 << TU : 16), (TU < 3 ? 1 : 2)>(l); }
+#else
+template <>
+hipError_t scn_launch_avg_unit<SCN_AVG_TU>(const ScnAvgLaunch &l) { return launch_power<(SCN_AVG_TU < 3 ? 4 << SCN_AVG_TU : 16), (SCN_AVG_TU < 3 ? 1 : 2)>(l); }
 #endif
-#if SCN_AVG_IN_TU(1)
-hipError_t scn_avg_launch_2048(SCN_AVG_LAUNCH_ARGS) { return launch_power_kind<8, 1>(kind, dc, out, a, grid, s); }
-#endif
-#if SCN_AVG_IN_TU(2)
-hipError_t scn_avg_launch_4096(SCN_AVG_LAUNCH_ARGS) { return launch_power_kind<16, 1>(kind, dc, out, a, grid, s); }
-#endif
-#if SCN_AVG_IN_TU(3)
-hipError_t scn_avg_launch_8192(SCN_AVG_LAUNCH_ARGS) { return launch_power_kind<16, 2>(kind, dc, out, a, grid, s); }
 
+#if SCN_AVG_IN_TU(3)
 bool scn_avg_size_supported(uint32_t n) { return n == 1024 || n == 2048 || n == 4096 || n == 8192; }
 
 uint32_t scn_avg_parts(uint32_t n, uint32_t n_groups, uint32_t k, int num_cus) {
@@ -457,27 +449,21 @@ size_t scn_avg_partial_floats(uint32_t n, uint32_t max_groups, int num_cus) {
 hipError_t scn_launch_average(int kind, bool correct_dc, bool hits, bool spectrum, const ScnAvgArgs &a, int num_cus, hipStream_t s) {
   if (!a.n_groups) return hipSuccess;
   const bool split = a.parts > 1u;
-  const int out = split ? OUT_PARTIAL : hits && spectrum ? OUT_BOTH : hits ? OUT_HITS : OUT_SPEC;
   // items spread evenly: ceil(items / slots) items per workgroup, and the fewest workgroups that cover them at that rate (the
   // last ones may take one item fewer; at G = 1024, P = 1, 4096 points: 512 workgroups of two items, a third of the slots idle)
   const uint32_t items = a.n_groups * a.parts, slots = (uint32_t)num_cus * avg_wg_per_cu(a.n);
   const uint32_t per = (items + slots - 1u) / slots;
   const uint32_t grid = (items + per - 1u) / per;
-  hipError_t e;
-  switch (a.n) {
-    case 1024: e = scn_avg_launch_1024(kind, correct_dc, out, a, grid, s); break;
-    case 2048: e = scn_avg_launch_2048(kind, correct_dc, out, a, grid, s); break;
-    case 4096: e = scn_avg_launch_4096(kind, correct_dc, out, a, grid, s); break;
-    case 8192: e = scn_avg_launch_8192(kind, correct_dc, out, a, grid, s); break;
-    default: return hipErrorInvalidValue;
-  }
+  if (!scn_avg_size_supported(a.n)) return hipErrorInvalidValue;
+  static constexpr hipError_t (*units[4])(const ScnAvgLaunch &) = {scn_launch_avg_unit<0>, scn_launch_avg_unit<1>, scn_launch_avg_unit<2>, scn_launch_avg_unit<3>};
+  hipError_t e = units[__builtin_ctz(a.n) - 10](ScnAvgLaunch{kind, correct_dc, split, hits, spectrum, a, grid, s});
   if (e != hipSuccess || !split) return e;
   if (hits && (e = hipMemsetAsync(a.per_group_hits, 0, sizeof(uint32_t) * a.n_groups, s)) != hipSuccess) return e;
   const uint32_t waves = a.parts < 16u ? a.parts : 16u;
   const dim3 cgrid(a.n_groups * (a.n / 64u)), block(64u * waves);
-  if (hits && spectrum) hipLaunchKernelGGL((scn_avg_combine_kernel<true, true>), cgrid, block, 0, s, a);
-  else if (hits) hipLaunchKernelGGL((scn_avg_combine_kernel<true, false>), cgrid, block, 0, s, a);
-  else hipLaunchKernelGGL((scn_avg_combine_kernel<false, true>), cgrid, block, 0, s, a);
-  return hipGetLastError();
+  return scn_with_mode(hits, spectrum, [&](auto h, auto sp) {
+    hipLaunchKernelGGL((scn_avg_combine_kernel<decltype(h)::value, decltype(sp)::value>), cgrid, block, 0, s, a);
+    return hipGetLastError();
+  });
 }
 #endif

@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "scn_device.h"
+#include "scn_dispatch.h"
 
 #ifndef SCN_BIG_AUX_IN_POLICY
 #define SCN_BIG_AUX_IN_POLICY 2
@@ -33,58 +34,34 @@ constexpr int BIG_AUX_IN = SCN_BIG_AUX_IN_POLICY;
 constexpr uint32_t BN = 65536;
 constexpr uint32_t BP = 272;  // LDS row pitch (slots): 16 rows of 256 + 16, as in scn_welch.hip
 
+// how the column kernel fetches sample s + (n / 16) a; the decode is Wire<KIND>'s: conv(raw, dc_re, dc_im) leaves float(source - dc),
+// the scale rides in the window tap
 template <int KIND>
 struct BigRaw;
 template <>
-struct BigRaw<SCN_K_FLOAT_COMPLEX> {
-  static constexpr uint32_t kBytes = 8;
-  typedef v2f raw_t;
-  static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t s, uint32_t a, uint32_t n) {  // sample s + (n / 16) a
+struct BigRaw<SCN_K_FLOAT_COMPLEX> : Wire<SCN_K_FLOAT_COMPLEX> {
+  static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t s, uint32_t a, uint32_t n) {
     return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, s * 8u, a * (n / 2u), BIG_AUX_IN));
   }
-  static __device__ __forceinline__ cf conv(raw_t r, int, int) { return from_v2f(r); }
-  static __device__ __forceinline__ void ints(raw_t, int &re, int &im) { re = im = 0; }  // (no DC removal for float samples)
 };
 template <>
-struct BigRaw<SCN_K_SHORT_COMPLEX> {
-  static constexpr uint32_t kBytes = 4;
-  typedef int raw_t;
+struct BigRaw<SCN_K_SHORT_COMPLEX> : Wire<SCN_K_SHORT_COMPLEX> {
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t s, uint32_t a, uint32_t n) {
     return __builtin_amdgcn_raw_buffer_load_b32(r, s * 4u, a * (n / 4u), BIG_AUX_IN);
   }
-  // float(source) * onebymax with the scale folded into the window tap (utility.cpp:81-82; onebymax is +-2^-k: exact)
-  // (source - dc in int arithmetic with wrap-around, as the oracle's conv1)
-  static __device__ __forceinline__ void ints(raw_t r, int &re, int &im) { re = (int)(short)(r & 0xffff); im = r >> 16; }
-  static __device__ __forceinline__ cf conv(raw_t r, int dc_re, int dc_im) {
-    int re, im;
-    ints(r, re, im);
-    return cf{(float)(int)((uint32_t)re - (uint32_t)dc_re), (float)(int)((uint32_t)im - (uint32_t)dc_im)};
-  }
 };
 template <>
-struct BigRaw<SCN_K_SHORT> {  // planar: I[n] then Q[n]
-  static constexpr uint32_t kBytes = 4;
-  typedef int raw_t;
+struct BigRaw<SCN_K_SHORT> : Wire<SCN_K_SHORT> {  // planar: I[n] then Q[n]
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t s, uint32_t a, uint32_t n) {
     const int re = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, s * 2u, a * (n / 8u), BIG_AUX_IN);
     const int im = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, s * 2u, n * 2u + a * (n / 8u), BIG_AUX_IN);
     return (re & 0xffff) | (im << 16);
   }
-  static __device__ __forceinline__ void ints(raw_t r, int &re, int &im) { BigRaw<SCN_K_SHORT_COMPLEX>::ints(r, re, im); }
-  static __device__ __forceinline__ cf conv(raw_t r, int dc_re, int dc_im) { return BigRaw<SCN_K_SHORT_COMPLEX>::conv(r, dc_re, dc_im); }
 };
 template <>
-struct BigRaw<SCN_K_BYTE_COMPLEX> {
-  static constexpr uint32_t kBytes = 2;
-  typedef int raw_t;
+struct BigRaw<SCN_K_BYTE_COMPLEX> : Wire<SCN_K_BYTE_COMPLEX> {
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t s, uint32_t a, uint32_t n) {
     return (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, s * 2u, a * (n / 8u), BIG_AUX_IN);
-  }
-  static __device__ __forceinline__ void ints(raw_t r, int &re, int &im) { re = (int)(signed char)(r & 0xff); im = (int)(signed char)((r >> 8) & 0xff); }
-  static __device__ __forceinline__ cf conv(raw_t r, int dc_re, int dc_im) {
-    int re, im;
-    ints(r, re, im);
-    return cf{(float)(int)((uint32_t)re - (uint32_t)dc_re), (float)(int)((uint32_t)im - (uint32_t)dc_im)};
   }
 };
 }  // namespace
@@ -415,35 +392,17 @@ bool scn_big_size_supported(uint32_t n) { return n == BN || n == 32768u; }
 
 template <uint32_t N>
 static hipError_t launch_cols(int kind, bool dc, const ScnBigArgs &a, uint32_t grid, size_t lds, hipStream_t s) {
-  if (dc && kind != SCN_K_FLOAT_COMPLEX) {
-    hipError_t e = hipMemsetAsync(a.dc_sums, 0, sizeof(int) * 2 * a.n_buffers, s);
-    if (e != hipSuccess) return e;
-    const dim3 gd(4u * a.n_buffers);
-    switch (kind) {
-      case SCN_K_SHORT_COMPLEX:
-        hipLaunchKernelGGL((scn_big_dc_kernel<SCN_K_SHORT_COMPLEX, N>), gd, dim3(256), 0, s, a);
-        hipLaunchKernelGGL((scn_big_cols_kernel<SCN_K_SHORT_COMPLEX, N, true>), dim3(grid), dim3(256), lds, s, a);
-        break;
-      case SCN_K_SHORT:
-        hipLaunchKernelGGL((scn_big_dc_kernel<SCN_K_SHORT, N>), gd, dim3(256), 0, s, a);
-        hipLaunchKernelGGL((scn_big_cols_kernel<SCN_K_SHORT, N, true>), dim3(grid), dim3(256), lds, s, a);
-        break;
-      case SCN_K_BYTE_COMPLEX:
-        hipLaunchKernelGGL((scn_big_dc_kernel<SCN_K_BYTE_COMPLEX, N>), gd, dim3(256), 0, s, a);
-        hipLaunchKernelGGL((scn_big_cols_kernel<SCN_K_BYTE_COMPLEX, N, true>), dim3(grid), dim3(256), lds, s, a);
-        break;
-      default: return hipErrorInvalidValue;
+  return scn_with_kind(kind, dc, [&](auto k, auto d) {
+    constexpr int KIND = decltype(k)::value;
+    constexpr bool DC = decltype(d)::value;
+    if constexpr (DC) {
+      hipError_t e = hipMemsetAsync(a.dc_sums, 0, sizeof(int) * 2 * a.n_buffers, s);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((scn_big_dc_kernel<KIND, N>), dim3(4u * a.n_buffers), dim3(256), 0, s, a);
     }
+    hipLaunchKernelGGL((scn_big_cols_kernel<KIND, N, DC>), dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
-  }
-  switch (kind) {
-    case SCN_K_FLOAT_COMPLEX: hipLaunchKernelGGL((scn_big_cols_kernel<SCN_K_FLOAT_COMPLEX, N, false>), dim3(grid), dim3(256), lds, s, a); break;
-    case SCN_K_SHORT_COMPLEX: hipLaunchKernelGGL((scn_big_cols_kernel<SCN_K_SHORT_COMPLEX, N, false>), dim3(grid), dim3(256), lds, s, a); break;
-    case SCN_K_SHORT: hipLaunchKernelGGL((scn_big_cols_kernel<SCN_K_SHORT, N, false>), dim3(grid), dim3(256), lds, s, a); break;
-    case SCN_K_BYTE_COMPLEX: hipLaunchKernelGGL((scn_big_cols_kernel<SCN_K_BYTE_COMPLEX, N, false>), dim3(grid), dim3(256), lds, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  });
 }
 
 hipError_t scn_launch_big(uint32_t n, int kind, bool dc, bool hits, bool spec, const ScnBigArgs &a, int num_cus, hipStream_t s) {
@@ -460,17 +419,11 @@ hipError_t scn_launch_big(uint32_t n, int kind, bool dc, bool hits, bool spec, c
   if (G > a.n_buffers) G = a.n_buffers;
   e = n == BN ? launch_cols<BN>(kind, dc, a, ct * G, lds, s) : launch_cols<32768u>(kind, dc, a, ct * G, lds, s);
   if (e != hipSuccess) return e;
-  if (n == BN) {
-    const dim3 grid(16u * a.n_buffers);
-    if (hits && spec) hipLaunchKernelGGL((scn_big_rows_kernel<true, true>), grid, dim3(256), lds, s, a);
-    else if (hits) hipLaunchKernelGGL((scn_big_rows_kernel<true, false>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((scn_big_rows_kernel<false, true>), grid, dim3(256), lds, s, a);
-  } else {
-    const dim3 grid(8u * a.n_buffers);
-    const size_t lds32 = 32 * 152 * sizeof(v2f);  // 38 KiB: the exchange (the 128 x 32 float output tile fits inside)
-    if (hits && spec) hipLaunchKernelGGL((scn_big_rows32k_kernel<true, true>), grid, dim3(256), lds32, s, a);
-    else if (hits) hipLaunchKernelGGL((scn_big_rows32k_kernel<true, false>), grid, dim3(256), lds32, s, a);
-    else hipLaunchKernelGGL((scn_big_rows32k_kernel<false, true>), grid, dim3(256), lds32, s, a);
-  }
-  return hipGetLastError();
+  return scn_with_mode(hits, spec, [&](auto h, auto sp) {
+    constexpr bool HITS = decltype(h)::value, SPEC = decltype(sp)::value;
+    // 32768 points: 38 KiB, the exchange (the 128 x 32 float output tile fits inside)
+    if (n == BN) hipLaunchKernelGGL((scn_big_rows_kernel<HITS, SPEC>), dim3(16u * a.n_buffers), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((scn_big_rows32k_kernel<HITS, SPEC>), dim3(8u * a.n_buffers), dim3(256), 32 * 152 * sizeof(v2f), s, a);
+    return hipGetLastError();
+  });
 }

@@ -9,13 +9,7 @@
 typedef scn_v2f v2f;  // memory / LDS element (8 B)
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-// Register-resident complex value.  Deliberately two independent floats, not an
-// ext_vector: on gfx950 a v_pk_*_f32 costs the same 4 issue cycles as two scalar ops, and
-// hipcc's packed complex multiply is 3 packed ops + a move + wait states (~14 cycles)
-// against 8 for mul/mul/fma/fma, so scalar arithmetic is the faster form here.
-struct cf {
-  float x, y;
-};
+// (cf, the register-resident complex value, is scn_wire.h's: K1 returns it)
 __device__ __forceinline__ cf operator+(cf a, cf b) { return cf{a.x + b.x, a.y + b.y}; }
 __device__ __forceinline__ cf operator-(cf a, cf b) { return cf{a.x - b.x, a.y - b.y}; }
 __device__ __forceinline__ cf operator*(cf a, float s) { return cf{a.x * s, a.y * s}; }
@@ -440,21 +434,19 @@ __device__ __forceinline__ void scn_store_exact_db(const VEC &pw, const float (&
   }
 }
 
-// ---- K1: the wire formats (8 / 4 / 2 bytes per sample) --------------------------------------------------------------
+// ---- K1: how the fused kernels FETCH a sample (addressing, cache-policy immediate); what a sample is and how it decodes --
+// kBytes, raw_t, ints, conv -- is Wire<KIND>'s (scn_wire.h).  load: sample idx0 + t of a buffer of n; load2: the two consecutive
+// samples idx0 + 2t, idx0 + 2t + 1 in one load of twice the width (the wide 8192-point kernel's lane pairs)
 template <int KIND>
 struct RawLoader;
 
-// float I,Q interleaved: 8 B per sample
 template <>
-struct RawLoader<SCN_K_FLOAT_COMPLEX> {
-  static constexpr uint32_t kBufBytes(uint32_t n) { return 8u * n; }
-  typedef v2f raw_t;
+struct RawLoader<SCN_K_FLOAT_COMPLEX> : Wire<SCN_K_FLOAT_COMPLEX> {
   template <int AUX>
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t, uint32_t t, uint32_t idx0) {
     // (the builtin returns a GCC-style vector; bit_cast, never assign it to an ext_vector)
     return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, t * 8u, idx0 * 8u, AUX));
   }
-  // two consecutive samples idx0 + 2t, idx0 + 2t + 1 in one 16-byte load (the wide 8192-point kernel's lane pairs)
   template <int AUX>
   static __device__ __forceinline__ void load2(__amdgpu_buffer_rsrc_t r, uint32_t, uint32_t t, uint32_t idx0, raw_t &r0, raw_t &r1) {
     typedef float v4f_t __attribute__((ext_vector_type(4)));
@@ -462,15 +454,10 @@ struct RawLoader<SCN_K_FLOAT_COMPLEX> {
     r0 = v2f{v.x, v.y};
     r1 = v2f{v.z, v.w};
   }
-  static __device__ __forceinline__ void ints(raw_t, int &re, int &im) { re = im = 0; }
-  static __device__ __forceinline__ cf conv(raw_t r, int, int, float) { return from_v2f(r); }
 };
 
-// int16 I,Q interleaved: 4 B per sample
 template <>
-struct RawLoader<SCN_K_SHORT_COMPLEX> {
-  static constexpr uint32_t kBufBytes(uint32_t n) { return 4u * n; }
-  typedef int raw_t;
+struct RawLoader<SCN_K_SHORT_COMPLEX> : Wire<SCN_K_SHORT_COMPLEX> {
   template <int AUX>
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t, uint32_t t, uint32_t idx0) {
     return __builtin_amdgcn_raw_buffer_load_b32(r, t * 4u, idx0 * 4u, AUX);
@@ -482,24 +469,10 @@ struct RawLoader<SCN_K_SHORT_COMPLEX> {
     r0 = v.x;
     r1 = v.y;
   }
-  static __device__ __forceinline__ void ints(raw_t r, int &re, int &im) {
-    re = (int)(short)(r & 0xffff);
-    im = r >> 16;
-  }
-  static __device__ __forceinline__ cf conv(raw_t r, int dc_re, int dc_im, float scale) {
-    int re, im;
-    ints(r, re, im);
-    // float(source - dc) * onebymax, utility.cpp:81-82 (wrapping int arithmetic)
-    return cf{(float)(int)((uint32_t)re - (uint32_t)dc_re) * scale,
-              (float)(int)((uint32_t)im - (uint32_t)dc_im) * scale};
-  }
 };
 
-// int8 I,Q interleaved: 2 B per sample
 template <>
-struct RawLoader<SCN_K_BYTE_COMPLEX> {
-  static constexpr uint32_t kBufBytes(uint32_t n) { return 2u * n; }
-  typedef int raw_t;
+struct RawLoader<SCN_K_BYTE_COMPLEX> : Wire<SCN_K_BYTE_COMPLEX> {
   template <int AUX>
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t, uint32_t t, uint32_t idx0) {
     // (only bytes 0 and 1 of the register are ever read -- by the SDWA converts of conv() --, so the 16-bit load is taken as it
@@ -515,23 +488,11 @@ struct RawLoader<SCN_K_BYTE_COMPLEX> {
     r0 = (int)(v & 0xffffu);
     r1 = (int)(v >> 16);
   }
-  static __device__ __forceinline__ void ints(raw_t r, int &re, int &im) {
-    re = (int)(signed char)(r & 0xff);
-    im = (int)(signed char)((r >> 8) & 0xff);
-  }
-  static __device__ __forceinline__ cf conv(raw_t r, int dc_re, int dc_im, float scale) {
-    int re, im;
-    ints(r, re, im);
-    return cf{(float)(int)((uint32_t)re - (uint32_t)dc_re) * scale,
-              (float)(int)((uint32_t)im - (uint32_t)dc_im) * scale};
-  }
 };
 
-// int16 planar: I[n] then Q[n] per buffer; packed into the SHORT_COMPLEX register form
+// planar: I from the first half of the buffer, Q from the second
 template <>
-struct RawLoader<SCN_K_SHORT> {
-  static constexpr uint32_t kBufBytes(uint32_t n) { return 4u * n; }
-  typedef int raw_t;
+struct RawLoader<SCN_K_SHORT> : Wire<SCN_K_SHORT> {
   template <int AUX>
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t n, uint32_t t, uint32_t idx0) {
     int re = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, t * 2u, idx0 * 2u, AUX);
@@ -544,12 +505,6 @@ struct RawLoader<SCN_K_SHORT> {
     const uint32_t im = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, t * 4u, (n + idx0) * 2u, AUX);  // Q[2t], Q[2t+1]
     r0 = (int)((re & 0xffffu) | (im << 16));
     r1 = (int)((re >> 16) | (im & 0xffff0000u));
-  }
-  static __device__ __forceinline__ void ints(raw_t r, int &re, int &im) {
-    RawLoader<SCN_K_SHORT_COMPLEX>::ints(r, re, im);
-  }
-  static __device__ __forceinline__ cf conv(raw_t r, int dc_re, int dc_im, float scale) {
-    return RawLoader<SCN_K_SHORT_COMPLEX>::conv(r, dc_re, dc_im, scale);
   }
 };
 

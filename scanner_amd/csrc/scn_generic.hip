@@ -25,6 +25,7 @@
 #include <utility>
 
 #include "scn_device.h"
+#include "scn_dispatch.h"
 #include "scn_kernels.h"
 
 namespace {
@@ -35,61 +36,19 @@ namespace {
 // buffers: eight stages then round a strong tone's partial sums to float eight times (the fused kernels: three), and a
 // buffer with peak/mean power 8e3 at 32768 points read 1.0e-5 .. 1.2e-5 on bins near the mean -- AT the parity bar.  This
 // is the correctness path for unusual sizes; it is bound by its HBM passes, and it pays for the wider ones.
+// sample i of an n-sample buffer in Wire<KIND>'s register form, from the plain pointer
 template <int KIND>
-struct GenRaw;
-template <>
-struct GenRaw<SCN_K_FLOAT_COMPLEX> {
-  static constexpr uint32_t kBytes = 8;
-  static __device__ __forceinline__ void ints(const void *, uint32_t, uint32_t, int &re, int &im) { re = im = 0; }
-  static __device__ __forceinline__ cf conv(const void *buf, uint32_t, uint32_t i, int, int, float) {
-    return from_v2f(static_cast<const v2f *>(buf)[i]);
-  }
-};
-template <>
-struct GenRaw<SCN_K_SHORT_COMPLEX> {
-  static constexpr uint32_t kBytes = 4;
-  static __device__ __forceinline__ void ints(const void *buf, uint32_t, uint32_t i, int &re, int &im) {
-    const int r = static_cast<const int *>(buf)[i];
-    re = (int)(short)(r & 0xffff);
-    im = r >> 16;
-  }
-  static __device__ __forceinline__ cf conv(const void *buf, uint32_t n, uint32_t i, int dc_re, int dc_im, float scale) {
-    int re, im;
-    ints(buf, n, i, re, im);
-    // float(source - dc) * onebymax, utility.cpp:81-82 (wrapping int arithmetic)
-    return cf{(float)(int)((uint32_t)re - (uint32_t)dc_re) * scale, (float)(int)((uint32_t)im - (uint32_t)dc_im) * scale};
-  }
-};
-template <>
-struct GenRaw<SCN_K_SHORT> {  // planar: I[n] then Q[n]
-  static constexpr uint32_t kBytes = 4;
-  static __device__ __forceinline__ void ints(const void *buf, uint32_t n, uint32_t i, int &re, int &im) {
-    re = static_cast<const short *>(buf)[i];
-    im = static_cast<const short *>(buf)[n + i];
-  }
-  static __device__ __forceinline__ cf conv(const void *buf, uint32_t n, uint32_t i, int dc_re, int dc_im, float scale) {
-    int re, im;
-    ints(buf, n, i, re, im);
-    return cf{(float)(int)((uint32_t)re - (uint32_t)dc_re) * scale, (float)(int)((uint32_t)im - (uint32_t)dc_im) * scale};
-  }
-};
-template <>
-struct GenRaw<SCN_K_BYTE_COMPLEX> {
-  static constexpr uint32_t kBytes = 2;
-  static __device__ __forceinline__ void ints(const void *buf, uint32_t, uint32_t i, int &re, int &im) {
-    re = static_cast<const signed char *>(buf)[2 * i];
-    im = static_cast<const signed char *>(buf)[2 * i + 1];
-  }
-  static __device__ __forceinline__ cf conv(const void *buf, uint32_t n, uint32_t i, int dc_re, int dc_im, float scale) {
-    int re, im;
-    ints(buf, n, i, re, im);
-    return cf{(float)(int)((uint32_t)re - (uint32_t)dc_re) * scale, (float)(int)((uint32_t)im - (uint32_t)dc_im) * scale};
-  }
-};
+__device__ __forceinline__ typename Wire<KIND>::raw_t gen_fetch(const void *buf, uint32_t n, uint32_t i) {
+  if constexpr (KIND == SCN_K_FLOAT_COMPLEX) return static_cast<const v2f *>(buf)[i];
+  else if constexpr (KIND == SCN_K_SHORT_COMPLEX) return static_cast<const int *>(buf)[i];
+  else if constexpr (KIND == SCN_K_BYTE_COMPLEX)  // (two byte loads: the load kernel's code as it was, profiles/wire_once.md)
+    return (int)static_cast<const unsigned char *>(buf)[2 * i] | ((int)static_cast<const unsigned char *>(buf)[2 * i + 1] << 8);
+  else return (int)static_cast<const unsigned short *>(buf)[i] | ((int)static_cast<const unsigned short *>(buf)[n + i] << 16);  // planar: I[n] then Q[n]
+}
 
 template <int KIND, bool DC>
 __global__ __launch_bounds__(256) void scn_gen_load_kernel(ScnGenericArgs a) {
-  typedef GenRaw<KIND> L;
+  typedef Wire<KIND> L;
   __shared__ int s_sum[8];
   const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
   const uint32_t n = a.n;
@@ -100,7 +59,7 @@ __global__ __launch_bounds__(256) void scn_gen_load_kernel(ScnGenericArgs a) {
       int sr = 0, si = 0;
       for (uint32_t i = t; i < n; i += 256u) {
         int re, im;
-        L::ints(buf, n, i, re, im);
+        L::ints(gen_fetch<KIND>(buf, n, i), re, im);
         sr += re;
         si += im;
       }
@@ -122,7 +81,7 @@ __global__ __launch_bounds__(256) void scn_gen_load_kernel(ScnGenericArgs a) {
     for (uint32_t i = t; i < a.m; i += 256u) {
       cd v = cd{0.0, 0.0};
       if (i < n) {
-        const cf x = L::conv(buf, n, i, dc_re, dc_im, 1.0f) * (a.window[i] * a.scale);
+        const cf x = L::conv(gen_fetch<KIND>(buf, n, i), dc_re, dc_im) * (a.window[i] * a.scale);
         // (the written-out FMA form: left to the compiler, the contraction of x w = (x.x w.x - x.y w.y, ...) came out differently
         //  in the int16 instantiation than in the others, and a constant buffer's residue bins differed between wire formats)
         const scn_v2d c = static_cast<const scn_v2d *>(a.chirp)[i];
@@ -216,13 +175,6 @@ __global__ __launch_bounds__(256) void scn_gen_finish_kernel(ScnGenericArgs a, c
   }
 }
 
-template <int KIND>
-hipError_t launch_load(bool dc, const ScnGenericArgs &a, int grid, hipStream_t s) {
-  if (dc) hipLaunchKernelGGL((scn_gen_load_kernel<KIND, true>), dim3(grid), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((scn_gen_load_kernel<KIND, false>), dim3(grid), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
 }  // namespace
 
 bool scn_bluestein_size_supported(uint32_t n) { return n >= 16u && n < 65536u && (n & (n - 1u)) != 0u; }  // transform length <= 131072
@@ -236,13 +188,10 @@ hipError_t scn_launch_generic(int kind, bool dc, bool hits, const ScnGenericArgs
   }
   const int resident = num_cus * 8;
   const int load_grid = (int)((uint32_t)resident < a.n_buffers ? (uint32_t)resident : a.n_buffers);
-  switch (kind) {
-    case SCN_K_FLOAT_COMPLEX: e = launch_load<SCN_K_FLOAT_COMPLEX>(false, a, load_grid, s); break;
-    case SCN_K_SHORT_COMPLEX: e = launch_load<SCN_K_SHORT_COMPLEX>(dc, a, load_grid, s); break;
-    case SCN_K_SHORT: e = launch_load<SCN_K_SHORT>(dc, a, load_grid, s); break;
-    case SCN_K_BYTE_COMPLEX: e = launch_load<SCN_K_BYTE_COMPLEX>(dc, a, load_grid, s); break;
-    default: return hipErrorInvalidValue;
-  }
+  e = scn_with_kind(kind, dc, [&](auto k, auto d) {
+    hipLaunchKernelGGL((scn_gen_load_kernel<decltype(k)::value, decltype(d)::value>), dim3(load_grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
   if (e != hipSuccess) return e;
   auto blocks_for = [&](size_t items) {
     size_t b = (items + 255u) / 256u;

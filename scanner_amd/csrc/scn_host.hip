@@ -3,6 +3,8 @@
 // unit with g++ under the sanitizers); the .hip suffix only puts it through the same compiler as the rest of the library.
 #include "scn_host.h"
 
+#include "scn_wire.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -22,15 +24,7 @@ int scn_fail(int status, const char *fmt, ...) {
   return status;
 }
 
-size_t bytes_per_sample(uint32_t kind) {
-  switch (kind) {
-    case SCN_KIND_BYTE_COMPLEX: return 2;
-    case SCN_KIND_SHORT:
-    case SCN_KIND_SHORT_COMPLEX: return 4;
-    case SCN_KIND_FLOAT_COMPLEX: return 8;
-    default: return 0;
-  }
-}
+size_t bytes_per_sample(uint32_t kind) { return scn_wire_bytes(kind); }
 
 // `int16_t max = 1 << (enob - 1); float onebymax = float(1.0/max);` (utility.cpp:64-65,
 // :16-17) and the int8_t flavour (utility.cpp:40-41), including the narrowing wrap that

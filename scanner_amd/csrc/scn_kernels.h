@@ -1,19 +1,14 @@
 // scn_kernels.h -- internal interface between the C-ABI layer (scn_plan.hip, scn_submit.hip,
 // scn_collect.hip, scn_welch_plan.hip) and the
-// kernels (scn_kernels.hip).  Not installed; the public surface is include/scanner_hip.h.
+// kernel files (scn_kernels.hip, scn_mixed.hip, scn_average.hip, scn_big.hip, scn_generic.hip, scn_welch.hip, ...): argument structs and
+// launchers.  K1's wire formats are scn_wire.h's (Wire<KIND>).  Not installed; the public surface is include/scanner_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "scn_mask.h"  // scn_bin_evaluated: K5's mask, shared with the host arithmetic
+#include "scn_wire.h"  // SCN_K_*, scn_v2f, Wire<KIND>: K1's wire formats
 
-// same numbering as messageQueue.h:31-37 / SCN_KIND_*
-#define SCN_K_BYTE_COMPLEX 1
-#define SCN_K_SHORT 2
-#define SCN_K_SHORT_COMPLEX 3
-#define SCN_K_FLOAT_COMPLEX 4
-
-typedef float scn_v2f __attribute__((ext_vector_type(2)));
 typedef double double2_scn __attribute__((ext_vector_type(2)));
 
 // A hit as the FFT kernel records it: slot `pos` of its buffer's region, in arbitrary order.  The compaction
@@ -240,6 +235,15 @@ static inline float scn_hit_prefilter(float threshold) {
   return f;
 }
 bool scn_fft_size_supported(uint32_t n);
+// a fused launch on its way from scn_launch_fft / scn_launch_mixed to the translation unit that holds the size's kernels
+struct ScnFftLaunch {
+  int kind;
+  bool dc, hits, spec;
+  const ScnFftArgs &args;
+  int num_cus;
+  hipStream_t stream;
+  hipEvent_t stop;
+};
 void scn_tw1_layout(uint32_t n, uint32_t *rows, uint32_t *threads);  // shape of ScnFftArgs::tw1_table for a fused size
 
 // The fused kernels for the sizes 2^a 3^b 5^c that are not powers of two (scn_mixed.hip, scn_mixed_plans.h): same arguments, same

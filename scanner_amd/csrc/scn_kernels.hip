@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "scn_device.h"
+#include "scn_dispatch.h"
 #include "scn_kernels.h"
 
 // Build-time split: every kernel here is a template, compiled where a launcher instantiates it.  scanner_amd/build.py compiles
@@ -39,8 +40,8 @@
 #define SCN_IN_TU(x) (SCN_TU == -1 || SCN_TU == (x))
 #define SCN_TU_COUNT 8  // 0: 16 / 32 points, 1: 64 / 128, 2: 256 / 512, 3: 1024 / 2048, 4: 4096, 5: 8192, 6: 16384, 7: everything that is not a fused FFT kernel
 
-// (RawLoader<KIND>, the wire-format loaders of K1, and the cache policy of the two streams live in scn_device.h: the mixed-radix
-// kernels of scn_mixed.hip use them too)
+// (K1: a sample's decode is Wire<KIND>'s, scn_wire.h; RawLoader<KIND>, how the fused kernels fetch one, and the cache policy of
+// the two streams live in scn_device.h: the mixed-radix kernels of scn_mixed.hip use them too)
 
 // ------------------------------------------------------------------------------------
 // Fused kernel for N = 256*M points, M in {4, 8, 16} (N = 1024 / 2048 / 4096).
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(16 * M, Geo<M>::WAVES_PER_SIMD) void scn_fft_kernel
   // ~31 table loads below instead of following them
   typename L::raw_t raw[16];
   if (blockIdx.x < args.n_buffers) {
-    __amdgpu_buffer_rsrc_t r0 = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)blockIdx.x * L::kBufBytes(N), L::kBufBytes(N));
+    __amdgpu_buffer_rsrc_t r0 = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)blockIdx.x * L::kBytes * N, L::kBytes * N);
 #pragma unroll
     for (int a = 0; a < 16; a++) raw[a] = L::template load<AUX_LD>(r0, N, t, T * a);
   }
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(16 * M, Geo<M>::WAVES_PER_SIMD) void scn_fft_kernel
     // zeros without touching memory), so every load sits in the same basic block as the butterflies and
     // can be issued between them.
     const __amdgpu_buffer_rsrc_t rn =
-        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)(more ? nxt : buf) * L::kBufBytes(N), more ? L::kBufBytes(N) : 0u);
+        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)(more ? nxt : buf) * (L::kBytes * N), more ? L::kBytes * N : 0u);
     auto prefetch = [&](int a_lo, int a_hi) {
 #pragma unroll
       for (int a = 0; a < 16; a++)
@@ -419,7 +420,7 @@ __global__ __launch_bounds__(256, 3) void scn_fft_small_kernel(ScnFftArgs args) 
   v2f *lds = reinterpret_cast<v2f *>(smem_raw) + slot * G::EXCH;                     // this buffer's exchange area
   v2f *lds_tw2 = reinterpret_cast<v2f *>(smem_raw) + SLOTS * G::EXCH;                // [16][M], shared by the slots
   const uint32_t p2 = t / M, c2 = t % M;
-  const uint32_t buf_bytes = L::kBufBytes(N);
+  const uint32_t buf_bytes = L::kBytes * N;
 
   // the iteration's SLOTS consecutive buffers under one descriptor (zero records past the end of the batch)
   auto in_rsrc = [&](uint32_t first) {
@@ -641,7 +642,7 @@ __global__ __launch_bounds__(256, 3) void scn_fft_tiny_kernel(ScnFftArgs args) {
   const uint32_t tid = threadIdx.x, t = tid % R, slot = tid / R;
   v2f *lds = reinterpret_cast<v2f *>(smem_raw) + slot * G::EXCH;  // this buffer's exchange area
   float *tile_out = reinterpret_cast<float *>(smem_raw);          // the dB tile [slot][PITCH]
-  const uint32_t buf_bytes = L::kBufBytes(N);
+  const uint32_t buf_bytes = L::kBytes * N;
 
   auto in_rsrc = [&](uint32_t first) {  // the iteration's chunk: SLOTS consecutive buffers (zero records past the end of the batch)
     const bool ok = first < args.n_buffers;
@@ -829,7 +830,7 @@ __device__ __forceinline__ void scn_fft8k_body(const ScnFftArgs &args) {
       if (a >= a_lo && a < a_hi) L::template load2<AUX_LD>(r, N, t, TV * a, raw[2 * a], raw[2 * a + 1]);
   };
   if (blockIdx.x < args.n_buffers) {
-    __amdgpu_buffer_rsrc_t r0 = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)blockIdx.x * L::kBufBytes(N), L::kBufBytes(N));
+    __amdgpu_buffer_rsrc_t r0 = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)blockIdx.x * L::kBytes * N, L::kBytes * N);
     load_group(r0, 0, 16);
   }
   // persistent constants: pass-1 twiddles of both virtual threads (table rows of TV), window taps
@@ -917,7 +918,7 @@ __device__ __forceinline__ void scn_fft8k_body(const ScnFftArgs &args) {
     if (DYN && t == 0 && more) taken = wq_take();
     // next buffer of this workgroup, branch-free (zero records past the end), in three groups
     const __amdgpu_buffer_rsrc_t rn =
-        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)(more ? nxt : buf) * L::kBufBytes(N), more ? L::kBufBytes(N) : 0u);
+        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)(more ? nxt : buf) * (L::kBytes * N), more ? L::kBytes * N : 0u);
     load_group(rn, 0, 6);
 
     // ---- pass 1: virtual threads tau0 and tau0 + 1 ----
@@ -1095,7 +1096,7 @@ __device__ __forceinline__ void scn_fft16k2_body(const ScnFftArgs &args) {
   };
   if (blockIdx.x < args.n_buffers) {
     __amdgpu_buffer_rsrc_t r0 =
-        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)blockIdx.x * L::kBufBytes(N), L::kBufBytes(N));
+        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)blockIdx.x * L::kBytes * N, L::kBytes * N);
     load_group(r0, 0, PFN);
   }
   // persistent constants: W_N^(t p) (table rows of 512, scn_tw1_layout), window taps.  Only p = 1 .. 16 are kept and
@@ -1137,8 +1138,8 @@ __device__ __forceinline__ void scn_fft16k2_body(const ScnFftArgs &args) {
     const uint32_t nxt = buf + gridDim.x;
     const bool more = nxt < args.n_buffers;
     if (PFN < 32) {  // the part of this buffer that was not prefetched
-      const __amdgpu_buffer_rsrc_t rc = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)buf * L::kBufBytes(N),
-                                                  L::kBufBytes(N));
+      const __amdgpu_buffer_rsrc_t rc = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)buf * (L::kBytes * N),
+                                                  L::kBytes * N);
       load_group(rc, PFN, 32);
     }
     // ---- K1 + K2 ----
@@ -1176,8 +1177,8 @@ __device__ __forceinline__ void scn_fft16k2_body(const ScnFftArgs &args) {
     }
     // next buffer of this workgroup, branch-free (zero records past the end), in three groups
     const __amdgpu_buffer_rsrc_t rn =
-        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)(more ? nxt : buf) * L::kBufBytes(N),
-                  more ? L::kBufBytes(N) : 0u);
+        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)(more ? nxt : buf) * (L::kBytes * N),
+                  more ? L::kBytes * N : 0u);
     load_group(rn, 0, PF0);
 
     // ---- pass 1: 32-point DFT over a: E, O = DFT16 of the even / odd samples, A[p'] = E + W_32^p' O, A[p' + 16] = E - W_32^p' O ----
@@ -1332,7 +1333,7 @@ __global__ __launch_bounds__(256) void scn_time_domain_kernel(ScnTdArgs args) {
   const uint32_t N = args.n;
   for (uint32_t buf = blockIdx.x; buf < args.n_buffers; buf += gridDim.x) {
     __amdgpu_buffer_rsrc_t rin =
-        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)buf * L::kBufBytes(N), L::kBufBytes(N));
+        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)buf * (L::kBytes * N), L::kBytes * N);
     int dc_re = 0, dc_im = 0;
     if (DC) {
       int sr = 0, si = 0;
@@ -1390,7 +1391,7 @@ __global__ __launch_bounds__(256) void scn_time_domain_kernel(ScnTdArgs args) {
 // for float / int16 / int8), four loads in flight per lane, wave-level reductions only -- no LDS, no barriers.  The
 // per-sample form above (one workgroup per buffer, one sample per lane per load) left a pure streaming reduction at
 // 46-51 us per 33.5 M int16 samples and 77-93 us at 1024 points; this is the product path whenever N is a multiple
-// of 8 (every supported size).  Same arithmetic, sample by sample, through RawLoader<KIND>::ints / conv.
+// of 8 (every supported size).  Same arithmetic, sample by sample, through Wire<KIND>::ints / conv.
 template <int KIND, bool DC>
 __global__ __launch_bounds__(256) void scn_time_domain_wave_kernel(ScnTdArgs args) {
   typedef RawLoader<KIND> L;
@@ -1401,7 +1402,7 @@ __global__ __launch_bounds__(256) void scn_time_domain_wave_kernel(ScnTdArgs arg
   //  sits in a one-trip waterfall loop)
   const uint32_t gw = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nw = gridDim.x * 4u;
   const uint32_t N = args.n;
-  const uint32_t bytes = L::kBufBytes(N);
+  const uint32_t bytes = L::kBytes * N;
   const uint32_t stream_bytes = PLANAR ? 2u * N : bytes;  // planar: the I block, then the Q block
   const uint32_t chunks = stream_bytes / 16u;
   for (uint32_t buf = gw; buf < args.n_buffers; buf += nw) {
@@ -1481,31 +1482,17 @@ __global__ __launch_bounds__(256) void scn_time_domain_wave_kernel(ScnTdArgs arg
 #if SCN_IN_TU(7)
 hipError_t scn_launch_time_domain(int kind, bool dc, const ScnTdArgs &a, int num_cus, hipStream_t s) {
   if (a.n_buffers == 0) return hipSuccess;
-  void (*k)(ScnTdArgs) = nullptr;
-  switch (kind) {
-    case SCN_K_FLOAT_COMPLEX: k = scn_time_domain_kernel<SCN_K_FLOAT_COMPLEX, false>; break;
-    case SCN_K_SHORT_COMPLEX: k = dc ? scn_time_domain_kernel<SCN_K_SHORT_COMPLEX, true> : scn_time_domain_kernel<SCN_K_SHORT_COMPLEX, false>; break;
-    case SCN_K_SHORT: k = dc ? scn_time_domain_kernel<SCN_K_SHORT, true> : scn_time_domain_kernel<SCN_K_SHORT, false>; break;
-    case SCN_K_BYTE_COMPLEX: k = dc ? scn_time_domain_kernel<SCN_K_BYTE_COMPLEX, true> : scn_time_domain_kernel<SCN_K_BYTE_COMPLEX, false>; break;
-    default: return hipErrorInvalidValue;
-  }
-  if (a.n % 8u == 0) {  // one wave per buffer, 16-byte loads
-    switch (kind) {
-      case SCN_K_FLOAT_COMPLEX: k = scn_time_domain_wave_kernel<SCN_K_FLOAT_COMPLEX, false>; break;
-      case SCN_K_SHORT_COMPLEX: k = dc ? scn_time_domain_wave_kernel<SCN_K_SHORT_COMPLEX, true> : scn_time_domain_wave_kernel<SCN_K_SHORT_COMPLEX, false>; break;
-      case SCN_K_SHORT: k = dc ? scn_time_domain_wave_kernel<SCN_K_SHORT, true> : scn_time_domain_wave_kernel<SCN_K_SHORT, false>; break;
-      default: k = dc ? scn_time_domain_wave_kernel<SCN_K_BYTE_COMPLEX, true> : scn_time_domain_wave_kernel<SCN_K_BYTE_COMPLEX, false>; break;
-    }
-    uint32_t blocks = (a.n_buffers + 3u) / 4u;  // four waves (buffers) per block
-    const uint32_t resident = (uint32_t)num_cus * 8u;
-    if (blocks > resident) blocks = resident;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, s, a);
+  const bool waves = a.n % 8u == 0;  // one wave per buffer, 16-byte loads: four waves (buffers) per block
+  uint32_t grid = waves ? (a.n_buffers + 3u) / 4u : a.n_buffers;
+  const uint32_t resident = (uint32_t)num_cus * 8u;
+  if (grid > resident) grid = resident;
+  return scn_with_kind(kind, dc, [&](auto k, auto d) {
+    constexpr int KIND = decltype(k)::value;
+    constexpr bool DC = decltype(d)::value;
+    if (waves) hipLaunchKernelGGL((scn_time_domain_wave_kernel<KIND, DC>), dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((scn_time_domain_kernel<KIND, DC>), dim3(grid), dim3(256), 0, s, a);
     return hipGetLastError();
-  }
-  int grid = num_cus * 8;
-  if ((uint32_t)grid > a.n_buffers) grid = (int)a.n_buffers;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, s, a);
-  return hipGetLastError();
+  });
 }
 #endif  // SCN_IN_TU(7)
 
@@ -1520,7 +1507,7 @@ __global__ __launch_bounds__(256) void scn_convert_kernel(const void *raw, scn_v
   __shared__ int s_sum[8];
   const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
   for (uint32_t buf = blockIdx.x; buf < n_buffers; buf += gridDim.x) {
-    __amdgpu_buffer_rsrc_t rin = make_rsrc(reinterpret_cast<const char *>(raw) + (size_t)buf * L::kBufBytes(n), L::kBufBytes(n));
+    __amdgpu_buffer_rsrc_t rin = make_rsrc(reinterpret_cast<const char *>(raw) + (size_t)buf * (L::kBytes * n), L::kBytes * n);
     int dc_re = 0, dc_im = 0;
     if (DC) {
       int sr = 0, si = 0;
@@ -1550,16 +1537,11 @@ __global__ __launch_bounds__(256) void scn_convert_kernel(const void *raw, scn_v
 hipError_t scn_launch_convert(int kind, bool dc, const void *raw, scn_v2f *out, uint32_t n, uint32_t n_buffers, float scale,
                               hipStream_t s) {
   if (n_buffers == 0) return hipSuccess;
-  void (*k)(const void *, scn_v2f *, uint32_t, uint32_t, float) = nullptr;
-  switch (kind) {
-    case SCN_K_FLOAT_COMPLEX: k = scn_convert_kernel<SCN_K_FLOAT_COMPLEX, false>; break;
-    case SCN_K_SHORT_COMPLEX: k = dc ? scn_convert_kernel<SCN_K_SHORT_COMPLEX, true> : scn_convert_kernel<SCN_K_SHORT_COMPLEX, false>; break;
-    case SCN_K_SHORT: k = dc ? scn_convert_kernel<SCN_K_SHORT, true> : scn_convert_kernel<SCN_K_SHORT, false>; break;
-    case SCN_K_BYTE_COMPLEX: k = dc ? scn_convert_kernel<SCN_K_BYTE_COMPLEX, true> : scn_convert_kernel<SCN_K_BYTE_COMPLEX, false>; break;
-    default: return hipErrorInvalidValue;
-  }
-  hipLaunchKernelGGL(k, dim3(n_buffers < 2048 ? n_buffers : 2048), dim3(256), 0, s, raw, out, n, n_buffers, scale);
-  return hipGetLastError();
+  return scn_with_kind(kind, dc, [&](auto k, auto d) {
+    hipLaunchKernelGGL((scn_convert_kernel<decltype(k)::value, decltype(d)::value>), dim3(n_buffers < 2048 ? n_buffers : 2048), dim3(256), 0, s, raw, out,
+                       n, n_buffers, scale);
+    return hipGetLastError();
+  });
 }
 #endif  // SCN_IN_TU(7)
 
@@ -1575,140 +1557,88 @@ static hipError_t launch_with_stop(K k, int grid, uint32_t threads, uint32_t lds
   return hipGetLastError();
 }
 
-// Output mode of a launch: which of the three kernels of a (size, wire format, DC) combination runs
-//   hits && spec: spectrum + hits;   !hits: spectrum only;   hits && !spec: hits only (no stores, no per-bin logarithm)
-template <template <bool, bool, bool> class K>
-static void (*pick_mode(bool dc, bool hits, bool spec))(ScnFftArgs) {
-  if (!hits) return dc ? K<true, false, true>::fn : K<false, false, true>::fn;
-  if (spec) return dc ? K<true, true, true>::fn : K<false, true, true>::fn;
-  return dc ? K<true, true, false>::fn : K<false, true, false>::fn;
-}
-// the kernel families: FAMILY<KIND>::T<DC, HITS, SPEC>::fn, with the family's geometry (threads, LDS, workgroups per CU,
+// the kernel families: FAMILY::kernel<KIND, DC, HITS, SPEC>, with the family's geometry (threads, LDS, workgroups per CU,
 // buffers per workgroup iteration)
 template <int M>
 struct NarrowFamily {
   typedef Geo<M> G;
   static constexpr uint32_t THREADS = G::T, SLOTS = 1;
-  template <int KIND>
-  struct K {
-    template <bool DC, bool HITS, bool SPEC>
-    struct T {
-      static constexpr void (*fn)(ScnFftArgs) = scn_fft_kernel<M, KIND, DC, HITS, SPEC>;
-    };
-  };
+  template <int KIND, bool DC, bool HITS, bool SPEC>
+  static constexpr void (*kernel)(ScnFftArgs) = scn_fft_kernel<M, KIND, DC, HITS, SPEC>;
 };
 template <int M>
 struct SmallFamily {
   typedef GeoSmall<M> G;
   static constexpr uint32_t THREADS = 256, SLOTS = G::SLOTS;
-  template <int KIND>
-  struct K {
-    template <bool DC, bool HITS, bool SPEC>
-    struct T {
-      static constexpr void (*fn)(ScnFftArgs) = scn_fft_small_kernel<M, KIND, DC, HITS, SPEC>;
-    };
-  };
+  template <int KIND, bool DC, bool HITS, bool SPEC>
+  static constexpr void (*kernel)(ScnFftArgs) = scn_fft_small_kernel<M, KIND, DC, HITS, SPEC>;
 };
 template <int R>
 struct TinyFamily {
   typedef GeoTiny<R> G;
   static constexpr uint32_t THREADS = 256, SLOTS = G::SLOTS;
-  template <int KIND>
-  struct K {
-    template <bool DC, bool HITS, bool SPEC>
-    struct T {
-      static constexpr void (*fn)(ScnFftArgs) = scn_fft_tiny_kernel<R, KIND, DC, HITS, SPEC>;
-    };
-  };
+  template <int KIND, bool DC, bool HITS, bool SPEC>
+  static constexpr void (*kernel)(ScnFftArgs) = scn_fft_tiny_kernel<R, KIND, DC, HITS, SPEC>;
 };
 struct Family8k {
   typedef Geo8k G;
   static constexpr uint32_t THREADS = G::T, SLOTS = 1;
-  template <int KIND>
-  struct K {
-    template <bool DC, bool HITS, bool SPEC>
-    struct T {
-      static constexpr void (*fn)(ScnFftArgs) = scn_fft8k_kernel<KIND, DC, HITS, SPEC>;
-    };
-  };
+  template <int KIND, bool DC, bool HITS, bool SPEC>
+  static constexpr void (*kernel)(ScnFftArgs) = scn_fft8k_kernel<KIND, DC, HITS, SPEC>;
 };
 struct Family16k {
   typedef Geo16k2 G;
   static constexpr uint32_t THREADS = G::T, SLOTS = 1;
-  template <int KIND>
-  struct K {
-    template <bool DC, bool HITS, bool SPEC>
-    struct T {
-      static constexpr void (*fn)(ScnFftArgs) = scn_fft16k2_kernel<KIND, DC, HITS, SPEC>;
-    };
-  };
+  template <int KIND, bool DC, bool HITS, bool SPEC>
+  static constexpr void (*kernel)(ScnFftArgs) = scn_fft16k2_kernel<KIND, DC, HITS, SPEC>;
 };
 
-template <class F, int KIND>
-static hipError_t launch_kind(const ScnFftArgs &a, bool dc, bool hits, bool spec, int num_cus, hipStream_t s, hipEvent_t stop) {
+template <class F>
+static hipError_t launch_kernel(void (*k)(ScnFftArgs), const ScnFftLaunch &l) {
   typedef typename F::G G;
-  void (*k)(ScnFftArgs) = pick_mode<F::template K<KIND>::template T>(dc, hits, spec);
   if (G::LDS_BYTES > 65536u) {
     // > 64 KiB of dynamic LDS needs the opt-in; it is per function AND per device, and a process may
     // drive several GPUs (one plan per consumer thread), so it is simply set on every launch
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
     if (e != hipSuccess) return e;
   }
-  const uint32_t groups = (a.n_buffers + F::SLOTS - 1u) / F::SLOTS;
-  int grid = num_cus * (int)G::WG_PER_CU;  // one resident wave of persistent workgroups
+  const uint32_t groups = (l.args.n_buffers + F::SLOTS - 1u) / F::SLOTS;
+  int grid = l.num_cus * (int)G::WG_PER_CU;  // one resident wave of persistent workgroups
   if ((uint32_t)grid > groups) grid = (int)groups;
-  return launch_with_stop(k, grid, F::THREADS, G::LDS_BYTES, s, stop, a);
+  return launch_with_stop(k, grid, F::THREADS, G::LDS_BYTES, l.stream, l.stop, l.args);
 }
 
+// which of the kernels of a family runs: wire format, DC removal, output mode
 template <class F>
-static hipError_t launch_family(int kind, bool dc, bool hits, bool spec, const ScnFftArgs &args, int num_cus, hipStream_t stream, hipEvent_t stop) {
-  switch (kind) {
-    case SCN_K_FLOAT_COMPLEX: return launch_kind<F, SCN_K_FLOAT_COMPLEX>(args, false, hits, spec, num_cus, stream, stop);
-    case SCN_K_SHORT_COMPLEX: return launch_kind<F, SCN_K_SHORT_COMPLEX>(args, dc, hits, spec, num_cus, stream, stop);
-    case SCN_K_SHORT: return launch_kind<F, SCN_K_SHORT>(args, dc, hits, spec, num_cus, stream, stop);
-    case SCN_K_BYTE_COMPLEX: return launch_kind<F, SCN_K_BYTE_COMPLEX>(args, dc, hits, spec, num_cus, stream, stop);
-    default: return hipErrorInvalidValue;
-  }
+static hipError_t launch_family(const ScnFftLaunch &l) {
+  return scn_with_kind(l.kind, l.dc, [&](auto kind, auto dc) {
+    return scn_with_mode(l.hits, l.spec, [&](auto hits, auto spec) {
+      return launch_kernel<F>(F::template kernel<decltype(kind)::value, decltype(dc)::value, decltype(hits)::value, decltype(spec)::value>, l);
+    });
+  });
 }
 
 // one launcher per translation unit (the sizes it instantiates), and the dispatcher over them
-#define SCN_FFT_LAUNCH_ARGS int kind, bool dc, bool hits, bool spec, const ScnFftArgs &args, int num_cus, hipStream_t stream, hipEvent_t stop
-#define SCN_FFT_LAUNCH_PASS kind, dc, hits, spec, args, num_cus, stream, stop
-hipError_t scn_launch_fft_tu0(uint32_t n, SCN_FFT_LAUNCH_ARGS);
-hipError_t scn_launch_fft_tu1(uint32_t n, SCN_FFT_LAUNCH_ARGS);
-hipError_t scn_launch_fft_tu2(uint32_t n, SCN_FFT_LAUNCH_ARGS);
-hipError_t scn_launch_fft_tu3(uint32_t n, SCN_FFT_LAUNCH_ARGS);
-hipError_t scn_launch_fft_tu4(uint32_t n, SCN_FFT_LAUNCH_ARGS);
-hipError_t scn_launch_fft_tu5(uint32_t n, SCN_FFT_LAUNCH_ARGS);
-hipError_t scn_launch_fft_tu6(uint32_t n, SCN_FFT_LAUNCH_ARGS);
-#if SCN_IN_TU(0)
-hipError_t scn_launch_fft_tu0(uint32_t n, SCN_FFT_LAUNCH_ARGS) {
-  return n == 16 ? launch_family<TinyFamily<1>>(SCN_FFT_LAUNCH_PASS) : launch_family<TinyFamily<2>>(SCN_FFT_LAUNCH_PASS);
+template <int TU>
+static hipError_t launch_fft_unit(uint32_t n, const ScnFftLaunch &l) {
+  if constexpr (TU == 0) return n == 16 ? launch_family<TinyFamily<1>>(l) : launch_family<TinyFamily<2>>(l);
+  else if constexpr (TU == 1) return n == 64 ? launch_family<TinyFamily<4>>(l) : launch_family<TinyFamily<8>>(l);
+  else if constexpr (TU == 2) return n == 256 ? launch_family<SmallFamily<1>>(l) : launch_family<SmallFamily<2>>(l);
+  else if constexpr (TU == 3) return n == 1024 ? launch_family<NarrowFamily<4>>(l) : launch_family<NarrowFamily<8>>(l);
+  else if constexpr (TU == 4) return launch_family<NarrowFamily<16>>(l);
+  else if constexpr (TU == 5) return launch_family<Family8k>(l);
+  else return launch_family<Family16k>(l);
 }
-#endif
-#if SCN_IN_TU(1)
-hipError_t scn_launch_fft_tu1(uint32_t n, SCN_FFT_LAUNCH_ARGS) {
-  return n == 64 ? launch_family<TinyFamily<4>>(SCN_FFT_LAUNCH_PASS) : launch_family<TinyFamily<8>>(SCN_FFT_LAUNCH_PASS);
-}
-#endif
-#if SCN_IN_TU(2)
-hipError_t scn_launch_fft_tu2(uint32_t n, SCN_FFT_LAUNCH_ARGS) {
-  return n == 256 ? launch_family<SmallFamily<1>>(SCN_FFT_LAUNCH_PASS) : launch_family<SmallFamily<2>>(SCN_FFT_LAUNCH_PASS);
-}
-#endif
-#if SCN_IN_TU(3)
-hipError_t scn_launch_fft_tu3(uint32_t n, SCN_FFT_LAUNCH_ARGS) {
-  return n == 1024 ? launch_family<NarrowFamily<4>>(SCN_FFT_LAUNCH_PASS) : launch_family<NarrowFamily<8>>(SCN_FFT_LAUNCH_PASS);
-}
-#endif
-#if SCN_IN_TU(4)
-hipError_t scn_launch_fft_tu4(uint32_t, SCN_FFT_LAUNCH_ARGS) { return launch_family<NarrowFamily<16>>(SCN_FFT_LAUNCH_PASS); }
-#endif
-#if SCN_IN_TU(5)
-hipError_t scn_launch_fft_tu5(uint32_t, SCN_FFT_LAUNCH_ARGS) { return launch_family<Family8k>(SCN_FFT_LAUNCH_PASS); }
-#endif
-#if SCN_IN_TU(6)
-hipError_t scn_launch_fft_tu6(uint32_t, SCN_FFT_LAUNCH_ARGS) { return launch_family<Family16k>(SCN_FFT_LAUNCH_PASS); }
+// (a unit of the split build defines its own specialisation and only that: the primary template's definition would let the
+//  dispatcher's table instantiate every unit's kernels where it stands)
+template <int TU>
+hipError_t scn_launch_fft_unit(uint32_t n, const ScnFftLaunch &l);
+#if SCN_TU == -1
+template <int TU>
+hipError_t scn_launch_fft_unit(uint32_t n, const ScnFftLaunch &l) { return launch_fft_unit<TU>(n, l); }
+#elif SCN_TU < 7
+template <>
+hipError_t scn_launch_fft_unit<SCN_TU>(uint32_t n, const ScnFftLaunch &l) { return launch_fft_unit<SCN_TU>(n, l); }
 #endif
 
 #if SCN_IN_TU(7)
@@ -1716,18 +1646,14 @@ hipError_t scn_launch_fft(uint32_t n, int kind, bool dc, bool hits, bool spec, c
                           hipStream_t stream, hipEvent_t stop) {
   if (!hits && !spec) return hipErrorInvalidValue;
   if (args.n_buffers == 0) return stop ? hipEventRecord(stop, stream) : hipSuccess;
+  if (!scn_fft_size_supported(n)) return hipErrorInvalidValue;
   // (256 / 512 points: one descriptor spans a workgroup's SLOTS buffers only, but the per-lane offsets are 32-bit)
   if (n < 1024 && (uint64_t)args.n_buffers * n * 8u > 0xffffffffull) return hipErrorInvalidValue;
-  switch (n) {
-    case 16: case 32: return scn_launch_fft_tu0(n, SCN_FFT_LAUNCH_PASS);
-    case 64: case 128: return scn_launch_fft_tu1(n, SCN_FFT_LAUNCH_PASS);
-    case 256: case 512: return scn_launch_fft_tu2(n, SCN_FFT_LAUNCH_PASS);
-    case 1024: case 2048: return scn_launch_fft_tu3(n, SCN_FFT_LAUNCH_PASS);
-    case 4096: return scn_launch_fft_tu4(n, SCN_FFT_LAUNCH_PASS);
-    case 8192: return scn_launch_fft_tu5(n, SCN_FFT_LAUNCH_PASS);
-    case 16384: return scn_launch_fft_tu6(n, SCN_FFT_LAUNCH_PASS);
-    default: return hipErrorInvalidValue;
-  }
+  static constexpr hipError_t (*units[7])(uint32_t, const ScnFftLaunch &) = {scn_launch_fft_unit<0>, scn_launch_fft_unit<1>, scn_launch_fft_unit<2>,
+                                                                             scn_launch_fft_unit<3>, scn_launch_fft_unit<4>, scn_launch_fft_unit<5>,
+                                                                             scn_launch_fft_unit<6>};
+  const int lg = __builtin_ctz(n);  // 16 / 32, 64 / 128, 256 / 512, 1024 / 2048 share a unit; 4096, 8192, 16384 have one each
+  return units[lg < 12 ? (lg - 4) / 2 : lg - 8](n, ScnFftLaunch{kind, dc, hits, spec, args, num_cus, stream, stop});
 }
 
 bool scn_fft_size_supported(uint32_t n) { return n >= 16 && n <= 16384 && (n & (n - 1u)) == 0u; }

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "scn_device.h"
+#include "scn_dispatch.h"
 #include "scn_kernels.h"
 #include "scn_mixed_dft.h"
 #include "scn_mixed_plans.h"
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(G::W) void scn_fft_mixed_kernel(ScnFftArgs args, ui
 
   typename L::raw_t raw[R1];
   if (blockIdx.x < args.n_buffers) {
-    const __amdgpu_buffer_rsrc_t r0 = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)blockIdx.x * L::kBufBytes(N), L::kBufBytes(N));
+    const __amdgpu_buffer_rsrc_t r0 = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)blockIdx.x * L::kBytes * N, L::kBytes * N);
 #pragma unroll
     for (uint32_t a = 0; a < R1; a++) raw[a] = L::template load<AUX_LD>(r0, N, t_ld, T1 * a);
   }
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(G::W) void scn_fft_mixed_kernel(ScnFftArgs args, ui
     for (uint32_t a = 0; a < R1; a++) v[a] = L::conv(raw[a], dc_re, dc_im, 1.0f) * win[a];
     // the next buffer of this workgroup, branch-free (zero records past the end), in three groups spread over the passes
     const __amdgpu_buffer_rsrc_t rn =
-        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)(more ? nxt : buf) * L::kBufBytes(N), more ? L::kBufBytes(N) : 0u);
+        make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)(more ? nxt : buf) * (L::kBytes * N), more ? L::kBytes * N : 0u);
     auto prefetch = [&](uint32_t a_lo, uint32_t a_hi) {
 #pragma unroll
       for (uint32_t a = 0; a < R1; a++)
@@ -322,7 +323,7 @@ __global__ __launch_bounds__(G::W) void scn_fft_mixed_big_kernel(ScnFftArgs args
   uint32_t par = 0, prev = 0xffffffffu;
 
   for (uint32_t buf = blockIdx.x; buf < args.n_buffers; buf += gridDim.x) {
-    const __amdgpu_buffer_rsrc_t rc = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)buf * L::kBufBytes(N), L::kBufBytes(N));
+    const __amdgpu_buffer_rsrc_t rc = make_rsrc(reinterpret_cast<const char *>(args.raw) + (size_t)buf * (L::kBytes * N), L::kBytes * N);
     int dc_re = 0, dc_im = 0;
     if (KIND != SCN_K_FLOAT_COMPLEX && correct_dc) {  // a pass of its own over the raw samples: the integer sums (utility.cpp:70-79)
       int sr = 0, si = 0;
@@ -476,24 +477,21 @@ __global__ __launch_bounds__(G::W) void scn_fft_mixed_big_kernel(ScnFftArgs args
 #define SCN_MIXED_IN_TU(x) (SCN_MIXED_TU == -1 || SCN_MIXED_TU == (x))
 
 namespace {
-template <class G, int KIND, bool BIG>
-hipError_t launch_mixed_kind(const ScnFftArgs &a, bool dc, bool hits, bool spec, int num_cus, hipStream_t s, hipEvent_t stop) {
+template <class G, int KIND, bool BIG, bool HITS, bool SPEC>
+hipError_t launch_mixed_kernel(const ScnFftLaunch &l) {
   void (*k)(ScnFftArgs, uint32_t);
-  if constexpr (BIG)
-    k = !hits ? scn_fft_mixed_big_kernel<G, KIND, false, true> : spec ? scn_fft_mixed_big_kernel<G, KIND, true, true> : scn_fft_mixed_big_kernel<G, KIND, true, false>;
-  else
-    k = !hits ? scn_fft_mixed_kernel<G, KIND, false, true> : spec ? scn_fft_mixed_kernel<G, KIND, true, true> : scn_fft_mixed_kernel<G, KIND, true, false>;
-  if (G::LDS_BYTES > 65536u) {  // per function and per device: simply set on every launch (see launch_kind, scn_kernels.hip)
+  if constexpr (BIG) k = scn_fft_mixed_big_kernel<G, KIND, HITS, SPEC>;
+  else k = scn_fft_mixed_kernel<G, KIND, HITS, SPEC>;
+  if (G::LDS_BYTES > 65536u) {  // per function and per device: simply set on every launch (see launch_kernel, scn_kernels.hip)
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
     if (e != hipSuccess) return e;
   }
   // one resident wave of persistent workgroups: what fits a CU by registers, LDS and waves (asked of the runtime: the register
   // count of these kernels is the compiler's choice)
-  // (asked once per kernel: one static per instantiation and output mode, atomic because several host threads -- one plan each --
+  // (asked once per kernel: one static per instantiation, atomic because several host threads -- one plan each --
   // may come through here at once; whoever asks first stores the answer, a second asker stores the same one: the figure is a property
   // of the kernel's code object and the GPU model, and the GPUs of a node are alike)
-  static std::atomic<int> per_cu_of_mode[3];
-  std::atomic<int> &cached = per_cu_of_mode[!hits ? 0 : spec ? 1 : 2];
+  static std::atomic<int> cached;
   int per_cu = cached.load(std::memory_order_relaxed);
   if (per_cu < 1) {
     int q = 0;
@@ -502,77 +500,49 @@ hipError_t launch_mixed_kind(const ScnFftArgs &a, bool dc, bool hits, bool spec,
     per_cu = q < 1 ? 1 : q;
     cached.store(per_cu, std::memory_order_relaxed);
   }
-  int grid = num_cus * per_cu;
-  if ((uint32_t)grid > a.n_buffers) grid = (int)a.n_buffers;
-  const uint32_t cdc = dc ? 1u : 0u;
-  if (stop) hipExtLaunchKernelGGL(k, dim3(grid), dim3(G::W), G::LDS_BYTES, s, nullptr, stop, 0, a, cdc);
-  else hipLaunchKernelGGL(k, dim3(grid), dim3(G::W), G::LDS_BYTES, s, a, cdc);
+  int grid = l.num_cus * per_cu;
+  if ((uint32_t)grid > l.args.n_buffers) grid = (int)l.args.n_buffers;
+  const uint32_t cdc = l.dc && KIND != SCN_K_FLOAT_COMPLEX ? 1u : 0u;  // DC removal is a run-time argument of these kernels
+  if (l.stop) hipExtLaunchKernelGGL(k, dim3(grid), dim3(G::W), G::LDS_BYTES, l.stream, nullptr, l.stop, 0, l.args, cdc);
+  else hipLaunchKernelGGL(k, dim3(grid), dim3(G::W), G::LDS_BYTES, l.stream, l.args, cdc);
   return hipGetLastError();
 }
 
 template <class G, bool BIG = false>
-hipError_t launch_mixed(int kind, bool dc, bool hits, bool spec, const ScnFftArgs &args, int num_cus, hipStream_t stream, hipEvent_t stop) {
-  switch (kind) {
-    case SCN_K_FLOAT_COMPLEX: return launch_mixed_kind<G, SCN_K_FLOAT_COMPLEX, BIG>(args, false, hits, spec, num_cus, stream, stop);
-    case SCN_K_SHORT_COMPLEX: return launch_mixed_kind<G, SCN_K_SHORT_COMPLEX, BIG>(args, dc, hits, spec, num_cus, stream, stop);
-    case SCN_K_SHORT: return launch_mixed_kind<G, SCN_K_SHORT, BIG>(args, dc, hits, spec, num_cus, stream, stop);
-    case SCN_K_BYTE_COMPLEX: return launch_mixed_kind<G, SCN_K_BYTE_COMPLEX, BIG>(args, dc, hits, spec, num_cus, stream, stop);
-    default: return hipErrorInvalidValue;
-  }
+hipError_t launch_mixed(const ScnFftLaunch &l) {
+  return scn_with_kind(l.kind, [&](auto kind) {
+    return scn_with_mode(l.hits, l.spec, [&](auto hits, auto spec) {
+      return launch_mixed_kernel<G, decltype(kind)::value, BIG, decltype(hits)::value, decltype(spec)::value>(l);
+    });
+  });
 }
-}  // namespace
-
-#define SCN_MIXED_ARGS int kind, bool dc, bool hits, bool spec, const ScnFftArgs &args, int num_cus, hipStream_t stream, hipEvent_t stop
-hipError_t scn_launch_mixed_tu0(uint32_t n, SCN_MIXED_ARGS);
-hipError_t scn_launch_mixed_tu1(uint32_t n, SCN_MIXED_ARGS);
-hipError_t scn_launch_mixed_tu2(uint32_t n, SCN_MIXED_ARGS);
-hipError_t scn_launch_mixed_tu3(uint32_t n, SCN_MIXED_ARGS);
-hipError_t scn_launch_mixed_tu4(uint32_t n, SCN_MIXED_ARGS);
-hipError_t scn_launch_mixed_tu5(uint32_t n, SCN_MIXED_ARGS);
-hipError_t scn_launch_mixed_tu6(uint32_t n, SCN_MIXED_ARGS);
-hipError_t scn_launch_mixed_tu7(uint32_t n, SCN_MIXED_ARGS);
 
 // (`if constexpr` on the template parameter: a discarded branch instantiates nothing -- with a plain `if` every translation unit
 //  would compile every size's kernels)
 #define SCN_MIXED_CASE(N, R1, R2, R3, PAD1, PAD2, UNIT)  \
   if constexpr (UNIT == TU) {                             \
-    if (n == N) return launch_mixed<GeoMixed<N, R1, R2, R3, PAD1, PAD2>>(kind, dc, hits, spec, args, num_cus, stream, stop); \
+    if (n == N) return launch_mixed<GeoMixed<N, R1, R2, R3, PAD1, PAD2>>(l); \
   }
 #define SCN_MIXED_BIG_CASE(N, R1, R2, R3, PAD1, UNIT)     \
   if constexpr (UNIT == TU) {                             \
-    if (n == N) return launch_mixed<GeoMixedBig<N, R1, R2, R3, PAD1>, true>(kind, dc, hits, spec, args, num_cus, stream, stop); \
+    if (n == N) return launch_mixed<GeoMixedBig<N, R1, R2, R3, PAD1>, true>(l); \
   }
-namespace {
 template <int TU>
-hipError_t launch_mixed_unit(uint32_t n, SCN_MIXED_ARGS) {
+hipError_t launch_mixed_unit(uint32_t n, const ScnFftLaunch &l) {
   SCN_MIXED_PLANS(SCN_MIXED_CASE)
   SCN_MIXED_BIG_PLANS(SCN_MIXED_BIG_CASE)
   return hipErrorInvalidValue;
 }
 }  // namespace
-#if SCN_MIXED_IN_TU(0)
-hipError_t scn_launch_mixed_tu0(uint32_t n, SCN_MIXED_ARGS) { return launch_mixed_unit<0>(n, kind, dc, hits, spec, args, num_cus, stream, stop); }
-#endif
-#if SCN_MIXED_IN_TU(1)
-hipError_t scn_launch_mixed_tu1(uint32_t n, SCN_MIXED_ARGS) { return launch_mixed_unit<1>(n, kind, dc, hits, spec, args, num_cus, stream, stop); }
-#endif
-#if SCN_MIXED_IN_TU(2)
-hipError_t scn_launch_mixed_tu2(uint32_t n, SCN_MIXED_ARGS) { return launch_mixed_unit<2>(n, kind, dc, hits, spec, args, num_cus, stream, stop); }
-#endif
-#if SCN_MIXED_IN_TU(3)
-hipError_t scn_launch_mixed_tu3(uint32_t n, SCN_MIXED_ARGS) { return launch_mixed_unit<3>(n, kind, dc, hits, spec, args, num_cus, stream, stop); }
-#endif
-#if SCN_MIXED_IN_TU(4)
-hipError_t scn_launch_mixed_tu4(uint32_t n, SCN_MIXED_ARGS) { return launch_mixed_unit<4>(n, kind, dc, hits, spec, args, num_cus, stream, stop); }
-#endif
-#if SCN_MIXED_IN_TU(5)
-hipError_t scn_launch_mixed_tu5(uint32_t n, SCN_MIXED_ARGS) { return launch_mixed_unit<5>(n, kind, dc, hits, spec, args, num_cus, stream, stop); }
-#endif
-#if SCN_MIXED_IN_TU(6)
-hipError_t scn_launch_mixed_tu6(uint32_t n, SCN_MIXED_ARGS) { return launch_mixed_unit<6>(n, kind, dc, hits, spec, args, num_cus, stream, stop); }
-#endif
-#if SCN_MIXED_IN_TU(7)
-hipError_t scn_launch_mixed_tu7(uint32_t n, SCN_MIXED_ARGS) { return launch_mixed_unit<7>(n, kind, dc, hits, spec, args, num_cus, stream, stop); }
+// one launcher per translation unit, as scn_launch_fft_unit (scn_kernels.hip)
+template <int TU>
+hipError_t scn_launch_mixed_unit(uint32_t n, const ScnFftLaunch &l);
+#if SCN_MIXED_TU == -1
+template <int TU>
+hipError_t scn_launch_mixed_unit(uint32_t n, const ScnFftLaunch &l) { return launch_mixed_unit<TU>(n, l); }
+#else
+template <>
+hipError_t scn_launch_mixed_unit<SCN_MIXED_TU>(uint32_t n, const ScnFftLaunch &l) { return launch_mixed_unit<SCN_MIXED_TU>(n, l); }
 #endif
 
 #if SCN_MIXED_IN_TU(0)
@@ -601,16 +571,9 @@ hipError_t scn_launch_mixed(uint32_t n, int kind, bool dc, bool hits, bool spec,
 #define SCN_MIXED_BIG_UNIT_OF(N, R1, R2, R3, PAD1, UNIT) SCN_MIXED_UNIT_OF(N, R1, R2, R3, PAD1, 0, UNIT)
   SCN_MIXED_PLANS(SCN_MIXED_UNIT_OF)
   SCN_MIXED_BIG_PLANS(SCN_MIXED_BIG_UNIT_OF)
-  switch (unit) {
-    case 0: return scn_launch_mixed_tu0(n, kind, dc, hits, spec, args, num_cus, stream, stop);
-    case 1: return scn_launch_mixed_tu1(n, kind, dc, hits, spec, args, num_cus, stream, stop);
-    case 2: return scn_launch_mixed_tu2(n, kind, dc, hits, spec, args, num_cus, stream, stop);
-    case 3: return scn_launch_mixed_tu3(n, kind, dc, hits, spec, args, num_cus, stream, stop);
-    case 4: return scn_launch_mixed_tu4(n, kind, dc, hits, spec, args, num_cus, stream, stop);
-    case 5: return scn_launch_mixed_tu5(n, kind, dc, hits, spec, args, num_cus, stream, stop);
-    case 6: return scn_launch_mixed_tu6(n, kind, dc, hits, spec, args, num_cus, stream, stop);
-    case 7: return scn_launch_mixed_tu7(n, kind, dc, hits, spec, args, num_cus, stream, stop);
-    default: return hipErrorInvalidValue;
-  }
+  static constexpr hipError_t (*units[8])(uint32_t, const ScnFftLaunch &) = {scn_launch_mixed_unit<0>, scn_launch_mixed_unit<1>, scn_launch_mixed_unit<2>,
+                                                                             scn_launch_mixed_unit<3>, scn_launch_mixed_unit<4>, scn_launch_mixed_unit<5>,
+                                                                             scn_launch_mixed_unit<6>, scn_launch_mixed_unit<7>};
+  return unit < 0 ? hipErrorInvalidValue : units[unit](n, ScnFftLaunch{kind, dc, hits, spec, args, num_cus, stream, stop});
 }
 #endif

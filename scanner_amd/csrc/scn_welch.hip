@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "scn_device.h"
+#include "scn_dispatch.h"
 
 // tunables, each measured (profiles/r02_experiments.md, r03_experiments.md section 5, r05_welch_ab.txt)
 // cache policy of the input stream loads: non-temporal -- with the overlapping half of a segment kept in registers a sample is
@@ -46,53 +47,35 @@ constexpr uint32_t WP = 272;  // LDS row pitch (slots): 16 rows of 256 + 16, as 
 // (messageQueue.h:190-237) -- here of hop = N/2 samples, the unit by which a 50 %-overlap consumer advances.  K1 is applied per
 // block: the integer mean removed with correctDC is the block's (utility.cpp:70-79 sums over the call's `count`), and planar
 // int16 is I[hop] then Q[hop] per block (utility.cpp:9-32).  WelchRaw<KIND>::load fetches sample s + 4096 a8 (a8 in [0, 8)) of
-// the block a descriptor covers; conv leaves float(source - dc) -- the scale 1/max is a power of two and rides in the window taps.
+// the block a descriptor covers; Wire<KIND>::conv (scn_wire.h) leaves float(source - dc) -- the scale 1/max is a power of two and rides in
+// the window taps.
 namespace {
 template <int KIND>
 struct WelchRaw;
 template <>
-struct WelchRaw<SCN_K_FLOAT_COMPLEX> {
-  static constexpr uint32_t kBytes = 8;
-  typedef v2f raw_t;
+struct WelchRaw<SCN_K_FLOAT_COMPLEX> : Wire<SCN_K_FLOAT_COMPLEX> {
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t s, uint32_t a8) {
     return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, s * 8u, a8 * 32768u, SCN_WELCH_AUX_IN));
   }
-  static __device__ __forceinline__ cf conv(raw_t r, int, int) { return from_v2f(r); }
 };
 template <>
-struct WelchRaw<SCN_K_SHORT_COMPLEX> {
-  static constexpr uint32_t kBytes = 4;
-  typedef int raw_t;
+struct WelchRaw<SCN_K_SHORT_COMPLEX> : Wire<SCN_K_SHORT_COMPLEX> {
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t s, uint32_t a8) {
     return __builtin_amdgcn_raw_buffer_load_b32(r, s * 4u, a8 * 16384u, SCN_WELCH_AUX_IN);
   }
-  // float(source - dc), utility.cpp:81-82, in wrapping int arithmetic like the oracle's conv1
-  static __device__ __forceinline__ cf conv(raw_t r, int dc_re, int dc_im) {
-    const int re = (int)(short)(r & 0xffff), im = r >> 16;
-    return cf{(float)(int)((uint32_t)re - (uint32_t)dc_re), (float)(int)((uint32_t)im - (uint32_t)dc_im)};
-  }
 };
 template <>
-struct WelchRaw<SCN_K_SHORT> {  // planar: I[hop] then Q[hop] per block
-  static constexpr uint32_t kBytes = 4;
-  typedef int raw_t;
+struct WelchRaw<SCN_K_SHORT> : Wire<SCN_K_SHORT> {  // planar: I[hop] then Q[hop] per block
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t s, uint32_t a8) {
     const int re = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, s * 2u, a8 * 8192u, SCN_WELCH_AUX_IN);
     const int im = (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, s * 2u, 65536u + a8 * 8192u, SCN_WELCH_AUX_IN);
     return (re & 0xffff) | (im << 16);
   }
-  static __device__ __forceinline__ cf conv(raw_t r, int dc_re, int dc_im) { return WelchRaw<SCN_K_SHORT_COMPLEX>::conv(r, dc_re, dc_im); }
 };
 template <>
-struct WelchRaw<SCN_K_BYTE_COMPLEX> {
-  static constexpr uint32_t kBytes = 2;
-  typedef int raw_t;
+struct WelchRaw<SCN_K_BYTE_COMPLEX> : Wire<SCN_K_BYTE_COMPLEX> {
   static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, uint32_t s, uint32_t a8) {
     return (int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, s * 2u, a8 * 8192u, SCN_WELCH_AUX_IN);
-  }
-  static __device__ __forceinline__ cf conv(raw_t r, int dc_re, int dc_im) {
-    const int re = (int)(signed char)(r & 0xff), im = (int)(signed char)((r >> 8) & 0xff);
-    return cf{(float)(int)((uint32_t)re - (uint32_t)dc_re), (float)(int)((uint32_t)im - (uint32_t)dc_im)};
   }
 };
 }  // namespace
@@ -368,38 +351,24 @@ void scn_welch_column_groups(uint32_t n_segments, int num_cus, uint32_t *groups,
   *per = G ? (n_segments + G - 1u) / G : 0u;
 }
 
-namespace {
-template <int KIND>
-hipError_t launch_cols(const ScnWelchArgs &a, bool dc, uint32_t G, size_t lds, hipStream_t s) {
-  if constexpr (KIND != SCN_K_FLOAT_COMPLEX) {  // (no DC removal for float samples, messageQueue.h:229-236)
-    if (dc) {
-      hipError_t e = hipMemsetAsync(a.dc_sums, 0, sizeof(int) * 2u * (a.n_segments + 1u), s);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(scn_welch_dc_kernel<KIND>, dim3(4u * (a.n_segments + 1u)), dim3(256), 0, s, a);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      hipLaunchKernelGGL((scn_welch_cols_kernel<KIND, true>), dim3(16 * G), dim3(256), lds, s, a);
-      return hipGetLastError();
-    }
-  }
-  hipLaunchKernelGGL((scn_welch_cols_kernel<KIND, false>), dim3(16 * G), dim3(256), lds, s, a);
-  return hipGetLastError();
-}
-}  // namespace
-
 hipError_t scn_launch_welch(int kind, bool correct_dc, const ScnWelchArgs &a, int num_cus, hipStream_t s) {
   if (a.n_segments == 0) return hipSuccess;
   if (a.hop != WN / 2u) return hipErrorInvalidValue;  // (the column kernel's in-register overlap is the 50 % one)
   const size_t lds = 16 * WP * sizeof(v2f);
   uint32_t G, per;
   scn_welch_column_groups(a.n_segments, num_cus, &G, &per);
-  hipError_t e;
-  switch (kind) {
-    case SCN_K_FLOAT_COMPLEX: e = launch_cols<SCN_K_FLOAT_COMPLEX>(a, false, G, lds, s); break;
-    case SCN_K_SHORT_COMPLEX: e = launch_cols<SCN_K_SHORT_COMPLEX>(a, correct_dc, G, lds, s); break;
-    case SCN_K_SHORT: e = launch_cols<SCN_K_SHORT>(a, correct_dc, G, lds, s); break;
-    case SCN_K_BYTE_COMPLEX: e = launch_cols<SCN_K_BYTE_COMPLEX>(a, correct_dc, G, lds, s); break;
-    default: return hipErrorInvalidValue;
-  }
+  hipError_t e = scn_with_kind(kind, correct_dc, [&](auto k, auto d) {
+    constexpr int KIND = decltype(k)::value;
+    constexpr bool DC = decltype(d)::value;
+    if constexpr (DC) {
+      hipError_t z = hipMemsetAsync(a.dc_sums, 0, sizeof(int) * 2u * (a.n_segments + 1u), s);
+      if (z != hipSuccess) return z;
+      hipLaunchKernelGGL(scn_welch_dc_kernel<KIND>, dim3(4u * (a.n_segments + 1u)), dim3(256), 0, s, a);
+      if ((z = hipGetLastError()) != hipSuccess) return z;
+    }
+    hipLaunchKernelGGL((scn_welch_cols_kernel<KIND, DC>), dim3(16 * G), dim3(256), lds, s, a);
+    return hipGetLastError();
+  });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(scn_welch_rows_kernel, dim3(16 * a.n_psd * a.parts), dim3(256), lds, s, a);
   e = hipGetLastError();

@@ -39,7 +39,7 @@ struct scn_welch {
   ScnDeviceMem<float> d_partial;  // [parts][max_psd][n] partial power sums (row kernel -> combine kernel); shared by the slots
                                   // through stream order on the device path, per-slot copies on the pinned path
   uint32_t parts = 1;
-  uint32_t bytes_per_sample = 8;
+  uint32_t bytes_per_sample = scn_wire_bytes(SCN_K_FLOAT_COMPLEX);
   float scale = 1.0f;      // K1's 1/max
   bool dc = false;         // correct_dc on an integer wire format
   ScnDeviceMem<int> d_dc;  // [max_psd*K + 1][2] block sums (device path; the pinned path's slots own theirs)

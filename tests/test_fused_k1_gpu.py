@@ -1,8 +1,10 @@
 """Every kernel family's OWN sample conversion (K1), bit for bit.
 
 scn_convert_kernel (Plan.convert_raw) is the one K1 pinned to the reference's utility.cpp:9-84 (tests/test_oracle_ref_dsp.py), but no
-transform runs it: each family carries its own integer DC sums, its own `int32 /= uint32` division, its own planar addressing and its
-own fold of onebymax into the window tap (search `dc_re = (int)((uint32_t)` in scanner_amd/csrc).  Each of them forms
+transform runs it.  A sample's decode is stated once (Wire<KIND>, scanner_amd/csrc/scn_wire.h, held on a CPU by tests/cpp/test_wire.cpp),
+but each family still fetches its samples its own way (RawLoader, BigRaw, WelchRaw: planar addressing, lane pairs) and carries its own
+integer DC sums, its own `int32 /= uint32` division (search `dc_re = (int)((uint32_t)` in scanner_amd/csrc) and its own fold of
+onebymax into the window tap.  Each of them forms
 conv(raw, dc, 1.0f) * (w[i] * scale) with scale = +-2^-k, so an integer-kind plan A on the raw bytes and a FLOAT_COMPLEX plan B of the
 same size, window, mask, threshold and flags on A.convert_raw(raw) multiply the same two real numbers in every lane
 (tests/test_fused_k1_cpu.py proves the fold exact, contracted into an FMA or not), and everything behind that product is the same
@@ -23,7 +25,7 @@ and maximum present; a constant buffer at the minimum and one at the maximum; bu
 sum and the converse; I and Q of visibly different content throughout (Q is a sawtooth where I is noise, or carries another offset).
 61 buffers per launch -- a prime, so that wherever a workgroup holds several buffers (256 ... 8 of them from 16 to 512 points) the last
 one's slots stay partly empty -- 29 from 32768 points up.  Two more launches at 4096 and 8192 points in int16 hold 61 buffers more than
-the launch has workgroups (scn_kernels.hip launch_kind: grid = CUs x WG_PER_CU, 3 for Geo<16> and 2 for Geo8k), so that workgroups take
+the launch has workgroups (scn_kernels.hip launch_kernel: grid = CUs x WG_PER_CU, 3 for Geo<16> and 2 for Geo8k), so that workgroups take
 further buffers from the queue (scn_uses_queue).
 
 ENOB cycles over the cases: 8 for int8 (the only value its reference path knows: the wrapping, negative scale); 12, 14, 16 and 1 for
@@ -32,8 +34,8 @@ is 1 / 0 (tests/test_fused_k1_cpu.py).
 
 EXEMPTIONS: none.  The issue that asked for this module allowed a family to be exempt where the dispatch instantiates another template
 or butterfly order for the integer kinds, and named a "wide 8192-point integer form".  No such form exists: scn_launch_fft
-(scn_kernels.hip, `case 8192`) sends every wire format to Family8k, i.e. scn_fft8k_kernel<KIND, DC, HITS, SPEC>, whose body differs by
-KIND only in RawLoader<KIND> (load2 / ints / conv) and in where the next buffer comes from (DYN); likewise every other family.  EXEMPT
+(scn_kernels.hip, unit 5 of its table) sends every wire format to Family8k, i.e. scn_fft8k_kernel<KIND, DC, HITS, SPEC>, whose body differs by
+KIND only in RawLoader<KIND>::load2, Wire<KIND>::ints / conv and in where the next buffer comes from (DYN); likewise every other family.  EXEMPT
 stays as the place to name one, with file and line, should a compiler ever contract the two instantiations differently; an exempt
 case is then not skipped but held against float64 (the module fails where EXEMPT is not empty and that path is not written), and the
 module fails above MAX_EXEMPT_SHARE.

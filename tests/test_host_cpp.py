@@ -116,6 +116,31 @@ def test_plan_arithmetic_stand_alone(tmp_path, san):
     assert "runtime error" not in out.stderr and "Sanitizer" not in out.stderr, out.stderr[-3000:]
 
 
+@pytest.mark.parametrize("san", ["address,undefined", ""])
+def test_wire_decode_stand_alone(tmp_path, san):
+    """K1's decode (scanner_amd/csrc/scn_wire.h: Wire<KIND>::ints / conv, scn_wire_bytes), the one every kernel family calls, compiled
+    by plain g++ as C++17 -- no HIP header on the include path -- into tests/cpp/test_wire.cpp's own program and held BIT FOR BIT
+    against the oracle's conversions (oracle/scn_oracle.c, built into the program as C): every int16 value of I with Q in another
+    order (interleaved and planar; ENOB 1, 12, 14, 16), every int8 I/Q pair (ENOB 8), DC removal off and on with integer sums that
+    are negative, zero, n - 1, n and n + 1; float samples a copy, NaN payloads included.  Plain, and under ASan + UBSan, which must
+    report nothing."""
+    csrc = os.path.join(ROOT, "scanner_amd", "csrc")
+    flags = ["-O1", "-g", "-fno-omit-frame-pointer"] + ([f"-fsanitize={san}"] if san else [])
+    obj, exe = tmp_path / "scn_oracle.o", tmp_path / "test_wire"
+    r = subprocess.run(["gcc", "-std=c11", "-fno-fast-math", "-ffp-contract=off"] + flags + ["-c", os.path.join(ROOT, "oracle", "scn_oracle.c"), "-o", str(obj)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    cmd = ["g++", "-x", "c++", "-std=c++17"] + flags + ["-Wall", "-I", csrc, "-I", os.path.join(ROOT, "oracle"),
+                                                          os.path.join(ROOT, "tests", "cpp", "test_wire.cpp"), os.path.join(csrc, "scn_host.hip"),
+                                                          "-x", "none", str(obj), "-o", str(exe), "-lm", "-lpthread"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
+    assert out.returncode == 0 and "wire tests ok" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+    assert "runtime error" not in out.stderr and "Sanitizer" not in out.stderr, out.stderr[-3000:]
+
+
 def test_abi_bench_refuses_what_it_does_not_understand(host_build):
     """bench.py's C++ child (the records legs): an unknown option or a depth outside the plan's slots is an error before
     anything touches the GPU, and without a GPU it says so instead of printing a line."""

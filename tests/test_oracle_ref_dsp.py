@@ -83,7 +83,7 @@ def test_live_reference_db_map_on_random_spectra(oracle_mod, seed, n, exp):
 
 @pytest.mark.gpu
 def test_product_k1_matches_reference_fixture(built_lib):
-    """The HIP path's own convert (scn_convert_raw = the RawLoader the fused kernels use) against the reference's output."""
+    """The HIP path's own convert (scn_convert_raw = the RawLoader and Wire<KIND> decode the fused kernels use) against the reference's output."""
     import torch
 
     from scanner_amd import Plan, capi
