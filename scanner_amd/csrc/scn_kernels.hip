@@ -1324,6 +1324,23 @@ __global__ __launch_bounds__(512, 2) void scn_fft16k2_kernel(ScnFftArgs args) {
 // converts the two extremes once.  One 256-thread workgroup per buffer, any N; pure HBM
 // streaming (8/4/2 B per sample in, 8 B per buffer out).
 // ------------------------------------------------------------------------------------
+// What both time-domain kernels end with: a buffer's extremes of |x|^2 -> max_db, min_db, once per buffer.  pmax = -1 / pmin = +inf: no
+// sample replaced the initial value (every power NaN; for the minimum also +inf, which `magnitude < minMagnitude` never takes).
+// 10*log2(sqrt(p))/log2(10).  v_sqrt_f32 and v_log_f32 read a denormal input as 0: a denormal p is scaled by 2^64 first (exact), which scales
+// the root by 2^32 and adds 32 to the logarithm.  A normal p goes through the same instructions as ever, bit for bit.
+__device__ __forceinline__ float scn_td_db(float p) {
+  const float k = 3.01029995663981195214f;  // 10/log2(10)
+  const bool denormal = p > 0.0f && p < 1.17549435e-38f;
+  const float l = __builtin_amdgcn_logf(__builtin_amdgcn_sqrtf(denormal ? p * 0x1p64f : p));
+  return k * (denormal ? l - 32.0f : l);
+}
+// the reference's odd initial values (numeric_limits<float>::min() is the smallest POSITIVE float, process.cpp:207-208) bound the
+// results, and a minimum nothing replaced stays FLT_MAX (a sample of p = FLT_MAX converts like any other: 192.66 dB)
+__device__ __forceinline__ void scn_td_store(const ScnTdArgs &args, uint32_t buf, float pmax, float pmin) {
+  args.max_db[buf] = fmaxf(1.17549435e-38f, scn_td_db(pmax));
+  args.min_db[buf] = pmin == __builtin_inff() ? 3.40282347e+38f : fminf(3.40282347e+38f, scn_td_db(pmin));
+}
+
 template <int KIND, bool DC>
 __global__ __launch_bounds__(256) void scn_time_domain_kernel(ScnTdArgs args) {
   typedef RawLoader<KIND> L;
@@ -1353,7 +1370,7 @@ __global__ __launch_bounds__(256) void scn_time_domain_kernel(ScnTdArgs args) {
       dc_re = (int)((uint32_t)(s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]) / N);  // utility.cpp:77-78 quirk
       dc_im = (int)((uint32_t)(s_sum[4] + s_sum[5] + s_sum[6] + s_sum[7]) / N);
     }
-    float pmax = -1.0f, pmin = 3.40282347e+38f;  // |x|^2 >= 0, so -1 is "no sample yet"
+    float pmax = -1.0f, pmin = __builtin_inff();  // |x|^2 >= 0, so -1 is "no sample yet"; +inf likewise (scn_td_store)
     for (uint32_t i = t; i < N; i += 256) {
 #pragma clang fp contract(off)  // (__fmul_rn / __fadd_rn are plain * and + in hipcc's headers, contracted like any other: the
                                 // operators are written here, where the pragma governs them)
@@ -1375,13 +1392,7 @@ __global__ __launch_bounds__(256) void scn_time_domain_kernel(ScnTdArgs args) {
     if (t == 0) {
       pmax = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
       pmin = fminf(fminf(s_min[0], s_min[1]), fminf(s_min[2], s_min[3]));
-      // 10*log2(sqrt(p))/log2(10); the reference's odd initial values (numeric_limits<float>::min()
-      // is the smallest POSITIVE float, process.cpp:207-208) bound the results
-      const float k = 3.01029995663981195214f;  // 10/log2(10)
-      float dmax = k * __builtin_amdgcn_logf(__builtin_amdgcn_sqrtf(pmax));
-      float dmin = k * __builtin_amdgcn_logf(__builtin_amdgcn_sqrtf(pmin));
-      args.max_db[buf] = fmaxf(1.17549435e-38f, dmax);
-      args.min_db[buf] = fminf(3.40282347e+38f, dmin);
+      scn_td_store(args, buf, pmax, pmin);
     }
     __syncthreads();
   }
@@ -1455,7 +1466,7 @@ __global__ __launch_bounds__(256) void scn_time_domain_wave_kernel(ScnTdArgs arg
       dc_re = (int)((uint32_t)sr / N);  // utility.cpp:77-78 quirk
       dc_im = (int)((uint32_t)si / N);
     }
-    float pmax = -1.0f, pmin = 3.40282347e+38f;  // |x|^2 >= 0, so -1 is "no sample yet"
+    float pmax = -1.0f, pmin = __builtin_inff();  // |x|^2 >= 0, so -1 is "no sample yet"; +inf likewise (scn_td_store)
     for_each_sample([&](typename L::raw_t r) {
 #pragma clang fp contract(off)  // (as in scn_time_domain_kernel)
       const cf x = L::conv(r, dc_re, dc_im, args.scale);
@@ -1469,12 +1480,7 @@ __global__ __launch_bounds__(256) void scn_time_domain_wave_kernel(ScnTdArgs arg
       pmin = fminf(pmin, __shfl_xor(pmin, off, 64));
     }
     if (lane == 0) {
-      // 10*log2(sqrt(p))/log2(10); the reference's odd initial values bound the results (process.cpp:207-208)
-      const float k = 3.01029995663981195214f;  // 10/log2(10)
-      const float dmax = k * __builtin_amdgcn_logf(__builtin_amdgcn_sqrtf(pmax));
-      const float dmin = k * __builtin_amdgcn_logf(__builtin_amdgcn_sqrtf(pmin));
-      args.max_db[buf] = fmaxf(1.17549435e-38f, dmax);
-      args.min_db[buf] = fminf(3.40282347e+38f, dmin);
+      scn_td_store(args, buf, pmax, pmin);
     }
   }
 }

@@ -1126,6 +1126,8 @@ def test_c2_full_size(torch_cuda, oracle_mod):
     (1004, capi.KIND_SHORT_COMPLEX, 12, True),
 ])
 def test_time_domain_mode(torch_cuda, oracle_mod, n, kind, enob, dc):
+    """These samples lie below 0 dB, where the reference's maximum reads as its clamp constant numeric_limits<float>::min()
+    (process.cpp:207) in most buffers; tests/test_time_domain_gpu.py holds the reduction itself, sample by sample."""
     nb = 50
     rng = np.random.default_rng(n)
     x = (rng.standard_normal((nb, n)) + 1j * rng.standard_normal((nb, n))).astype(np.complex64) * 0.05
