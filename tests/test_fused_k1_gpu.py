@@ -24,9 +24,10 @@ and maximum present; a constant buffer at the minimum and one at the maximum; bu
 -n (the 0 / 1 boundary of the mean, and the first sums the quirk turns into 2^32 / n); a buffer with a negative I sum and a positive Q
 sum and the converse; I and Q of visibly different content throughout (Q is a sawtooth where I is noise, or carries another offset).
 61 buffers per launch -- a prime, so that wherever a workgroup holds several buffers (256 ... 8 of them from 16 to 512 points) the last
-one's slots stay partly empty -- 29 from 32768 points up.  Two more launches at 4096 and 8192 points in int16 hold 61 buffers more than
-the launch has workgroups (scn_kernels.hip launch_kernel: grid = CUs x WG_PER_CU, 3 for Geo<16> and 2 for Geo8k), so that workgroups take
-further buffers from the queue (scn_uses_queue).
+one's slots stay partly empty -- 29 from 32768 points up (fewer than the column kernel's G = 3 CUs / (n / 4096) workgroup
+rows: no workgroup takes a second buffer there; tests/test_launch_shape_gpu.py runs that loop).  Two more launches at 4096 and
+8192 points in int16 hold 61 buffers more than the launch has workgroups (scn_kernels.hip launch_kernel: grid = CUs x WG_PER_CU, 3
+for Geo<16> and 2 for Geo8k), so that workgroups take further buffers from the queue (scn_uses_queue).
 
 ENOB cycles over the cases: 8 for int8 (the only value its reference path knows: the wrapping, negative scale); 12, 14, 16 and 1 for
 the int16 kinds.  16 and 1 are the extremes with a finite scale: the plan accepts up to 32, but from 17 up max wraps to 0 and the scale
