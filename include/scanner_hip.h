@@ -42,7 +42,9 @@ extern "C" {
                              still 6 (additions only, nothing existing changes): scn_signal, scn_collect_signals,
                              scn_signals_from_hits; scn_plan_desc.detect / floor_permille (carved out of its reserved words: same
                              size, zero = the fixed threshold), SCN_DETECT_*, SCN_FLOOR_MIN, scn_collect_floor,
-                             scn_floor_from_spectrum */
+                             scn_floor_from_spectrum;
+                             still 6 (additions only): the floor window -- SCN_FLOOR_TRAIN_MAX, SCN_FLOOR_GUARD_MAX,
+                             scn_plan_set_floor_window, scn_local_floor_from_spectrum */
 
 /* status codes */
 enum {
@@ -179,6 +181,27 @@ enum {
   SCN_DETECT_FLOOR = 1  /* power_db > floor_db[unit] + threshold */
 };
 #define SCN_FLOOR_MIN 0xffffffffu /* floor_permille: rank 0, the minimum (0 itself asks for the default, as SCN_DC_IGNORE_NONE) */
+
+/* Floor window (scn_plan_set_floor_window): each bin's floor comes from its own neighbourhood -- order-statistic CFAR.  A floor
+ * plan has a floor window (train, guard), initially none; without one the floor is the unit-wide one above.  With a window, for a
+ * unit u and an evaluated bin with fftshift index i (natural bin j = (i + n/2) % n; the mask is the one above, as everywhere):
+ *   reference cells of i: the EVALUATED bins at fftshift indices i' with guard < |i' - i| <= guard + train and 0 <= i' < n.
+ *     Distances are in fftshift (frequency) order; there is no wrap between i = 0 and i = n - 1, which are opposite band edges.
+ *     Bins the mask removes (outside [i_lo, i_hi], or in the DC window) take up distance but are not cells.  M_i is the number
+ *     of cells: 2*train for interior bins, fewer near a band edge or the DC hole.
+ *   r_i = (uint64)permille * (M_i - 1) / 1000 in integer arithmetic, permille from floor_permille exactly as above (0 -> 500,
+ *     SCN_FLOOR_MIN -> 0); floor_i = the value of rank r_i among the cells in the key order above;
+ *   cut_i = floor_i + threshold, ONE float addition; bin i is a hit iff power_db[u][j] > cut_i, strictly.
+ * Records, their power_db, freq_hz, seq_id, their order and trigger are those of a plan that cut bin i at cut_i.  A NaN is placed
+ * as the key places it and is otherwise unspecified; a unit that is all -inf has no hits.  No float sum is involved: the hit list
+ * is exact, the same bits on every run and every route, as the unit-wide floor's.
+ * Limits: 1 <= train <= SCN_FLOOR_TRAIN_MAX, guard <= SCN_FLOOR_GUARD_MAX.  A window under which some evaluated bin has M_i = 0
+ * is SCN_E_INVALID: n = 16 with the default mask evaluates i in {2, 3, 4, 12, 13, 14}; (train 1, guard 0) is valid, (1, 1) is not
+ * (bin 3's only candidates are i = 1, out of band, and i = 5, in the DC window).  That is a property of (n, mask, train, guard)
+ * alone.  A windowed submit has no per-unit floor: scn_collect_floor on its slot is SCN_E_INVALID; scn_local_floor_from_spectrum
+ * on the returned spectrum gives the per-bin floors. */
+#define SCN_FLOOR_TRAIN_MAX 128u
+#define SCN_FLOOR_GUARD_MAX 64u
 
 /* Signals (scn_collect_signals, scn_signals_from_hits): runs of nearby hits merged into one record each.  A plan's buffer is
  * its unit of output (for an averaged plan: the group).  The hits of one unit, in increasing i, are split into signals: a hit
@@ -317,6 +340,18 @@ SCN_API int scn_collect_floor(scn_plan *plan, int slot, float *floor_db);
  * values, is SCN_E_INVALID. */
 SCN_API int scn_floor_from_spectrum(const float *power_db, uint32_t n, uint32_t dc_ignore_bins, double use_bandwidth,
                                     uint32_t floor_permille, float *floor_db);
+
+/* Floor plans only (SCN_E_INVALID otherwise).  From the next submit on, each bin's floor is the rank among its own reference cells
+ * ("Floor window" above).  train_bins = 0 (with guard_bins = 0) returns to the unit-wide floor.  SCN_E_STATE while any slot is
+ * pending; collected slots keep their lists.  Limits and the M_i >= 1 rule: SCN_E_INVALID, nothing changed. */
+SCN_API int scn_plan_set_floor_window(scn_plan *plan, uint32_t train_bins, uint32_t guard_bins);
+
+/* The same definition on ONE unit's host spectrum (n floats, natural bin order), with the descriptor's zero defaults for
+ * dc_ignore_bins, use_bandwidth and floor_permille: floor_db[j] = floor_i for every evaluated bin, other entries left untouched
+ * (train_bins = guard_bins = 0: the unit-wide floor in every evaluated entry).  Needs no device; the definition the GPU form is
+ * held to.  Same rejections as scn_floor_from_spectrum, plus the window's. */
+SCN_API int scn_local_floor_from_spectrum(const float *power_db, uint32_t n, uint32_t dc_ignore_bins, double use_bandwidth,
+                                          uint32_t floor_permille, uint32_t train_bins, uint32_t guard_bins, float *floor_db);
 
 /* Time-domain plans (mode = SCN_MODE_TIME_DOMAIN; ProcessSamples::DoTimeDomainThresholding,
  * process.cpp:203-237): wait for the slot's submit and fetch, per buffer, the maximum and

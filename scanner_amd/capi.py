@@ -25,6 +25,7 @@ ABI_VERSION = 6
 AVG_DWELL, AVG_SWEEPS = 0, 1  # scn_plan_desc.average_layout
 DETECT_FIXED, DETECT_FLOOR = 0, 1  # scn_plan_desc.detect
 FLOOR_MIN = 0xFFFFFFFF  # scn_plan_desc.floor_permille: rank 0 (0 itself asks for the default, the median)
+FLOOR_TRAIN_MAX, FLOOR_GUARD_MAX = 128, 64  # the floor window's limits (scn_plan_set_floor_window)
 PATH_UNSUPPORTED, PATH_FUSED, PATH_FOUR_STEP, PATH_STAGED, PATH_BLUESTEIN = range(5)
 COMM_ID_BYTES = 128
 GATHER_TICKETS = 4
@@ -108,6 +109,8 @@ SYMBOLS = {
     "scn_signals_from_hits": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "scn_collect_floor": (C.c_int, [_vp, C.c_int, _vp]),
     "scn_floor_from_spectrum": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_float)]),
+    "scn_plan_set_floor_window": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
+    "scn_local_floor_from_spectrum": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
     "scn_collect_time_domain": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "scn_convert_raw": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "scn_wait": (C.c_int, [_vp, C.c_int]),
@@ -232,6 +235,21 @@ def floor_from_spectrum(power_db, dc_ignore_bins=4, use_bandwidth=0.75, floor_pe
     check(lib().scn_floor_from_spectrum(power_db.ctypes.data_as(_vp), power_db.size, DC_IGNORE_NONE if dc_ignore_bins == 0 else int(dc_ignore_bins),
                                         float(use_bandwidth), int(floor_permille), C.byref(out)), "scn_floor_from_spectrum")
     return np.frombuffer(bytes(out), np.float32)[0]  # (the bits as they are: no detour through a Python float)
+
+
+def local_floor_from_spectrum(power_db, train_bins, guard_bins=0, dc_ignore_bins=4, use_bandwidth=0.75, floor_permille=0, out=None):
+    """scn_local_floor_from_spectrum: the floor window's per-bin floors of ONE unit's dB spectrum (natural bin order) -- float32 [n],
+    entry j the value of rank floor_permille * (M_i - 1) // 1000 among the reference cells of the evaluated bin j (the evaluated bins
+    guard_bins < |i' - i| <= guard_bins + train_bins away in fftshift order).  Entries of bins the mask removes are left as they are
+    in `out` (NaN in a fresh array).  Needs no device."""
+    power_db = np.ascontiguousarray(power_db, np.float32).reshape(-1)
+    if out is None:
+        out = np.full(power_db.size, np.nan, np.float32)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == power_db.size
+    check(lib().scn_local_floor_from_spectrum(power_db.ctypes.data_as(_vp), power_db.size, DC_IGNORE_NONE if dc_ignore_bins == 0 else int(dc_ignore_bins),
+                                              float(use_bandwidth), int(floor_permille), int(train_bins), int(guard_bins), out.ctypes.data_as(_vp)),
+          "scn_local_floor_from_spectrum")
+    return out
 
 
 def hackrf_sweep_fixup(transfer, scan_offset_hz=0):

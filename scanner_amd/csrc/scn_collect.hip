@@ -259,6 +259,8 @@ int scn_collect_floor(scn_plan *p, int slot, float *floor_db) {
   if (!p->floor) return scn_fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_FLOOR");
   Slot &s = p->slot[slot];
   if (s.pending || !s.list_valid) return scn_fail(SCN_E_STATE, "slot %d: no collected submit whose floor is still available", slot);
+  if (s.floor_windowed)
+    return scn_fail(SCN_E_INVALID, "slot %d was submitted under a floor window: every bin has a floor of its own (scn_local_floor_from_spectrum), no unit has one", slot);
   if (s.n_buffers) memcpy(floor_db, s.h_floor.get(), sizeof(float) * s.n_buffers);  // (in pinned memory since `done`: scn_collect waited for it)
   return SCN_OK;
 }

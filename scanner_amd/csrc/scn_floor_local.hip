@@ -1,0 +1,216 @@
+// scn_floor_local.hip -- the floor detector with a floor window (scn_plan_set_floor_window; definition: scanner_hip.h, "Floor window").
+//
+// The same place as scn_floor.hip's kernel -- one kernel behind the transform, on the dB spectrum the spectrum-only specialisations
+// store -- and the same output: {i, power_db} records in the unit's region, in any order, and the unit's count.  Here every bin has
+// a floor of its own: the value of rank r_i among its reference cells, the evaluated bins guard < |i' - i| <= guard + train away in
+// fftshift order.  No FFT kernel is touched.
+//
+// No selection is needed.  With the cells' values in key order v_(0) <= v_(1) <= ... and w_(k) = fl(v_(k) + threshold),
+//     power_db[j] > fl(v_(r_i) + threshold)   <=>   #{cells c : fl(c + threshold) < power_db[j]} >= r_i + 1,
+// because v -> fl(v + threshold) is non-decreasing along the key order (-0.0 and +0.0 differ in key but compare equal, which
+// changes no comparison): if x > w_(r) then w_(0) ... w_(r) are all below x, r + 1 of them; and if r + 1 cells lie below x, one of
+// them has a rank k >= r, so w_(r) <= w_(k) < x.  Integer counts and float compares only: no atomics on floats, no float sums --
+// the hit set is the same whatever order the waves run in.
+// r_i + 1 depends on (n, mask, train, guard, permille) alone: the host makes the table need[i] once per window (floor_window_ranks,
+// scn_host.hip: M_i from the mask, never from the values), 0 for a bin the mask removes, and the kernel reads 2 bytes per bin of it.
+//
+// Geometry (a TEAM of T threads per unit, persistent: teams walk units with the grid's stride), scn_floor.hip's:
+//   n <= 512          T = 64: a wave per unit, four units per 256-thread workgroup, wave barriers only
+//   n <= 4096         T = 256, above: T = 1024: a workgroup per unit
+// Per unit and TILE of CAP = 4 T RUNS consecutive fftshift indices (one tile up to 16384 points, four at 65536), the team stages
+//   w[i] = evaluated ? fl(power_db + threshold) : +inf      (+inf is below nothing: a bin that is not a cell counts for nothing)
+// into LDS in fftshift order, with a halo of 192 = SCN_FLOOR_TRAIN_MAX + SCN_FLOOR_GUARD_MAX slots on either side -- the
+// neighbouring tiles' bins, re-read from L2, or +inf beyond the band's edges: there is no wrap.  A thread owns RUNS runs of 4
+// consecutive bins, run r at 4 (r T + t): it keeps their raw values in registers from the staging loads (for the compare and the
+// record), its LDS stores and loads are 16 bytes at 16-byte lane stride (full rate, no bank conflict), and the windows of the four
+// bins of a run share their reads: a 16-byte chunk of cells is read once and held against all four.  Whether cell e of chunk q
+// belongs to bin k's window depends on 4 q + e - k, guard and train only -- the same in every lane, so the membership tests are
+// scalar, and a chunk that lies inside all four windows (most of them once train >= 8) takes 16 compare-and-count pairs straight.
+// Hit pass: scn_floor.hip's -- the wave counts its hits (ballots), takes that many slots of the unit's region with one LDS atomic,
+// and its lanes store their records at ballot-prefix positions through a buffer descriptor of exactly the region (hit_region = M
+// records: it cannot overflow); the loads go through descriptors of exactly the unit's spectrum and the table.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/scanner_hip.h"
+#include "scn_device.h"
+
+namespace {
+
+constexpr uint32_t kHalo = SCN_FLOOR_TRAIN_MAX + SCN_FLOOR_GUARD_MAX;  // slots on either side of a tile (a multiple of 4)
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+template <int T>
+__device__ __forceinline__ void team_sync() {
+  if constexpr (T == 64) {  // a wave: its LDS operations complete in order
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    __syncthreads();
+  }
+}
+
+template <int T, int RUNS>
+struct LocalGeo {
+  static constexpr uint32_t BLOCK = T == 64 ? 256u : (uint32_t)T, TEAMS = BLOCK / (uint32_t)T;
+  static constexpr uint32_t CAP = 4u * (uint32_t)T * (uint32_t)RUNS;  // bins per tile
+  static constexpr uint32_t SLOTS = CAP + 2u * kHalo;                 // floats of LDS per team
+  static constexpr uint32_t LDS_BYTES = TEAMS * SLOTS * 4u + TEAMS * 4u;
+};
+
+template <int T, int RUNS>
+__global__ __launch_bounds__(T == 64 ? 256 : T) void scn_floor_local_kernel(ScnFloorLocalArgs a) {
+  typedef LocalGeo<T, RUNS> G;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const uint32_t t = threadIdx.x % T, team = threadIdx.x / T, lane = threadIdx.x & 63u;
+  float *const s_w = reinterpret_cast<float *>(smem_raw) + team * G::SLOTS + kHalo;  // s_w[il]: the tile's bin il, -kHalo <= il < CAP + kHalo
+  uint32_t *const s_count = reinterpret_cast<uint32_t *>(smem_raw + G::TEAMS * G::SLOTS * 4u) + team;
+  const uint32_t n = a.n, half = n / 2u;
+  const int guard = (int)a.guard, train = (int)a.train, reach = guard + train;
+  const float inf = __builtin_inff();
+  const __amdgpu_buffer_rsrc_t rneed = make_rsrc(a.need, ((n + 3u) & ~3u) * 2u);
+  for (uint32_t u0 = blockIdx.x * G::TEAMS + team; u0 < a.n_units; u0 += gridDim.x * G::TEAMS) {
+    const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)u0);  // (the same in every lane of a wave)
+    const __amdgpu_buffer_rsrc_t rin = make_rsrc(a.power_db + (size_t)u * n, n * 4u);
+    const __amdgpu_buffer_rsrc_t rhit = make_rsrc(a.hits + (size_t)u * a.hit_region, a.hit_region * (uint32_t)sizeof(ScnDevHit));
+    // the bin at fftshift index i (which may lie outside the band): its value's bits, and whether it is a cell
+    auto cell = [&](int i, uint32_t &bits) -> bool {
+      const bool inside = (uint32_t)i < n;
+      uint32_t j = (inside ? (uint32_t)i : 0u) + half;  // j = (i + n / 2) % n (process.cpp:47)
+      j = j >= n ? j - n : j;
+      bits = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rin, j * 4u, 0, 0);
+      return inside && scn_bin_evaluated(j, (uint32_t)i, n, a);
+    };
+    if (t == 0) *s_count = 0u;
+    for (uint32_t tile0 = 0; tile0 < n; tile0 += G::CAP) {
+      uint32_t x[RUNS][4];
+#pragma unroll
+      for (int r = 0; r < RUNS; r++) {
+        const uint32_t il0 = 4u * ((uint32_t)r * T + t);
+        f4 w;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          const bool ok = cell((int)(tile0 + il0) + e, x[r][e]);
+          w[e] = ok ? __uint_as_float(x[r][e]) + a.threshold : inf;
+        }
+        *reinterpret_cast<f4 *>(s_w + il0) = w;
+      }
+      for (uint32_t h = t; h < 2u * kHalo; h += T) {
+        const int il = h < kHalo ? (int)h - (int)kHalo : (int)(G::CAP + h - kHalo);
+        uint32_t bits;
+        const bool ok = cell((int)tile0 + il, bits);
+        s_w[il] = ok ? __uint_as_float(bits) + a.threshold : inf;
+      }
+      team_sync<T>();
+      uint32_t hm = 0;  // bit 4 r + k: bin k of run r is a hit
+#pragma unroll
+      for (int r = 0; r < RUNS; r++) {
+        const uint32_t il0 = 4u * ((uint32_t)r * T + t);
+        typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+        // (beyond the table -- the band's end inside the last tile -- the descriptor returns 0: not evaluated)
+        const u2 nd = __builtin_bit_cast(u2, __builtin_amdgcn_raw_buffer_load_b64(rneed, (tile0 + il0) * 2u, 0, 0));
+        if (!__ballot((nd.x | nd.y) != 0u)) continue;  // a wave whose runs the mask removes altogether (outside the band)
+        const uint32_t need[4] = {nd.x & 0xffffu, nd.x >> 16, nd.y & 0xffffu, nd.y >> 16};
+        const float xf[4] = {__uint_as_float(x[r][0]), __uint_as_float(x[r][1]), __uint_as_float(x[r][2]), __uint_as_float(x[r][3])};
+        uint32_t cnt[4] = {0u, 0u, 0u, 0u};
+        const float *const base = s_w + il0;
+        // chunk q: the four cells 4 q ... 4 q + 3 bins from the run's first bin; cell e lies d = 4 q + e - k from bin k
+        auto chunk = [&](int q) {
+          const f4 w = *reinterpret_cast<const f4 *>(base + 4 * q);
+          const int lo = 4 * q - 3, hi = 4 * q + 3;
+          if ((hi < -guard && lo >= -reach) || (lo > guard && hi <= reach)) {  // inside all four windows
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+#pragma unroll
+              for (int k = 0; k < 4; k++) cnt[k] += w[e] < xf[k] ? 1u : 0u;
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+#pragma unroll
+              for (int k = 0; k < 4; k++) {
+                const int d = 4 * q + e - k, ad = d < 0 ? -d : d;
+                const bool in = (uint32_t)(ad - guard - 1) < (uint32_t)train;  // guard < |d| <= guard + train
+                cnt[k] += (in && w[e] < xf[k]) ? 1u : 0u;
+              }
+          }
+        };
+        // the windows below the run reach from -reach to 2 - guard, those above it from guard + 1 to 3 + reach
+        const int l0 = (-reach) >> 2, l1 = (2 - guard) >> 2, r0 = (guard + 1) >> 2, r1 = (3 + reach) >> 2;
+        for (int q = l0; q <= l1; q++) chunk(q);
+        for (int q = r0 > l1 ? r0 : l1 + 1; q <= r1; q++) chunk(q);
+#pragma unroll
+        for (int k = 0; k < 4; k++) hm |= (need[k] != 0u && cnt[k] >= need[k]) ? 1u << (4 * r + k) : 0u;
+      }
+      // the hit pass: the wave's total first, one slot grab, then the records at ballot-prefix positions
+      uint32_t total = 0;
+#pragma unroll
+      for (int b = 0; b < 4 * RUNS; b++) total += (uint32_t)__popcll(__ballot((hm >> b) & 1u));
+      if (total) {
+        uint32_t slot = 0;
+        if (lane == 0) slot = atomicAdd(s_count, total);
+        slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot);
+        const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+        for (int b = 0; b < 4 * RUNS; b++) {
+          const bool hit = (hm >> b) & 1u;
+          const unsigned long long m = __ballot(hit);
+          const uint32_t pos = slot + (uint32_t)__popcll(m & below);
+          const uint32_t i = tile0 + 4u * ((uint32_t)(b / 4) * T + t) + (uint32_t)(b % 4);
+          typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+          // (a lane without a hit stores outside the descriptor: dropped)
+          __builtin_amdgcn_raw_buffer_store_b64(u2{i, x[b / 4][b % 4]}, rhit, hit ? pos * (uint32_t)sizeof(ScnDevHit) : 0x80000000u, 0, 0);
+          slot += (uint32_t)__popcll(m);
+        }
+      }
+      team_sync<T>();  // every wave is done with the tile's cells, and its grab is in s_count
+    }
+    if (t == 0) a.counts[u] = *s_count;
+    team_sync<T>();  // (s_count is zeroed again for the team's next unit)
+  }
+}
+
+template <int T, int RUNS>
+hipError_t launch(const ScnFloorLocalArgs &a, int num_cus, hipStream_t stream) {
+  typedef LocalGeo<T, RUNS> G;
+  if (G::LDS_BYTES > 65536u) {  // the opt-in for more than 64 KiB of dynamic LDS: per function and per device, so set on every launch
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(scn_floor_local_kernel<T, RUNS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)G::LDS_BYTES);
+    if (e != hipSuccess) return e;
+  }
+  // persistent teams: as many workgroups as the runtime says are resident at once for this instantiation's registers and LDS
+  // (asked once per instantiation; the fallback should the query fail: what its LDS alone allows, at most 8 of 256 threads or 2 of
+  // 1024 per CU); no more workgroups than there are units to walk.  The workgroups share nothing: the grid's size is a matter of
+  // speed only.
+  static int per_cu = 0;  // (plans of several threads may race to the same answer)
+  if (per_cu <= 0) {
+    int q = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, scn_floor_local_kernel<T, RUNS>, (int)G::BLOCK, G::LDS_BYTES) != hipSuccess || q <= 0) {
+      (void)hipGetLastError();
+      q = (int)std::min<uint32_t>(G::BLOCK == 256u ? 8u : 2u, std::max<uint32_t>(1u, 163840u / G::LDS_BYTES));
+    }
+    per_cu = q;
+  }
+  const uint32_t resident = (uint32_t)(num_cus > 0 ? num_cus : 256) * (uint32_t)per_cu;
+  uint32_t blocks = (a.n_units + G::TEAMS - 1u) / G::TEAMS;
+  if (blocks > resident) blocks = resident;
+  hipLaunchKernelGGL((scn_floor_local_kernel<T, RUNS>), dim3(blocks), dim3(G::BLOCK), G::LDS_BYTES, stream, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t scn_launch_floor_local(const ScnFloorLocalArgs &a, int num_cus, hipStream_t stream) {
+  if (a.n_units == 0) return hipSuccess;
+  if (a.n == 0 || a.n > 65536u || a.hit_region == 0 || a.train == 0 || a.train > SCN_FLOOR_TRAIN_MAX || a.guard > SCN_FLOOR_GUARD_MAX ||
+      !a.power_db || !a.hits || !a.counts || !a.need)
+    return hipErrorInvalidValue;
+  const uint32_t n = a.n;
+  if (n <= 256u) return launch<64, 1>(a, num_cus, stream);
+  if (n <= 512u) return launch<64, 2>(a, num_cus, stream);
+  if (n <= 1024u) return launch<256, 1>(a, num_cus, stream);
+  if (n <= 4096u) return launch<256, 4>(a, num_cus, stream);
+  if (n <= 8192u) return launch<1024, 2>(a, num_cus, stream);
+  return launch<1024, 4>(a, num_cus, stream);  // (one tile up to 16384 points, ceil(n / 16384) above)
+}

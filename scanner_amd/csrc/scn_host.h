@@ -29,6 +29,11 @@ ScnBluesteinTables bluestein_tables(uint32_t n);
 
 bool floor_permille_of(uint32_t given, uint32_t *permille);
 uint32_t evaluated_bins(uint32_t n, uint32_t dc_ignore, double use_bandwidth, uint32_t *i_lo, uint32_t *i_hi);
+// The floor window (scanner_hip.h, "Floor window") on a mask with the defaults applied: need[i] = r_i + 1 -- the number of reference
+// cells that must lie below bin i for it to be a hit -- for every evaluated fftshift index i, 0 for the others.  SCN_E_INVALID (with
+// the error text set, `need` unspecified) for a window outside the limits or one that leaves an evaluated bin without a cell.
+int floor_window_ranks(uint32_t n, uint32_t dc_ignore, uint32_t i_lo, uint32_t i_hi, uint32_t permille, uint32_t train, uint32_t guard,
+                       std::vector<uint16_t> &need);
 
 // Averaged plans (k = average > 1; sweeps: SCN_AVG_SWEEPS, else SCN_AVG_DWELL).  group_headers redirects fc / seq to the groups'
 // (held in group_fc / group_seq) where the submit gave them or the compaction kernel's default would be wrong; returns the groups

@@ -166,6 +166,33 @@ uint32_t evaluated_bins(uint32_t n, uint32_t dc_ignore, double use_bandwidth, ui
   return kept;
 }
 
+int floor_window_ranks(uint32_t n, uint32_t dc_ignore, uint32_t i_lo, uint32_t i_hi, uint32_t permille, uint32_t train, uint32_t guard,
+                       std::vector<uint16_t> &need) {
+  if (train == 0 || train > SCN_FLOOR_TRAIN_MAX)
+    return scn_fail(SCN_E_INVALID, "floor window: train_bins %u outside 1 ... %u", train, SCN_FLOOR_TRAIN_MAX);
+  if (guard > SCN_FLOOR_GUARD_MAX) return scn_fail(SCN_E_INVALID, "floor window: guard_bins %u > %u", guard, SCN_FLOOR_GUARD_MAX);
+  const struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {dc_ignore, i_lo, i_hi};
+  std::vector<uint32_t> before((size_t)n + 1u);  // before[i] = evaluated bins among the fftshift indices [0, i)
+  before[0] = 0;
+  for (uint32_t i = 0; i < n; i++) before[i + 1] = before[i] + (scn_bin_evaluated((i + n / 2) % n, i, n, mask) ? 1u : 0u);
+  // evaluated bins in [lo, hi] clipped to [0, n): no wrap between the band edges
+  auto cells = [&](int64_t lo, int64_t hi) -> uint32_t {
+    lo = std::max<int64_t>(lo, 0);
+    hi = std::min<int64_t>(hi, (int64_t)n - 1);
+    return lo > hi ? 0u : before[(size_t)hi + 1u] - before[(size_t)lo];
+  };
+  need.assign(n, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    if (before[i + 1] == before[i]) continue;
+    const int64_t c = i, reach = (int64_t)guard + train;
+    const uint32_t m = cells(c - reach, c - guard - 1) + cells(c + guard + 1, c + reach);
+    if (!m)
+      return scn_fail(SCN_E_INVALID, "floor window (train %u, guard %u): the evaluated bin i = %u of %u has no reference cell", train, guard, i, n);
+    need[i] = (uint16_t)((uint64_t)permille * (m - 1u) / 1000u + 1u);  // (m <= 2 SCN_FLOOR_TRAIN_MAX)
+  }
+  return SCN_OK;
+}
+
 // Averaged plans: a submit's arguments alone decide whether it can run -- checked before any copy or kernel is queued
 int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc) {
   if (nb % k) return scn_fail(SCN_E_INVALID, "n_buffers %u is not a multiple of average %u", nb, k);
@@ -283,6 +310,53 @@ int scn_floor_from_spectrum(const float *power_db, uint32_t n, uint32_t dc_ignor
   std::nth_element(keys.begin(), keys.begin() + (ptrdiff_t)r, keys.end());
   const uint32_t key = keys[r], bits = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;
   memcpy(floor_db, &bits, sizeof(bits));
+  return SCN_OK;
+}
+
+int scn_local_floor_from_spectrum(const float *power_db, uint32_t n, uint32_t dc_ignore_bins, double use_bandwidth, uint32_t floor_permille,
+                                  uint32_t train_bins, uint32_t guard_bins, float *floor_db) {
+  if (!power_db || !floor_db) return scn_fail(SCN_E_INVALID, "null argument");
+  if (n == 0 || n > (1u << 24)) return scn_fail(SCN_E_INVALID, "bad bin count %u", n);
+  uint32_t permille = 0;
+  if (!floor_permille_of(floor_permille, &permille))
+    return scn_fail(SCN_E_INVALID, "floor_permille %u: 0 (the median), 1 ... 1000 or SCN_FLOOR_MIN", floor_permille);
+  struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {dc_ignore_bins ? dc_ignore_bins : 4u, 0, 0};  // the descriptor's defaults (scn_plan_create)
+  if (mask.dc_ignore == SCN_DC_IGNORE_NONE) mask.dc_ignore = 0;
+  if (!evaluated_bins(n, mask.dc_ignore, use_bandwidth == 0.0 ? 0.75 : use_bandwidth, &mask.i_lo, &mask.i_hi))
+    return scn_fail(SCN_E_INVALID, "the mask (dc_ignore_bins, use_bandwidth) lets no bin through");
+  if (!train_bins && !guard_bins) {  // no window: the unit-wide floor
+    float unit_floor;
+    if (int st = scn_floor_from_spectrum(power_db, n, dc_ignore_bins, use_bandwidth, floor_permille, &unit_floor)) return st;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t j = (i + n / 2) % n;
+      if (scn_bin_evaluated(j, i, n, mask)) floor_db[j] = unit_floor;
+    }
+    return SCN_OK;
+  }
+  std::vector<uint16_t> need;
+  if (int st = floor_window_ranks(n, mask.dc_ignore, mask.i_lo, mask.i_hi, permille, train_bins, guard_bins, need)) return st;
+  std::vector<uint32_t> keys(n);  // in fftshift order (read before anything is written: floor_db may be power_db)
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t bits;
+    memcpy(&bits, power_db + (i + n / 2) % n, sizeof(bits));
+    keys[i] = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+  }
+  uint32_t cells[2u * SCN_FLOOR_TRAIN_MAX];
+  const int64_t reach = (int64_t)guard_bins + train_bins;
+  for (uint32_t i = 0; i < n; i++) {
+    if (!need[i]) continue;
+    uint32_t m = 0;
+    auto take = [&](int64_t lo, int64_t hi) {  // the evaluated bins of [lo, hi], clipped to the band: no wrap
+      for (int64_t c = std::max<int64_t>(lo, 0); c <= std::min<int64_t>(hi, (int64_t)n - 1); c++)
+        if (need[(size_t)c]) cells[m++] = keys[(size_t)c];
+    };
+    take((int64_t)i - reach, (int64_t)i - guard_bins - 1);
+    take((int64_t)i + guard_bins + 1, (int64_t)i + reach);
+    const uint32_t r = need[i] - 1u;  // < m
+    std::nth_element(cells, cells + r, cells + m);
+    const uint32_t key = cells[r], bits = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;
+    memcpy(floor_db + (i + n / 2) % n, &bits, sizeof(bits));
+  }
   return SCN_OK;
 }
 

@@ -150,6 +150,23 @@ struct ScnFloorArgs {
 };
 hipError_t scn_launch_floor(const ScnFloorArgs &args, int num_cus, hipStream_t stream);
 
+// The floor detector with a floor window (scn_floor_local.hip, scn_plan_set_floor_window): the same place behind the transform, the
+// same regions and counts; bin i of a unit is a hit iff at least need[i] of its reference cells c have c + threshold < power_db --
+// the order-statistic cut without a selection.  Every unit's count is written (nothing to zero beforehand); there is no per-unit floor.
+struct ScnFloorLocalArgs {
+  const float *power_db;      // [n_units][n], natural bin order
+  uint32_t n, n_units;
+  uint32_t train, guard;      // 1 <= train <= SCN_FLOOR_TRAIN_MAX, guard <= SCN_FLOOR_GUARD_MAX
+  uint32_t permille;          // what `need` was made with (floor_window_ranks); the kernel reads the table
+  const uint16_t *need;       // [n] by fftshift index i: r_i + 1 for an evaluated bin, 0 for the others (device memory, per plan)
+  float threshold;            // the offset above the floor, in the plan's dB scale
+  uint32_t dc_ignore, i_lo, i_hi;
+  ScnDevHit *hits;            // [n_units][hit_region]
+  uint32_t hit_region;        // = the number of evaluated bins M
+  uint32_t *counts;           // [n_units]
+};
+hipError_t scn_launch_floor_local(const ScnFloorLocalArgs &args, int num_cus, hipStream_t stream);
+
 // The same path for the sizes without a fused or four-step kernel (scn_generic.hip): Bluestein, through HBM, stage by stage
 struct ScnGenericArgs {
   const void *raw;            // n_buffers raw buffers back to back

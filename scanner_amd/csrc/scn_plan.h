@@ -84,6 +84,7 @@ struct Slot {
   // its collect has waited for `done` --, and h_floor is promised only until the slot's next submit.
   ScnDeviceMem<float> d_floor;      // [max_batch]
   ScnPinnedMem<float> h_floor;      // [max_batch]
+  bool floor_windowed = false;      // the pending / last submit ran under a floor window: it has no per-unit floor (scn_collect_floor)
   ScnDeviceMem<float> d_floor_power;  // [max_batch][N] the spectrum the detect kernel reads when the caller keeps none (hits-only floor plans)
   ScnEvent done;
   bool pending = false;
@@ -128,6 +129,11 @@ struct scn_plan {
   uint32_t avg = 1, avg_layout = SCN_AVG_DWELL;  // scn_plan_desc.average / average_layout with the defaults applied
   bool floor = false;       // scn_plan_desc.detect == SCN_DETECT_FLOOR: the transform stores the spectrum only, scn_floor.hip detects on it
   uint32_t floor_rank = 0;  // ... and the floor is the value of this rank among the hit_region evaluated bins
+  uint32_t floor_permille = 0;  // ... (floor_permille with its default applied: what a floor window's ranks are made from)
+  // the floor window (scn_plan_set_floor_window, scn_floor_local.hip): train 0 = none, the unit-wide floor above; with one, the
+  // table r_i + 1 by fftshift index (floor_window_ranks), padded with zeros to a multiple of 4 entries
+  uint32_t floor_train = 0, floor_guard = 0;
+  ScnDeviceMem<uint16_t> d_floor_need;
   uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
   ScnDeviceMem<double> d_twiddle64;  // four-step: [256][2] W_256^k; Bluestein: [fft_m][2] W_m^k; in double
   ScnDeviceMem<double> d_table;      // the plan's frequency table (scn_plan_set_table), read by the compaction kernel; grown on demand

@@ -209,6 +209,7 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   p->hit_region = std::max<uint32_t>(kept, 1u);
   p->floor = d.detect == SCN_DETECT_FLOOR;
   if (p->floor) p->floor_rank = (uint32_t)((uint64_t)floor_permille * (kept - 1u) / 1000u);
+  p->floor_permille = floor_permille;
   build_window(d.window_type, d.n, p->h_window);
 
   hipDeviceProp_t prop;

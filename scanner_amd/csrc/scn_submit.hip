@@ -133,6 +133,26 @@ int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float
 
 // Floor plans: the detect kernel on the spectrum the transform has just stored, behind it on the slot's stream; nu units
 int launch_floor(scn_plan *p, Slot &s, const float *d_power, uint32_t nu) {
+  if (p->floor_train) {  // a floor window: every bin against the rank among its own reference cells (scn_floor_local.hip)
+    ScnFloorLocalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.power_db = d_power;
+    a.n = p->d.n;
+    a.n_units = nu;
+    a.train = p->floor_train;
+    a.guard = p->floor_guard;
+    a.permille = p->floor_permille;
+    a.need = p->d_floor_need.get();
+    a.threshold = p->d.threshold;
+    a.dc_ignore = p->d.dc_ignore_bins;
+    a.i_lo = p->i_lo;
+    a.i_hi = p->i_hi;
+    a.hits = s.d_hits[s.gen].get();
+    a.hit_region = p->hit_region;
+    a.counts = s.d_buf_hits[s.gen].get();
+    SCN_HIP(scn_launch_floor_local(a, p->num_cus, s.stream));
+    return SCN_OK;
+  }
   ScnFloorArgs a;
   memset(&a, 0, sizeof(a));
   a.power_db = d_power;
@@ -189,6 +209,7 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
     d_power = s.d_floor_power.get();
   }
   s.n_buffers = nb;
+  s.floor_windowed = p->floor && p->floor_train != 0u;
   s.list_valid = false;
   const bool hits = (p->d.flags & SCN_OUT_HITS) != 0;
   s.list_built = false;
@@ -270,7 +291,8 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
     } else if (!direct) {
       SCN_HIP(hipMemcpyAsync(s.h_buf_hits.get(), s.d_buf_hits[s.gen].get(), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, cnt));
     }
-    if (p->floor) SCN_HIP(hipMemcpyAsync(s.h_floor.get(), s.d_floor.get(), sizeof(float) * nb, hipMemcpyDeviceToHost, cnt));  // the way the counts go
+    // (the way the counts go; a windowed submit has no per-unit floor)
+    if (p->floor && !s.floor_windowed) SCN_HIP(hipMemcpyAsync(s.h_floor.get(), s.d_floor.get(), sizeof(float) * nb, hipMemcpyDeviceToHost, cnt));
     if (!(after_is_done && after)) SCN_HIP(hipEventRecord(s.done.get(), cnt));
     if (eager) {
       int st2 = build_list(p, s, p->records_wanted);  // (the prefetch to pinned memory only for a caller that reads the records on the host)
@@ -375,6 +397,27 @@ int scn_plan_set_table(scn_plan *p, const double *fc, uint32_t count) {
   SCN_HIP(hipMemcpyAsync(p->d_table.get(), fc, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, p->list_stream.get()));
   SCN_HIP(hipStreamSynchronize(p->list_stream.get()));  // (fc is the caller's: done with it before returning; the list kernels run on this stream, after the copy)
   p->table_count = count;
+  return SCN_OK;
+}
+
+int scn_plan_set_floor_window(scn_plan *p, uint32_t train, uint32_t guard) {
+  if (!p) return scn_fail(SCN_E_INVALID, "null plan");
+  if (!p->floor) return scn_fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_FLOOR");
+  for (int i = 0; i < SCN_NUM_SLOTS; i++)
+    if (p->slot[i].pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit", i);
+  if (!train && !guard) {  // back to the unit-wide floor (collected slots keep their lists: nothing of theirs reads the table)
+    p->floor_train = p->floor_guard = 0;
+    return SCN_OK;
+  }
+  std::vector<uint16_t> need;
+  if (int st = floor_window_ranks(p->d.n, p->d.dc_ignore_bins, p->i_lo, p->i_hi, p->floor_permille, train, guard, need)) return st;
+  need.resize(((size_t)p->d.n + 3u) & ~(size_t)3u, 0);  // (whole 8-byte reads: ScnFloorLocalArgs::need)
+  SCN_HIP(hipSetDevice(p->d.device_id));
+  // (no slot is pending, and a slot's detect kernel is complete when its `done` is: nothing reads the old table any more)
+  SCN_HIP(p->d_floor_need.alloc(need.size()));
+  SCN_HIP(hipMemcpy(p->d_floor_need.get(), need.data(), sizeof(uint16_t) * need.size(), hipMemcpyHostToDevice));
+  p->floor_train = train;
+  p->floor_guard = guard;
   return SCN_OK;
 }
 

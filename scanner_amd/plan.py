@@ -16,8 +16,10 @@ class Plan:
                  correct_dc=False, max_batch=1, use_bandwidth=0.75, dc_ignore_bins=4, trigger_count=1047,
                  max_hits=0, flags=capi.OUT_SPECTRUM | capi.OUT_HITS, device_id=0,
                  window_type=capi.WIN_BLACKMAN_HARRIS, mode=capi.MODE_FREQUENCY_DOMAIN, average=1,
-                 average_layout=capi.AVG_DWELL, detect=capi.DETECT_FIXED, floor_permille=0):
-        """detect = capi.DETECT_FLOOR: a bin is a hit when it exceeds its own unit's floor -- the value of rank floor_permille
+                 average_layout=capi.AVG_DWELL, detect=capi.DETECT_FIXED, floor_permille=0, floor_window=None):
+        """floor_window = (train, guard), floor plans only: each bin's floor is the rank among its own reference cells, the evaluated
+        bins guard < |i' - i| <= guard + train away (set_floor_window; scanner_hip.h, "Floor window").
+        detect = capi.DETECT_FLOOR: a bin is a hit when it exceeds its own unit's floor -- the value of rank floor_permille
         (0: the median, capi.FLOOR_MIN: the minimum, 1000: the maximum) among the unit's evaluated bins -- by more than
         `threshold`, then an offset in the plan's dB scale; collect_floor returns the floors (scanner_hip.h, "Floor detector").
         average = K > 1: every K buffers of a submit form a group (average_layout: capi.AVG_DWELL, buffers gK ... gK+K-1,
@@ -56,6 +58,12 @@ class Plan:
         self._keep = [None] * capi.NUM_SLOTS
         self._submit_device, self._collect, self._n_hits = self._L.scn_submit_device, self._L.scn_collect, C.c_uint32()
         self._submit_device_indexed = self._L.scn_submit_device_indexed
+        if floor_window is not None:
+            try:
+                self.set_floor_window(*floor_window)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifetime -----------------------------------------------------------
     @property
@@ -110,6 +118,12 @@ class Plan:
         submit with `first_index` then tags buffer b with entry (first_index + b) % len(table) and sends no per-buffer centres."""
         fc = np.ascontiguousarray(center_freqs, np.float64).reshape(-1)
         capi.check(self._L.scn_plan_set_table(self._h, fc.ctypes.data_as(C.c_void_p), fc.size), "scn_plan_set_table")
+
+    def set_floor_window(self, train, guard=0):
+        """scn_plan_set_floor_window: from the next submit on every bin is held against the floor of its own neighbourhood --
+        `train` evaluated-or-masked bins on either side beyond `guard` bins, the masked ones taking up distance only.  (0, 0)
+        returns to the unit-wide floor.  Not while a slot is pending; a windowed slot has no collect_floor."""
+        capi.check(self._L.scn_plan_set_floor_window(self._h, int(train), int(guard)), "scn_plan_set_floor_window")
 
     def submit(self, slot, n_buffers, center_freqs=None, seq_ids=None, first_index=None):
         """Process the first n_buffers raw buffers of the pinned slot (async)."""
@@ -258,7 +272,8 @@ class Plan:
 
     def collect_floor(self, slot):
         """scn_collect_floor: floor_db float32[B] of the slot's last collected submit, one per buffer (per group on an averaged
-        plan).  Floor-detector plans only (detect=capi.DETECT_FLOOR)."""
+        plan).  Floor-detector plans only (detect=capi.DETECT_FLOOR); a slot submitted under a floor window has no per-unit floor and
+        raises ScannerError(E_INVALID), as the library does."""
         out = np.empty(self._nb[slot] // self.average, np.float32)
         capi.check(self._L.scn_collect_floor(self._h, slot, out.ctypes.data_as(C.c_void_p)), "scn_collect_floor")
         return out

@@ -1,5 +1,5 @@
-"""What the floor detector costs (scn_plan_desc.detect = SCN_DETECT_FLOOR, scn_floor.hip) beside the fixed-threshold plan of the
-same build, in the same loop.
+"""What the floor detector costs (scn_plan_desc.detect = SCN_DETECT_FLOOR, scn_floor.hip; with a floor window: scn_floor_local.hip)
+beside the fixed-threshold plan of the same build, in the same loop.
 
     python scripts/floor_bench.py [--json OUT] [--steps 60]
 
@@ -9,12 +9,16 @@ Shapes (inputs: synth.cfloat_batch_torch, seed 2, quantised for the integer kind
   small     262144 x 128 cfloat  fixed and floor, spectrum + hits
 The fixed plan's threshold is the bench's 10 dB (the other shapes: 8 above their spectrum's median); the floor plan's offset is that
 threshold less the median of the shape's spectrum, so both cut at about the same level and report about as many hits.
+Every shape also runs the floor plan under the floor windows (16, 2) and (128, 64) (scn_plan_set_floor_window; rows floor_w16_2 and
+floor_w128_64, same offset) where the window is valid -- at 128 points (128, 64) leaves bins without a reference cell and has no row.
 Per row:
   step_us       us per step of a two-slot loop (submit slot k, collect the counts of slot k ^ 1), host clock over `steps` steps;
                 the plans of a shape take turns, round by round, and the median of the rounds is reported
   over_fixed    step_us / the fixed plan's step_us of the same shape
-  detect_us     scn_floor_kernel alone: begin-to-end time of its dispatches from a kernel trace (rocprofv3 --kernel-trace) of a
-                second run of the same workload (median); the step figures come from the run WITHOUT the profiler
+  detect_us     the detect kernel alone (scn_floor_kernel, or scn_floor_local_kernel under a window): begin-to-end time of its
+                dispatches from a kernel trace (rocprofv3 --kernel-trace) of a second run of the same workload (median); the step
+                figures come from the run WITHOUT the profiler
+  over_unit_wide  windowed rows: detect_us / the detect_us of the shape's unit-wide `floor` row
 Each row carries the build hash (scanner_amd.build.source_hash)."""
 import argparse
 import csv
@@ -36,6 +40,7 @@ from scanner_amd import Plan, build, capi, synth  # noqa: E402
 FS = 8000000
 BOTH = capi.OUT_SPECTRUM | capi.OUT_HITS
 SHAPES = (("c2", 4096, 8192, capi.KIND_FLOAT_COMPLEX), ("int16", 8192, 4096, capi.KIND_SHORT_COMPLEX), ("small", 128, 262144, capi.KIND_FLOAT_COMPLEX))
+WINDOWS = ((16, 2), (128, 64))
 ROUNDS, WARM = 5, 8
 
 
@@ -79,6 +84,12 @@ def child(steps):
         if shape == "c2":
             plans.append(("floor_hits_only", dict(flags=capi.OUT_HITS, detect=capi.DETECT_FLOOR), offset))
         open_plans = [(name, Plan(n, FS, t, **k, **kw)) for name, k, t in plans]
+        for train, guard in WINDOWS:
+            try:
+                open_plans.append((f"floor_w{train}_{guard}", Plan(n, FS, offset, flags=BOTH, detect=capi.DETECT_FLOOR, floor_window=(train, guard), **kw)))
+            except capi.ScannerError as e:  # (a window that leaves an evaluated bin of this size without a cell)
+                if e.status != capi.E_INVALID:
+                    raise
         us = {name: [] for name, _ in open_plans}
         hits = {}
         for _ in range(ROUNDS):
@@ -115,7 +126,7 @@ def main():
         t = []
         for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
             for r in csv.DictReader(open(f)):
-                if "scn_floor_kernel" in r["Kernel_Name"]:
+                if "scn_floor_kernel" in r["Kernel_Name"] or "scn_floor_local_kernel" in r["Kernel_Name"]:
                     t.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
     finally:
         shutil.rmtree(trace_dir, ignore_errors=True)
@@ -132,6 +143,10 @@ def main():
         for r in floor_rows:
             assert len(d[r["plan"]]) == ROUNDS * per, (shape, r["plan"], len(d[r["plan"]]))
             r["detect_us"] = round(float(np.median(d[r["plan"]])) / 1e3, 2)
+        unit_wide = next(r["detect_us"] for r in floor_rows if r["plan"] == "floor")
+        for r in floor_rows:
+            if r["plan"].startswith("floor_w"):
+                r["over_unit_wide"] = round(r["detect_us"] / unit_wide, 2)
     assert pos == len(t), (pos, len(t))
     for r in rows:
         r["build"] = build.source_hash()
