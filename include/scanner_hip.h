@@ -44,7 +44,9 @@ extern "C" {
                              size, zero = the fixed threshold), SCN_DETECT_*, SCN_FLOOR_MIN, scn_collect_floor,
                              scn_floor_from_spectrum;
                              still 6 (additions only): the floor window -- SCN_FLOOR_TRAIN_MAX, SCN_FLOOR_GUARD_MAX,
-                             scn_plan_set_floor_window, scn_local_floor_from_spectrum */
+                             scn_plan_set_floor_window, scn_local_floor_from_spectrum;
+                             still 6 (additions only): the baseline detector -- SCN_DETECT_BASELINE, SCN_BASELINE_*,
+                             scn_plan_set_baseline, scn_plan_update_baseline, scn_plan_get_baseline */
 
 /* status codes */
 enum {
@@ -178,7 +180,8 @@ enum {
  * scn_hits_view, scn_collect_signals and the gathers work as on any plan.  scn_collect_floor returns floor_db. */
 enum {
   SCN_DETECT_FIXED = 0, /* power_db > threshold, one level for every unit */
-  SCN_DETECT_FLOOR = 1  /* power_db > floor_db[unit] + threshold */
+  SCN_DETECT_FLOOR = 1, /* power_db > floor_db[unit] + threshold */
+  SCN_DETECT_BASELINE = 2 /* power_db > baseline_db[row of the unit][bin] + threshold (below) */
 };
 #define SCN_FLOOR_MIN 0xffffffffu /* floor_permille: rank 0, the minimum (0 itself asks for the default, as SCN_DC_IGNORE_NONE) */
 
@@ -202,6 +205,31 @@ enum {
  * on the returned spectrum gives the per-bin floors. */
 #define SCN_FLOOR_TRAIN_MAX 128u
 #define SCN_FLOOR_GUARD_MAX 64u
+
+/* Baseline detector (detect = SCN_DETECT_BASELINE): hits are what exceeds a stored spectrum -- what is here now that was not here
+ * before.  A baseline plan owns baseline_db[rows][n]: float32, natural bin order, device memory; it has none at first
+ * (scn_plan_set_baseline).  A unit is a buffer (for an averaged plan: the group).
+ *   Row of a unit: unit u of a submit reads row (first + u) % rows, first = the submit's first_index for the indexed submits and 0
+ *     otherwise; on an averaged plan u counts groups, as the frequency table does.  An indexed submit needs rows == the table's
+ *     count or rows == 1, anything else is SCN_E_STATE; so is any submit on a plan that has no baseline.  Both are refused before
+ *     anything is queued.
+ *   Decision: an evaluated bin j (the mask of process.cpp:46-52, as everywhere) of unit u is a hit iff
+ *     power_db[u][j] > baseline_db[row][j] + threshold: ONE float addition and a strict compare; `threshold` is an offset in the
+ *     plan's own dB scale, as in floor mode.  So a NaN entry never produces a hit, nor does a +inf entry -- a caller's way to switch
+ *     one bin of one row off --, a -inf entry produces a hit for every bin above -inf, and a bin that is itself -inf is never a hit.
+ * No float is summed and nothing is selected: the hit list is exact, the same bits on every run and on every route.  Records, their
+ * power_db, freq_hz, seq_id, their order and trigger are those of a plan that cut bin j at that value.  Frequency-domain plans with
+ * SCN_OUT_HITS only (SCN_E_INVALID at create otherwise, before a device is looked for) -- and the flag is SET: a baseline plan names
+ * its outputs, flags without SCN_OUT_SPECTRUM and SCN_OUT_HITS (elsewhere: both) are SCN_E_INVALID; every size scn_size_path
+ * supports, and averaged plans; floor_permille is ignored.  The transform runs as the spectrum-only plan's does and one detect kernel, which only
+ * reads the baseline, follows it on the spectrum it stored (a hits-only plan keeps that spectrum in a buffer of its own);
+ * scn_collect_more, scn_hits_view, scn_collect_signals and the gathers work as on any plan; scn_collect_floor and
+ * scn_plan_set_floor_window are SCN_E_INVALID.  The baseline changes only through scn_plan_set_baseline and
+ * scn_plan_update_baseline, both refused while a submit is pending. */
+enum {
+  SCN_BASELINE_SET = 0, /* the row becomes the unit's spectrum, byte for byte */
+  SCN_BASELINE_MAX = 1  /* per bin the larger of the two in the floor detector's key order (max-hold): exact, whatever the order */
+};
 
 /* Signals (scn_collect_signals, scn_signals_from_hits): runs of nearby hits merged into one record each.  A plan's buffer is
  * its unit of output (for an averaged plan: the group).  The hits of one unit, in increasing i, are split into signals: a hit
@@ -352,6 +380,24 @@ SCN_API int scn_plan_set_floor_window(scn_plan *plan, uint32_t train_bins, uint3
  * held to.  Same rejections as scn_floor_from_spectrum, plus the window's. */
 SCN_API int scn_local_floor_from_spectrum(const float *power_db, uint32_t n, uint32_t dc_ignore_bins, double use_bandwidth,
                                           uint32_t floor_permille, uint32_t train_bins, uint32_t guard_bins, float *floor_db);
+
+/* Baseline plans only (SCN_E_INVALID otherwise).  Replaces the baseline with `rows` rows of n floats from host memory (natural bin
+ * order).  baseline_db == NULL with rows > 0 makes `rows` rows of +inf: armed, but nothing can hit -- where learning starts.
+ * rows == 0 drops the baseline.  SCN_E_STATE while any slot is pending.  Synchronous, like scn_plan_set_table, and waits for this
+ * plan's streams only. */
+SCN_API int scn_plan_set_baseline(scn_plan *plan, uint32_t rows, const float *baseline_db);
+
+/* Folds the spectrum of the slot's last COLLECTED submit -- the one its detect kernel read, all n bins of every unit, not only the
+ * evaluated ones -- into the rows of that submit's units, on the GPU: op = SCN_BASELINE_SET or SCN_BASELINE_MAX.  Needs units <=
+ * rows, so that no row is written twice in one call (SCN_E_INVALID otherwise, as an unknown op), no pending slot on the plan, and
+ * a slot submitted and collected since the plan was made (SCN_E_STATE otherwise).  Returns when the update is complete.  A submit
+ * that wrote its spectrum into the caller's d_power_db is read from there: the caller keeps that memory intact until this call
+ * has returned. */
+SCN_API int scn_plan_update_baseline(scn_plan *plan, int slot, uint32_t op);
+
+/* Copies rows [first_row, first_row + rows) of the baseline to out (host, rows * n floats): what a caller stores to keep a learnt
+ * baseline across runs.  A range outside the baseline is SCN_E_INVALID. */
+SCN_API int scn_plan_get_baseline(scn_plan *plan, uint32_t first_row, uint32_t rows, float *out);
 
 /* Time-domain plans (mode = SCN_MODE_TIME_DOMAIN; ProcessSamples::DoTimeDomainThresholding,
  * process.cpp:203-237): wait for the slot's submit and fetch, per buffer, the maximum and

@@ -23,7 +23,8 @@ DC_IGNORE_NONE = 0xFFFFFFFF
 NUM_SLOTS = 4
 ABI_VERSION = 6
 AVG_DWELL, AVG_SWEEPS = 0, 1  # scn_plan_desc.average_layout
-DETECT_FIXED, DETECT_FLOOR = 0, 1  # scn_plan_desc.detect
+DETECT_FIXED, DETECT_FLOOR, DETECT_BASELINE = 0, 1, 2  # scn_plan_desc.detect
+BASELINE_SET, BASELINE_MAX = 0, 1  # scn_plan_update_baseline's op
 FLOOR_MIN = 0xFFFFFFFF  # scn_plan_desc.floor_permille: rank 0 (0 itself asks for the default, the median)
 FLOOR_TRAIN_MAX, FLOOR_GUARD_MAX = 128, 64  # the floor window's limits (scn_plan_set_floor_window)
 PATH_UNSUPPORTED, PATH_FUSED, PATH_FOUR_STEP, PATH_STAGED, PATH_BLUESTEIN = range(5)
@@ -111,6 +112,9 @@ SYMBOLS = {
     "scn_floor_from_spectrum": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_float)]),
     "scn_plan_set_floor_window": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
     "scn_local_floor_from_spectrum": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    "scn_plan_set_baseline": (C.c_int, [_vp, C.c_uint32, _vp]),
+    "scn_plan_update_baseline": (C.c_int, [_vp, C.c_int, C.c_uint32]),
+    "scn_plan_get_baseline": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
     "scn_collect_time_domain": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "scn_convert_raw": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "scn_wait": (C.c_int, [_vp, C.c_int]),

@@ -35,6 +35,12 @@ uint32_t evaluated_bins(uint32_t n, uint32_t dc_ignore, double use_bandwidth, ui
 int floor_window_ranks(uint32_t n, uint32_t dc_ignore, uint32_t i_lo, uint32_t i_hi, uint32_t permille, uint32_t train, uint32_t guard,
                        std::vector<uint16_t> &need);
 
+// Baseline plans (scanner_hip.h, "Baseline detector"): what a submit, an update and a read-out must satisfy, from numbers alone
+// (SCN_OK, or the status with the error text set).  rows: the baseline's; indexed: the submit names a run of the plan's table
+int check_baseline_submit(uint32_t rows, bool indexed, uint32_t table_count);
+int check_baseline_update(uint32_t rows, uint32_t units, uint32_t op);
+int check_baseline_range(uint32_t have, uint32_t first_row, uint32_t rows);
+
 // Averaged plans (k = average > 1; sweeps: SCN_AVG_SWEEPS, else SCN_AVG_DWELL).  group_headers redirects fc / seq to the groups'
 // (held in group_fc / group_seq) where the submit gave them or the compaction kernel's default would be wrong; returns the groups
 int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc);

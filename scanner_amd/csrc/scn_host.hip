@@ -193,6 +193,24 @@ int floor_window_ranks(uint32_t n, uint32_t dc_ignore, uint32_t i_lo, uint32_t i
   return SCN_OK;
 }
 
+int check_baseline_submit(uint32_t rows, bool indexed, uint32_t table_count) {
+  if (!rows) return scn_fail(SCN_E_STATE, "the plan has no baseline: scn_plan_set_baseline was never called, or dropped it");
+  if (indexed && rows != 1u && rows != table_count)
+    return scn_fail(SCN_E_STATE, "an indexed submit needs a baseline of 1 row or of one per table entry (%u): it has %u", table_count, rows);
+  return SCN_OK;
+}
+
+int check_baseline_update(uint32_t rows, uint32_t units, uint32_t op) {
+  if (op != SCN_BASELINE_SET && op != SCN_BASELINE_MAX) return scn_fail(SCN_E_INVALID, "unknown baseline op %u", op);
+  if (units > rows) return scn_fail(SCN_E_INVALID, "the submit had %u units, the baseline has %u rows: a row would be written twice", units, rows);
+  return SCN_OK;
+}
+
+int check_baseline_range(uint32_t have, uint32_t first_row, uint32_t rows) {
+  if ((uint64_t)first_row + rows > have) return scn_fail(SCN_E_INVALID, "rows [%u, %u + %u) outside the baseline of %u rows", first_row, first_row, rows, have);
+  return SCN_OK;
+}
+
 // Averaged plans: a submit's arguments alone decide whether it can run -- checked before any copy or kernel is queued
 int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc) {
   if (nb % k) return scn_fail(SCN_E_INVALID, "n_buffers %u is not a multiple of average %u", nb, k);

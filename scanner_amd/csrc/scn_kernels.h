@@ -167,6 +167,26 @@ struct ScnFloorLocalArgs {
 };
 hipError_t scn_launch_floor_local(const ScnFloorLocalArgs &args, int num_cus, hipStream_t stream);
 
+// The baseline detector (scn_baseline.hip, scn_plan_desc.detect = SCN_DETECT_BASELINE): the same place behind the transform, the same
+// regions and counts; bin j of unit u is a hit iff power_db[u][j] > baseline_db[row][j] + threshold, row = scn_baseline_row(first, u,
+// rows).  The detect launch only reads the baseline and writes every unit's count (nothing to zero beforehand).  The update launch
+// (scn_plan_update_baseline) reads the same spectra and writes the same rows, all n bins of each: op SCN_BASELINE_SET copies the
+// bits, SCN_BASELINE_MAX keeps the larger in the floor's key order; it needs n_units <= rows and reads none of the hit fields.
+struct ScnBaselineArgs {
+  const float *power_db;      // [n_units][n], natural bin order
+  float *baseline_db;         // [rows][n], natural bin order (device memory, per plan)
+  uint32_t n, n_units;
+  uint32_t rows, first;       // first < rows
+  float threshold;            // the offset above the baseline, in the plan's dB scale
+  uint32_t dc_ignore, i_lo, i_hi;
+  ScnDevHit *hits;            // [n_units][hit_region]
+  uint32_t hit_region;        // = the number of evaluated bins M
+  uint32_t *counts;           // [n_units]
+  uint32_t op;                // the update launch: SCN_BASELINE_SET / SCN_BASELINE_MAX
+};
+hipError_t scn_launch_baseline_detect(const ScnBaselineArgs &args, int num_cus, hipStream_t stream);
+hipError_t scn_launch_baseline_update(const ScnBaselineArgs &args, hipStream_t stream);
+
 // The same path for the sizes without a fused or four-step kernel (scn_generic.hip): Bluestein, through HBM, stage by stage
 struct ScnGenericArgs {
   const void *raw;            // n_buffers raw buffers back to back

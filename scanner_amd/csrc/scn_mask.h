@@ -1,4 +1,4 @@
-// scn_mask.h -- K5's mask, the one piece of kernel-side arithmetic the host restates: shared by the kernels (through
+// scn_mask.h -- the kernel-side arithmetic the host restates, K5's mask and the baseline row of a unit: shared by the kernels (through
 // scn_kernels.h) and by the plan arithmetic of scn_host.hip, which a plain C++ compiler builds without a HIP header in sight.
 #pragma once
 #include <stdint.h>
@@ -14,4 +14,11 @@
 template <class A>
 SCN_HOST_DEVICE bool scn_bin_evaluated(uint32_t j, uint32_t i, uint32_t n, const A &a) {
   return !(j < a.dc_ignore || (n - j) < a.dc_ignore) && !(i < a.i_lo || i > a.i_hi);
+}
+
+// The baseline row that unit u of a submit reads, and an update writes (scanner_hip.h, "Baseline detector"): (first + u) % rows.
+// The caller keeps first < rows and first + u below 2^32; a row per unit, the usual table, takes no division.
+SCN_HOST_DEVICE uint32_t scn_baseline_row(uint32_t first, uint32_t u, uint32_t rows) {
+  const uint32_t s = first + u;
+  return s < rows ? s : s % rows;
 }

@@ -31,7 +31,7 @@ struct Slot {
   ScnPinnedMem<char> h_raw;         // pinned staging, max_batch raw buffers
   ScnDeviceMem<char> d_raw;         // device copy of the staging slot
   ScnDeviceMem<float> d_power;      // [max_batch][N] dB spectra (plan-owned destination)
-  float *cur_power = nullptr;       // destination of the pending submit (d_power, d_floor_power or the caller's)
+  float *cur_power = nullptr;       // destination of the pending submit (d_power or the caller's; nullptr: the caller collects none)
   ScnPinnedMem<float> h_td;         // time-domain mode: [2][max_batch] max / min dB, pinned, kernel-written
   // [max_batch] hits per buffer.  The kernel writes device memory; a 4*n_buffers-byte D2H copy on
   // the plan's d2h stream (ordered behind the kernel by an event) brings them to the pinned copy,
@@ -85,7 +85,12 @@ struct Slot {
   ScnDeviceMem<float> d_floor;      // [max_batch]
   ScnPinnedMem<float> h_floor;      // [max_batch]
   bool floor_windowed = false;      // the pending / last submit ran under a floor window: it has no per-unit floor (scn_collect_floor)
-  ScnDeviceMem<float> d_floor_power;  // [max_batch][N] the spectrum the detect kernel reads when the caller keeps none (hits-only floor plans)
+  ScnDeviceMem<float> d_detect_power;  // [max_batch][N] the spectrum the detect kernel reads when the caller keeps none (hits-only floor / baseline plans)
+  // baseline plans (scn_baseline.hip): what scn_plan_update_baseline needs of the slot's last submit -- the spectrum its detect
+  // kernel read (cur_power, d_detect_power: still intact, the slot's next submit is what overwrites it), its units and its first_index
+  const float *base_power = nullptr;
+  uint32_t base_units = 0, base_first = 0;
+  bool base_submitted = false;      // ... and that there has been one
   ScnEvent done;
   bool pending = false;
   uint32_t n_buffers = 0;
@@ -134,6 +139,11 @@ struct scn_plan {
   // table r_i + 1 by fftshift index (floor_window_ranks), padded with zeros to a multiple of 4 entries
   uint32_t floor_train = 0, floor_guard = 0;
   ScnDeviceMem<uint16_t> d_floor_need;
+  // scn_plan_desc.detect == SCN_DETECT_BASELINE: as a floor plan's, the transform stores the spectrum only and scn_baseline.hip detects
+  // on it, against d_baseline [baseline_rows][n] (scn_plan_set_baseline; kept allocated when dropped, as d_table)
+  bool baseline = false;
+  ScnDeviceMem<float> d_baseline;
+  uint32_t baseline_rows = 0;  // 0: none, every submit is refused
   uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
   ScnDeviceMem<double> d_twiddle64;  // four-step: [256][2] W_256^k; Bluestein: [fft_m][2] W_m^k; in double
   ScnDeviceMem<double> d_table;      // the plan's frequency table (scn_plan_set_table), read by the compaction kernel; grown on demand
@@ -176,6 +186,10 @@ int build_list(scn_plan *p, Slot &s, bool prefetch);
 // receives the event that marks its completion (nullptr when there is nothing to wait for) and the caller orders its own stream
 // behind it (hipStreamWaitEvent): nothing waits on the host -- what scn_gather_post needs to stay out of the sweep loop's way.
 int scn_plan_device_hits(scn_plan *p, int slot, const scn_hit **d_list, uint32_t *n, int *device_id, void **list_ready = nullptr);
+
+// the plan detects behind the transform (floor and baseline plans): the transform reports the spectrum only, into a plan-owned buffer
+// when the caller keeps none, and the detect kernel that follows it on the slot's stream is the submit's last kernel
+inline bool detects_behind(const scn_plan *p) { return p->floor || p->baseline; }
 
 // the stream the slot's ordered list is built and fetched on
 inline hipStream_t list_stream_of(const scn_plan *p, const Slot &s) { return s.own_stream ? s.stream : p->list_stream.get(); }

@@ -182,7 +182,13 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   }
   uint32_t i_lo = 0, i_hi = 0, floor_permille = 0;
   const uint32_t kept = evaluated_bins(d.n, d.dc_ignore_bins, d.use_bandwidth, &i_lo, &i_hi);
-  if (d.detect != SCN_DETECT_FIXED && d.detect != SCN_DETECT_FLOOR) return scn_fail(SCN_E_INVALID, "unknown detect %u", d.detect);
+  if (d.detect != SCN_DETECT_FIXED && d.detect != SCN_DETECT_FLOOR && d.detect != SCN_DETECT_BASELINE)
+    return scn_fail(SCN_E_INVALID, "unknown detect %u", d.detect);
+  if (d.detect == SCN_DETECT_BASELINE) {  // (floor_permille is not read)
+    if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_BASELINE needs a frequency-domain plan");
+    // (the caller's own flags: a baseline plan names its outputs, the default of "neither -> both" does not apply to it)
+    if (!(desc->flags & SCN_OUT_HITS)) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_BASELINE needs SCN_OUT_HITS set in flags");
+  }
   if (d.detect == SCN_DETECT_FLOOR) {  // (as the average's: properties of the descriptor alone)
     if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR needs a frequency-domain plan");
     if (!(d.flags & SCN_OUT_HITS)) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR needs SCN_OUT_HITS");
@@ -210,6 +216,7 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   p->floor = d.detect == SCN_DETECT_FLOOR;
   if (p->floor) p->floor_rank = (uint32_t)((uint64_t)floor_permille * (kept - 1u) / 1000u);
   p->floor_permille = floor_permille;
+  p->baseline = d.detect == SCN_DETECT_BASELINE;
   build_window(d.window_type, d.n, p->h_window);
 
   hipDeviceProp_t prop;

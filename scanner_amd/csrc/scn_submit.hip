@@ -1,5 +1,6 @@
 // scn_submit.hip -- the submit side of the C-ABI: the transform's launch on the slot's stream and what follows it there and on
-// the side streams (counts, total, floor, the eager list), the frequency table, and K1 alone for the capture path.
+// the side streams (counts, total, floor, the eager list), the frequency table, the floor window, the baseline, and K1 alone for the
+// capture path.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -43,8 +44,8 @@ void set_common_args(A &a, const scn_plan *p, const Slot &s, const void *d_raw, 
 int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float *d_power, uint32_t *host_hits, hipEvent_t stop) {
   const uint32_t n = p->d.n;
   const int kind = (int)p->d.sample_kind;
-  // (a floor plan's transform reports the spectrum only: its hits come from the detect kernel behind it, launch_floor)
-  const bool hits = (p->d.flags & SCN_OUT_HITS) != 0 && !p->floor, dc = p->d.correct_dc != 0;
+  // (a floor or baseline plan's transform reports the spectrum only: its hits come from the detect kernel behind it, launch_floor / launch_baseline)
+  const bool hits = (p->d.flags & SCN_OUT_HITS) != 0 && !detects_behind(p), dc = p->d.correct_dc != 0;
   if (p->avg > 1u) {  // nb buffers = nb / K groups (scn_average.hip)
     const uint32_t ng = nb / p->avg;
     if (ng) SCN_HIP(s.d_avg_partial.alloc(scn_avg_partial_floats(n, p->d.max_batch / p->avg, p->num_cus)));
@@ -171,6 +172,27 @@ int launch_floor(scn_plan *p, Slot &s, const float *d_power, uint32_t nu) {
   return SCN_OK;
 }
 
+// Baseline plans: the detect kernel in the same place, unit u against row (first + u) % rows of the plan's baseline
+int launch_baseline(scn_plan *p, Slot &s, const float *d_power, uint32_t nu, uint32_t first) {
+  ScnBaselineArgs a;
+  memset(&a, 0, sizeof(a));
+  a.power_db = d_power;
+  a.baseline_db = p->d_baseline.get();
+  a.n = p->d.n;
+  a.n_units = nu;
+  a.rows = p->baseline_rows;
+  a.first = first % p->baseline_rows;  // (begin_submit refused a plan without rows)
+  a.threshold = p->d.threshold;
+  a.dc_ignore = p->d.dc_ignore_bins;
+  a.i_lo = p->i_lo;
+  a.i_hi = p->i_hi;
+  a.hits = s.d_hits[s.gen].get();
+  a.hit_region = p->hit_region;
+  a.counts = s.d_buf_hits[s.gen].get();
+  SCN_HIP(scn_launch_baseline_detect(a, p->num_cus, s.stream));
+  return SCN_OK;
+}
+
 // fc == nullptr: the buffers carry entries table_first, table_first + 1, ... (wrapping) of the plan's frequency table
 int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const double *fc, const uint64_t *seq,
                   float *d_power, uint32_t table_first = 0) {
@@ -204,9 +226,15 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
     d_power = s.d_power.get();
   }
   s.cur_power = d_power;  // (what the caller may collect)
-  if (p->floor && !d_power && nb) {  // a hits-only floor plan: the same spectrum-only transform, into a buffer the caller never sees
-    SCN_HIP(s.d_floor_power.alloc((size_t)n * p->d.max_batch));
-    d_power = s.d_floor_power.get();
+  if (detects_behind(p) && !d_power && nb) {  // a hits-only floor or baseline plan: the same spectrum-only transform, into a buffer the caller never sees
+    SCN_HIP(s.d_detect_power.alloc((size_t)n * p->d.max_batch));
+    d_power = s.d_detect_power.get();
+  }
+  if (p->baseline) {  // (what scn_plan_update_baseline folds in once this submit is collected)
+    s.base_power = d_power;
+    s.base_units = nb;
+    s.base_first = table_first;
+    s.base_submitted = true;
   }
   s.n_buffers = nb;
   s.floor_windowed = p->floor && p->floor_train != 0u;
@@ -248,9 +276,9 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   // on that stream against 73 us of FFT; records read in place, three in flight: 373 .. 403 -> 429 Gsamples/s).  So the kernel
   // stores the counts itself when the launch has few buffers or the list follows eagerly, and a DMA carries them otherwise.
   const bool eager = hits && nb && (p->records_wanted || p->device_list_wanted);
-  // (floor plans take the route of the paths that are not fused: the detect kernel, not the transform, is the submit's last kernel,
-  //  and it stores the counts to device memory only -- counts by DMA or scn_hit_total_kernel, a marker event behind it)
-  const bool fused = (p->path == Path::FusedPow2 || p->path == Path::FusedMixed) && p->avg == 1u && !p->floor;
+  // (floor and baseline plans take the route of the paths that are not fused: the detect kernel, not the transform, is the submit's last
+  //  kernel, and it stores the counts to device memory only -- counts by DMA or scn_hit_total_kernel, a marker event behind it)
+  const bool fused = (p->path == Path::FusedPow2 || p->path == Path::FusedMixed) && p->avg == 1u && !detects_behind(p);
   const bool direct = fused && (p->direct_counts || nb <= 4096u || eager);
   // What follows the kernel: the counts (a DMA on the d2h stream: needs no CU -- or nothing, when the kernel stores them to
   // pinned memory itself) and, when the caller is known to want records, the ordered list (two small kernels + a DMA on
@@ -275,6 +303,7 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   st = launch_transform(p, s, d_raw, n_raw, d_power, (hits && direct) ? s.h_buf_hits.get() : nullptr, in_packet ? after : nullptr);
   if (st) return st;
   if (p->floor && nb && (st = launch_floor(p, s, d_power, nb))) return st;
+  if (p->baseline && nb && (st = launch_baseline(p, s, d_power, nb, table_first))) return st;
   if (hits && nb) {
     if (after && !in_packet) SCN_HIP(hipEventRecord(after, s.stream));
     if (cnt != s.stream) SCN_HIP(hipStreamWaitEvent(cnt, after, 0));
@@ -306,13 +335,16 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
 }
 
 // What every submit checks before anything is queued, in this order: the batch's size, the entry point's own pointers, the averaged
-// plan's grouping, the slot (free; `host`: its staging buffer exists) -- then the plan's device is current and the slot's stream exists
-int begin_submit(scn_plan *p, int slot, uint32_t nb, const double *fc, bool null_argument, bool host) {
+// plan's grouping, a baseline plan's rows (`indexed`: against the table), the slot (free; `host`: its staging buffer exists) -- then the
+// plan's device is current and the slot's stream exists
+int begin_submit(scn_plan *p, int slot, uint32_t nb, const double *fc, bool null_argument, bool host, bool indexed) {
   Slot &s = p->slot[slot];
   if (nb > p->d.max_batch) return scn_fail(SCN_E_INVALID, "n_buffers %u > max_batch %u", nb, p->d.max_batch);
   if (null_argument) return scn_fail(SCN_E_INVALID, "null argument");
   if (p->avg > 1u)
     if (int st = check_average(p->avg, p->avg_layout == SCN_AVG_SWEEPS, nb, fc)) return st;
+  if (p->baseline)
+    if (int st = check_baseline_submit(p->baseline_rows, indexed, p->table_count)) return st;
   if (s.pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit", slot);
   if (host && !s.h_raw) return scn_fail(SCN_E_STATE, "slot %d: scn_host_buffer was never called", slot);
   SCN_HIP(hipSetDevice(p->d.device_id));
@@ -320,8 +352,8 @@ int begin_submit(scn_plan *p, int slot, uint32_t nb, const double *fc, bool null
 }
 
 // the pinned slot's buffers -> the GPU -> the kernels; fc == nullptr: entries first_index ... of the plan's frequency table
-int submit_host(scn_plan *p, int slot, uint32_t nb, const double *fc, const uint64_t *seq, uint32_t first_index) {
-  if (int st = begin_submit(p, slot, nb, fc, false, true)) return st;
+int submit_host(scn_plan *p, int slot, uint32_t nb, const double *fc, const uint64_t *seq, uint32_t first_index, bool indexed) {
+  if (int st = begin_submit(p, slot, nb, fc, false, true, indexed)) return st;
   Slot &s = p->slot[slot];
   SCN_HIP(s.d_raw.alloc(p->buf_bytes * p->d.max_batch));
   if (nb) {
@@ -349,14 +381,14 @@ extern "C" {
 int scn_submit(scn_plan *p, int slot, uint32_t nb, const double *fc, const uint64_t *seq) {
   if (int st = check_slot(p, slot)) return st;
   if (nb && !fc) return scn_fail(SCN_E_INVALID, "center_freqs is null");
-  return submit_host(p, slot, nb, fc, seq, 0);
+  return submit_host(p, slot, nb, fc, seq, 0, false);
 }
 
 int scn_submit_device(scn_plan *p, int slot, const void *d_raw, uint32_t nb, const double *fc, const uint64_t *seq,
                       float *d_power_db) {
   int st = check_slot(p, slot);
   if (st) return st;
-  if ((st = begin_submit(p, slot, nb, fc, nb && (!fc || !d_raw), false))) return st;
+  if ((st = begin_submit(p, slot, nb, fc, nb && (!fc || !d_raw), false, false))) return st;
   return submit_common(p, p->slot[slot], d_raw, nb, fc, seq, d_power_db);
 }
 
@@ -364,7 +396,7 @@ int scn_submit_indexed(scn_plan *p, int slot, uint32_t nb, uint32_t first_index,
   int st = check_slot(p, slot);
   if (st) return st;
   if ((st = check_indexed(p, nb, first_index))) return st;
-  return submit_host(p, slot, nb, nullptr, seq, first_index);
+  return submit_host(p, slot, nb, nullptr, seq, first_index, true);
 }
 
 int scn_submit_device_indexed(scn_plan *p, int slot, const void *d_raw, uint32_t nb, uint32_t first_index, const uint64_t *seq,
@@ -372,7 +404,7 @@ int scn_submit_device_indexed(scn_plan *p, int slot, const void *d_raw, uint32_t
   int st = check_slot(p, slot);
   if (st) return st;
   if ((st = check_indexed(p, nb, first_index))) return st;
-  if ((st = begin_submit(p, slot, nb, nullptr, nb && !d_raw, false))) return st;
+  if ((st = begin_submit(p, slot, nb, nullptr, nb && !d_raw, false, true))) return st;
   return submit_common(p, p->slot[slot], d_raw, nb, nullptr, seq, d_power_db, first_index);
 }
 
@@ -418,6 +450,62 @@ int scn_plan_set_floor_window(scn_plan *p, uint32_t train, uint32_t guard) {
   SCN_HIP(hipMemcpy(p->d_floor_need.get(), need.data(), sizeof(uint16_t) * need.size(), hipMemcpyHostToDevice));
   p->floor_train = train;
   p->floor_guard = guard;
+  return SCN_OK;
+}
+
+int scn_plan_set_baseline(scn_plan *p, uint32_t rows, const float *baseline_db) {
+  if (!p) return scn_fail(SCN_E_INVALID, "null plan");
+  if (!p->baseline) return scn_fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_BASELINE");
+  for (int i = 0; i < SCN_NUM_SLOTS; i++)
+    if (p->slot[i].pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit: its detect kernel may still read the baseline", i);
+  // (no slot is pending, and a slot's detect kernel is complete when its `done` is: nothing reads the old rows any more)
+  p->baseline_rows = 0;
+  if (!rows) return SCN_OK;  // (the allocation stays for the next one, as the table's)
+  const size_t count = (size_t)rows * p->d.n;
+  SCN_HIP(hipSetDevice(p->d.device_id));
+  if (count > p->d_baseline.capacity()) SCN_HIP(p->d_baseline.grow(count));
+  if (baseline_db) SCN_HIP(hipMemcpyAsync(p->d_baseline.get(), baseline_db, sizeof(float) * count, hipMemcpyHostToDevice, p->stream.get()));
+  else SCN_HIP(hipMemsetD32Async((hipDeviceptr_t)p->d_baseline.get(), 0x7f800000, count, p->stream.get()));  // +inf
+  SCN_HIP(hipStreamSynchronize(p->stream.get()));  // (baseline_db is the caller's: done with it before returning; slots with a stream of their own start behind this)
+  p->baseline_rows = rows;
+  return SCN_OK;
+}
+
+int scn_plan_update_baseline(scn_plan *p, int slot, uint32_t op) {
+  if (int st = check_slot(p, slot)) return st;
+  if (!p->baseline) return scn_fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_BASELINE");
+  for (int i = 0; i < SCN_NUM_SLOTS; i++)
+    if (p->slot[i].pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit: its detect kernel may still read the baseline", i);
+  const Slot &s = p->slot[slot];
+  if (!s.base_submitted) return scn_fail(SCN_E_STATE, "slot %d has no collected submit to learn from", slot);
+  if (!p->baseline_rows) return scn_fail(SCN_E_STATE, "the plan has no baseline: scn_plan_set_baseline was never called, or dropped it");
+  if (int st = check_baseline_update(p->baseline_rows, s.base_units, op)) return st;
+  if (!s.base_units) return SCN_OK;
+  SCN_HIP(hipSetDevice(p->d.device_id));
+  ScnBaselineArgs a;
+  memset(&a, 0, sizeof(a));
+  a.power_db = s.base_power;  // (complete: the slot's collect waited for the detect kernel behind the transform that wrote it)
+  a.baseline_db = p->d_baseline.get();
+  a.n = p->d.n;
+  a.n_units = s.base_units;
+  a.rows = p->baseline_rows;
+  a.first = s.base_first % p->baseline_rows;
+  a.op = op;
+  SCN_HIP(scn_launch_baseline_update(a, p->stream.get()));
+  SCN_HIP(hipStreamSynchronize(p->stream.get()));
+  return SCN_OK;
+}
+
+int scn_plan_get_baseline(scn_plan *p, uint32_t first_row, uint32_t rows, float *out) {
+  if (!p) return scn_fail(SCN_E_INVALID, "null plan");
+  if (!p->baseline) return scn_fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_BASELINE");
+  if (int st = check_baseline_range(p->baseline_rows, first_row, rows)) return st;
+  if (!rows) return SCN_OK;
+  if (!out) return scn_fail(SCN_E_INVALID, "null argument");
+  SCN_HIP(hipSetDevice(p->d.device_id));
+  const size_t n = p->d.n;
+  SCN_HIP(hipMemcpyAsync(out, p->d_baseline.get() + (size_t)first_row * n, sizeof(float) * (size_t)rows * n, hipMemcpyDeviceToHost, p->stream.get()));
+  SCN_HIP(hipStreamSynchronize(p->stream.get()));
   return SCN_OK;
 }
 

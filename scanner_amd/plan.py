@@ -16,8 +16,11 @@ class Plan:
                  correct_dc=False, max_batch=1, use_bandwidth=0.75, dc_ignore_bins=4, trigger_count=1047,
                  max_hits=0, flags=capi.OUT_SPECTRUM | capi.OUT_HITS, device_id=0,
                  window_type=capi.WIN_BLACKMAN_HARRIS, mode=capi.MODE_FREQUENCY_DOMAIN, average=1,
-                 average_layout=capi.AVG_DWELL, detect=capi.DETECT_FIXED, floor_permille=0, floor_window=None):
-        """floor_window = (train, guard), floor plans only: each bin's floor is the rank among its own reference cells, the evaluated
+                 average_layout=capi.AVG_DWELL, detect=capi.DETECT_FIXED, floor_permille=0, floor_window=None, baseline=None):
+        """detect = capi.DETECT_BASELINE: a bin is a hit when it exceeds the stored spectrum of its unit's table entry by more than
+        `threshold`, then an offset in the plan's dB scale; baseline = a float32 array [rows, n] (or a row count: that many rows of
+        +inf) is set_baseline's argument, and a plan without one refuses every submit (scanner_hip.h, "Baseline detector").
+        floor_window = (train, guard), floor plans only: each bin's floor is the rank among its own reference cells, the evaluated
         bins guard < |i' - i| <= guard + train away (set_floor_window; scanner_hip.h, "Floor window").
         detect = capi.DETECT_FLOOR: a bin is a hit when it exceeds its own unit's floor -- the value of rank floor_permille
         (0: the median, capi.FLOOR_MIN: the minimum, 1000: the maximum) among the unit's evaluated bins -- by more than
@@ -58,12 +61,15 @@ class Plan:
         self._keep = [None] * capi.NUM_SLOTS
         self._submit_device, self._collect, self._n_hits = self._L.scn_submit_device, self._L.scn_collect, C.c_uint32()
         self._submit_device_indexed = self._L.scn_submit_device_indexed
-        if floor_window is not None:
-            try:
+        self._baseline_rows = 0
+        try:
+            if floor_window is not None:
                 self.set_floor_window(*floor_window)
-            except Exception:
-                self.close()
-                raise
+            if baseline is not None:
+                self.set_baseline(baseline)
+        except Exception:
+            self.close()
+            raise
 
     # -- lifetime -----------------------------------------------------------
     @property
@@ -124,6 +130,31 @@ class Plan:
         `train` evaluated-or-masked bins on either side beyond `guard` bins, the masked ones taking up distance only.  (0, 0)
         returns to the unit-wide floor.  Not while a slot is pending; a windowed slot has no collect_floor."""
         capi.check(self._L.scn_plan_set_floor_window(self._h, int(train), int(guard)), "scn_plan_set_floor_window")
+
+    def set_baseline(self, baseline):
+        """scn_plan_set_baseline: the stored spectra a baseline plan's units are held against, float32 [rows, n] in natural bin order;
+        unit u of a submit reads row (first_index + u) % rows.  An int makes that many rows of +inf -- armed, nothing can hit: where
+        learning with update_baseline starts --, 0 drops the baseline.  Not while a slot is pending."""
+        if isinstance(baseline, (int, np.integer)):
+            rows, ptr = int(baseline), None
+        else:
+            arr = np.ascontiguousarray(baseline, np.float32)
+            assert arr.ndim == 2 and arr.shape[1] == self.n, f"a baseline is [rows, {self.n}]"
+            rows, ptr = arr.shape[0], arr.ctypes.data_as(C.c_void_p)
+        capi.check(self._L.scn_plan_set_baseline(self._h, rows, ptr), "scn_plan_set_baseline")
+        self._baseline_rows = rows
+
+    def update_baseline(self, slot, op=capi.BASELINE_MAX):
+        """scn_plan_update_baseline: fold the spectra of the slot's last collected submit into the rows of its units, on the GPU --
+        capi.BASELINE_SET copies them, capi.BASELINE_MAX keeps the larger per bin (max-hold).  No slot may be pending."""
+        capi.check(self._L.scn_plan_update_baseline(self._h, slot, int(op)), "scn_plan_update_baseline")
+
+    def baseline(self, first_row=0, rows=None):
+        """scn_plan_get_baseline: rows [first_row, first_row + rows) of the baseline (to its end by default), float32 [rows, n]."""
+        rows = max(0, self._baseline_rows - int(first_row)) if rows is None else int(rows)
+        out = np.empty((rows, self.n), np.float32)
+        capi.check(self._L.scn_plan_get_baseline(self._h, int(first_row), rows, out.ctypes.data_as(C.c_void_p)), "scn_plan_get_baseline")
+        return out
 
     def submit(self, slot, n_buffers, center_freqs=None, seq_ids=None, first_index=None):
         """Process the first n_buffers raw buffers of the pinned slot (async)."""
