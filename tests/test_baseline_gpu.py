@@ -46,15 +46,16 @@ def _headers(nb, average, layout):
 
 
 def _check(n, x, baseline, threshold, want_spectrum=None, average=1, layout=capi.AVG_DWELL, trigger_count=1047, want_parts=None,
-           flags_extra=0):
+           flags_extra=0, use_bandwidth=0.75, dc_ignore_bins=4):
     """assertions 1 to 3 on one input against one baseline (a plain submit: unit u reads row u % rows); returns (spectrum, hits)"""
     nb = x.shape[0]
     units = nb // average
     sub, fc_units, seq_units = _headers(nb, average, layout)
+    mask = dict(use_bandwidth=use_bandwidth, dc_ignore_bins=dc_ignore_bins)  # every plan's and the reference's
     out = {}
     for flags in (BOTH, capi.OUT_HITS):
         with Plan(n, FS, threshold, flags=flags | flags_extra, detect=capi.DETECT_BASELINE, baseline=baseline, max_batch=nb, average=average,
-                  average_layout=layout, trigger_count=trigger_count) as plan:
+                  average_layout=layout, trigger_count=trigger_count, **mask) as plan:
             if want_parts is not None:
                 assert (plan.average_parts(nb) > 1) == want_parts
             _submit(plan, 0, x, **sub)
@@ -63,7 +64,7 @@ def _check(n, x, baseline, threshold, want_spectrum=None, average=1, layout=capi
             out[flags] = (p, h.copy(), t)
     p, h, t = out[BOTH]
     assert p.shape == (units, n)
-    want_h, want_t = baseline_ref.detect(p, baseline, 0, threshold, fc_units, seq_units, FS, trigger_count)
+    want_h, want_t = baseline_ref.detect(p, baseline, 0, threshold, fc_units, seq_units, FS, trigger_count, **mask)
     baseline_ref.assert_same_records(h, want_h, f"n {n}: the baseline plan against the reference")              # 1
     assert np.array_equal(t, want_t)
     if want_spectrum is not None:                                                                                # 2

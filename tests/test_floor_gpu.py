@@ -34,11 +34,12 @@ def _submit(plan, slot, x, nb=None, **kw):
 
 
 def _check(n, x, threshold, permille=0, kind=capi.KIND_FLOAT_COMPLEX, enob=12, average=1, layout=capi.AVG_DWELL, trigger_count=1047,
-           indexed=False, want_parts=None):
+           indexed=False, want_parts=None, use_bandwidth=0.75, dc_ignore_bins=4):
     """the four assertions above on one input; returns (spectrum, floors, hits) of the spectrum + hits floor plan"""
     nb = x.shape[0]
     units = nb // average
-    kw = dict(kind=kind, enob=enob, max_batch=nb, average=average, average_layout=layout, trigger_count=trigger_count)
+    mask = dict(use_bandwidth=use_bandwidth, dc_ignore_bins=dc_ignore_bins)  # every plan's, the reference's and the host form's
+    kw = dict(kind=kind, enob=enob, max_batch=nb, average=average, average_layout=layout, trigger_count=trigger_count, **mask)
     fc_units = 100e6 + 6e6 * np.arange(units)
     sub = {}
     if indexed:  # a run of the plan's table that wraps
@@ -68,10 +69,10 @@ def _check(n, x, threshold, permille=0, kind=capi.KIND_FLOAT_COMPLEX, enob=12, a
             out[flags] = (p, h.copy(), t, plan.collect_floor(0))
     p, h, t, fl = out[BOTH]
     assert p.shape == (units, n) and fl.shape == (units,)
-    want_fl, want_h, want_t = floor_ref.detect(p, threshold, permille, fc_units, seq_units, FS, trigger_count)
+    want_fl, want_h, want_t = floor_ref.detect(p, threshold, permille, fc_units, seq_units, FS, trigger_count, **mask)
     assert floor_ref.same_bits(fl, want_fl), (fl, want_fl)                                        # 1
     for u in range(units):
-        assert floor_ref.same_bits(fl[u], capi.floor_from_spectrum(p[u], floor_permille=permille)), u
+        assert floor_ref.same_bits(fl[u], capi.floor_from_spectrum(p[u], floor_permille=permille, **mask)), u
     floor_ref.assert_same_records(h, want_h, f"n {n}: the floor plan against the reference")      # 2
     assert np.array_equal(t, want_t)
     with Plan(n, FS, 1e9, flags=capi.OUT_SPECTRUM, **kw) as plan:                                  # 3

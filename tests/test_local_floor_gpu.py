@@ -21,12 +21,13 @@ BOTH = capi.OUT_SPECTRUM | capi.OUT_HITS
 
 
 def _check(n, x, threshold, window, permille=0, kind=capi.KIND_FLOAT_COMPLEX, enob=12, average=1, layout=capi.AVG_DWELL, trigger_count=1047,
-           indexed=False, want_parts=None):
+           indexed=False, want_parts=None, use_bandwidth=0.75, dc_ignore_bins=4):
     """the four assertions above on one input; returns (spectrum, hits, trigger) of the spectrum + hits plan"""
     nb = x.shape[0]
     units = nb // average
     train, guard = window
-    kw = dict(kind=kind, enob=enob, max_batch=nb, average=average, average_layout=layout, trigger_count=trigger_count)
+    mask = dict(use_bandwidth=use_bandwidth, dc_ignore_bins=dc_ignore_bins)  # every plan's, the reference's and the host form's
+    kw = dict(kind=kind, enob=enob, max_batch=nb, average=average, average_layout=layout, trigger_count=trigger_count, **mask)
     fc_units = 100e6 + 6e6 * np.arange(units)
     if indexed:  # a run of the plan's table that wraps
         table = 100e6 + 6e6 * np.arange(units + 2)
@@ -55,7 +56,7 @@ def _check(n, x, threshold, window, permille=0, kind=capi.KIND_FLOAT_COMPLEX, en
             out[flags] = (p, h.copy(), t)
     p, h, t = out[BOTH]
     assert p.shape == (units, n)
-    want_fl, want_h, want_t = local_floor_ref.detect(p, threshold, train, guard, permille, fc_units, seq_units, FS, trigger_count)
+    want_fl, want_h, want_t = local_floor_ref.detect(p, threshold, train, guard, permille, fc_units, seq_units, FS, trigger_count, **mask)
     floor_ref.assert_same_records(h, want_h, f"n {n} window {window}: the windowed plan against the reference")     # 1
     assert np.array_equal(t, want_t)
     with Plan(n, FS, 1e9, flags=capi.OUT_SPECTRUM, **kw) as plan:                                                    # 2
@@ -64,9 +65,9 @@ def _check(n, x, threshold, window, permille=0, kind=capi.KIND_FLOAT_COMPLEX, en
     assert p_fixed.tobytes() == p.tobytes(), "the windowed plan's spectrum differs from the fixed spectrum-only plan's"
     p2, h2, t2 = out[capi.OUT_HITS]                                                                                  # 3
     assert p2 is None and h2.tobytes() == h.tobytes() and np.array_equal(t2, t)
-    ev = tol.evaluated_mask(n)                                                                                       # 4
+    ev = tol.evaluated_mask(n, use_bandwidth, dc_ignore_bins)                                                        # 4
     for u in range(units):
-        host = capi.local_floor_from_spectrum(p[u], train, guard, floor_permille=permille)
+        host = capi.local_floor_from_spectrum(p[u], train, guard, floor_permille=permille, **mask)
         assert floor_ref.same_bits(floor_ref.cut_of(host[ev], threshold), floor_ref.cut_of(want_fl[u][ev], threshold)), u
     return p, h, t
 
