@@ -1,17 +1,15 @@
 // scn_baseline.hip -- the baseline detector (scn_plan_desc.detect = SCN_DETECT_BASELINE; definition: scanner_hip.h, "Baseline
 // detector") and the kernel that folds a collected spectrum into the baseline (scn_plan_update_baseline).
 //
-// Detect: one kernel behind the transform, where scn_floor_kernel sits, on the dB spectrum the spectrum-only specialisations
-// store.  Unit u (a buffer, or a group of an averaged plan) is held against row (first + u) % rows of the plan's baseline: an
+// Detect: one kernel behind the transform, on the dB spectrum the spectrum-only specialisations store (the team model and the hit
+// pass are scn_detect.h's).  Unit u (a buffer, or a group of an averaged plan) is held against row (first + u) % rows of the plan's baseline: an
 // evaluated bin j is a hit iff power_db[u][j] > baseline_db[row][j] + threshold -- ONE float addition, a strict compare -- and is
 // recorded as the FFT kernels' own hit paths record it: {i, power_db} in the unit's region, in any order, and the unit's count.
 // Scan, compaction, signals and gather read them unchanged.  The kernel only READS the baseline.  There is nothing to select, so it
 // is a single streaming pass over the two rows: no float arithmetic beyond that addition, no global atomics, nothing zeroed
 // beforehand (every unit's count is written).
 //
-// Geometry (a TEAM of T threads per unit, persistent: teams walk units with the grid's stride, the grid capped at what is resident):
-//   n <= 512          T = 64: a wave per unit, four units per 256-thread workgroup, wave barriers only
-//   n <= 4096         T = 256, above: T = 1024: a workgroup per unit
+// Sizes: n <= 512: T = 64, n <= 4096: T = 256, above: T = 1024.
 // Loads (VEC): rows that start 16-byte aligned -- n % 4 == 0 and both base pointers 16-byte aligned -- are read 16 bytes per lane,
 // four consecutive bins j = 4 q ... 4 q + 3; every other size (odd n: row u starts 4-byte aligned only; n = 18: 8-byte) takes the
 // 4-byte form, a bin per lane and load.  A lane keeps U loads of each row in flight before it looks at the first: U = 1, 2 or 4,
@@ -19,35 +17,21 @@
 //   16 ... 256 (n % 4 == 0)  <64, VEC, 1>      512 <64, VEC, 2>      1000, 1024 <256, VEC, 1>     2048 <256, VEC, 2>
 //   4096 <256, VEC, 4>       8192 <1024, VEC, 2>      16384 ... 65536 <1024, VEC, 4>
 //   18, 1001 and every n % 4 != 0: <64 | 256 | 1024, scalar, U by the same rule> (n <= 64: U = 1, n <= 128: 2, ...)
-// Both rows are read through a buffer descriptor of exactly that row and the records are stored through one of exactly the unit's
-// region: a load past the row reads 0 and its bins are not evaluated (j >= n), a store of a lane without a hit goes outside the
-// descriptor and is dropped.
+// The baseline row is read through a descriptor of exactly that row, as the spectrum's is: a load past either reads 0 and its bins
+// are not evaluated (j >= n).
 // Cache policy: default on both streams.  The baseline rows are re-read every sweep and must stay cacheable.  The spectrum was
 // written by the transform immediately before, on the same stream, and is read again by scn_collect's copy (spectrum + hits plans)
 // or by scn_plan_update_baseline: a non-temporal read would not save a fetch that reaches memory, and was not measured.
-// Hit pass: the hits-only kernels' slot grab -- per group of loads a wave counts its hits (ballots), takes that many slots of the
-// unit's region with one LDS atomic, and its lanes store their records at ballot-prefix positions.  A wave without a hit in the
-// group touches neither LDS nor memory.  A region holds hit_region = M records, as many as there are evaluated bins.
+// One slot grab per wave and load: a wave without a hit in it touches neither LDS nor memory.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/scanner_hip.h"  // SCN_BASELINE_*
-#include "scn_device.h"
+#include "scn_detect.h"
 
 namespace {
 
 typedef float v4f_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u2_t __attribute__((ext_vector_type(2)));
-
-template <int T>
-__device__ __forceinline__ void team_sync() {
-  if constexpr (T == 64) {  // a wave: its LDS operations complete in order
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  } else {
-    __syncthreads();
-  }
-}
 
 // W consecutive floats at byte offset `off` of the row behind r (outside the row: zeros)
 template <bool VEC>
@@ -65,18 +49,20 @@ __device__ __forceinline__ void load_bins(__amdgpu_buffer_rsrc_t r, uint32_t off
 
 template <int T, bool VEC, int U>
 __global__ __launch_bounds__(T == 64 ? 256 : T) void scn_baseline_kernel(ScnBaselineArgs a) {
-  constexpr int BLOCK = T == 64 ? 256 : T, TEAMS = BLOCK / T, W = VEC ? 4 : 1;
+  typedef Team<T> G;
+  constexpr uint32_t TEAMS = G::TEAMS;
+  constexpr int W = VEC ? 4 : 1;
   __shared__ uint32_t s_count[TEAMS];
-  const uint32_t t = threadIdx.x % T, team = threadIdx.x / T, lane = threadIdx.x & 63u;
-  const uint32_t n = a.n, to_i = n - n / 2u;  // i = (j + n - n / 2) % n is the i with (i + n / 2) % n == j (process.cpp:47)
+  const uint32_t t = G::t(), team = G::team(), lane = G::lane();
+  const uint32_t n = a.n, to_i = n - n / 2u;
   const uint32_t trips = (n + (uint32_t)(W * T) - 1u) / (uint32_t)(W * T);
   const unsigned long long below = (1ull << lane) - 1ull;
   for (uint32_t u0 = blockIdx.x * TEAMS + team; u0 < a.n_units; u0 += gridDim.x * TEAMS) {
     const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)u0);  // (the same in every lane of a wave)
     const uint32_t row = scn_baseline_row(a.first, u, a.rows);
-    const __amdgpu_buffer_rsrc_t rin = make_rsrc(a.power_db + (size_t)u * n, n * 4u);
+    const __amdgpu_buffer_rsrc_t rin = spectrum_rsrc(a, u);
     const __amdgpu_buffer_rsrc_t rbase = make_rsrc(a.baseline_db + (size_t)row * n, n * 4u);
-    const __amdgpu_buffer_rsrc_t rhit = make_rsrc(a.hits + (size_t)u * a.hit_region, a.hit_region * (uint32_t)sizeof(ScnDevHit));
+    const __amdgpu_buffer_rsrc_t rhit = region_rsrc(a, u);
     if (t == 0) s_count[team] = 0u;
     team_sync<T>();
     for (uint32_t k0 = 0; k0 < trips; k0 += (uint32_t)U) {
@@ -95,26 +81,17 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void scn_baseline_kernel(ScnBase
 #pragma unroll
         for (int c = 0; c < W; c++) {
           const uint32_t j = j0 + (uint32_t)c;
-          uint32_t i = j + to_i;
-          i = i >= n ? i - n : i;
+          const uint32_t i = shift_of_bin(j, to_i, n);
           const bool hit = (j < n) & scn_bin_evaluated(j, i, n, a) & (p[x][c] > b[x][c] + a.threshold);  // (no branches)
           m[c] = __ballot(hit);
           total += (uint32_t)__popcll(m[c]);
         }
         if (total) {  // one slot grab for the wave, then the records at ballot-prefix positions
-          uint32_t base = 0;
-          if (lane == 0) base = atomicAdd(&s_count[team], total);
-          base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+          uint32_t base = grab_slots(&s_count[team], total, lane);
 #pragma unroll
           for (int c = 0; c < W; c++) {
-            const uint32_t j = j0 + (uint32_t)c;
-            uint32_t i = j + to_i;
-            i = i >= n ? i - n : i;
-            const bool hit = (m[c] >> lane) & 1ull;
-            const uint32_t pos = base + (uint32_t)__popcll(m[c] & below);
-            // (a lane without a hit stores outside the descriptor: dropped)
-            __builtin_amdgcn_raw_buffer_store_b64(u2_t{i, __float_as_uint(p[x][c])}, rhit, hit ? pos * (uint32_t)sizeof(ScnDevHit) : 0x80000000u, 0, 0);
-            base += (uint32_t)__popcll(m[c]);
+            const uint32_t i = shift_of_bin(j0 + (uint32_t)c, to_i, n);
+            store_record(rhit, base, m[c], (m[c] >> lane) & 1ull, below, i, __float_as_uint(p[x][c]));
           }
         }
       }
@@ -126,24 +103,8 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void scn_baseline_kernel(ScnBase
 
 template <int T, bool VEC, int U>
 hipError_t launch(const ScnBaselineArgs &a, int num_cus, hipStream_t stream) {
-  constexpr uint32_t block = T == 64 ? 256u : (uint32_t)T, teams = block / (uint32_t)T;
-  // persistent teams: as many workgroups as the runtime says are resident at once for this instantiation (asked once per
-  // instantiation; 8 of 256 threads or 2 of 1024 per CU should the query fail); no more workgroups than there are units to walk.
-  // The workgroups share nothing: the grid's size is a matter of speed only.
-  static int per_cu = 0;  // (plans of several threads may race to the same answer)
-  if (per_cu <= 0) {
-    int q = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, scn_baseline_kernel<T, VEC, U>, (int)block, 0) != hipSuccess || q <= 0) {
-      (void)hipGetLastError();
-      q = block == 256u ? 8 : 2;
-    }
-    per_cu = q;
-  }
-  const uint32_t resident = (uint32_t)(num_cus > 0 ? num_cus : 256) * (uint32_t)per_cu;
-  uint32_t blocks = (a.n_units + teams - 1u) / teams;
-  if (blocks > resident) blocks = resident;
-  hipLaunchKernelGGL((scn_baseline_kernel<T, VEC, U>), dim3(blocks), dim3(block), 0, stream, a);
-  return hipGetLastError();
+  typedef Team<T> G;  // (the fallback: 8 workgroups of 256 threads or 2 of 1024 per CU)
+  return launch_teams<scn_baseline_kernel<T, VEC, U>, G::BLOCK, G::TEAMS>(0, G::BLOCK == 256u ? 8 : 2, a, num_cus, stream);
 }
 
 template <int T, bool VEC>
@@ -160,8 +121,6 @@ hipError_t launch_size(const ScnBaselineArgs &a, int num_cus, hipStream_t stream
   if (a.n <= 4096u) return launch_team<256, VEC>(a, num_cus, stream);
   return launch_team<1024, VEC>(a, num_cus, stream);
 }
-
-__device__ __forceinline__ uint32_t floor_key(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u); }
 
 // Element-wise over units x n: a workgroup per unit (walking units with the grid's stride), its threads over the row's bins.
 // units <= rows (the caller's check), so no row is named by two units of one launch: no two threads write the same word.

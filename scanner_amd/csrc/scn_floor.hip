@@ -4,11 +4,10 @@
 // of an averaged plan) it selects the value of a given rank among the evaluated bins -- the unit's floor --, adds the plan's
 // offset to it in one float addition and records every evaluated bin strictly above that cut, in the format the FFT kernels'
 // own hit paths leave: {i, power_db} records in the unit's region, in any order, and the unit's count.  Scan, compaction,
-// signals and gather read them unchanged.  No FFT kernel is touched (sharing code with them reschedules
-// every instantiation).
+// signals and gather read them unchanged.  The team model and the hit pass are scn_detect.h's.
 //
-// Selection: an MSB-first radix select on the keys `(bits & 0x80000000) ? ~bits : bits | 0x80000000` (unsigned order = float
-// order, -inf lowest, -0.0 below +0.0).  Per pass: a histogram of the digit over the keys that match the prefix found so far,
+// Selection: an MSB-first radix select on the ordered keys (floor_key, scn_detect.h: unsigned order = float order, -inf lowest,
+// -0.0 below +0.0).  Per pass: a histogram of the digit over the keys that match the prefix found so far,
 // built in LDS with integer atomics; every wave scans it (4 entries per lane, one 16-byte read, a shuffle scan) and picks the
 // digit that holds the rank.  Integer counts only: no global atomics, no float atomics, no float sums -- the floor, the cut and
 // the hit set are the same whatever order the waves run in.
@@ -20,35 +19,16 @@
 // digit: the lanes with the leading lane's digit add their number with ONE atomic (up to three such rounds), the rest singly
 // -- 64 same-address LDS atomics would serialise.
 //
-// Geometry (a TEAM of T threads per unit, persistent: teams walk units with the grid's stride):
-//   n <= 512          T = 64: a wave per unit, four units per 256-thread workgroup, wave barriers only
-//   n <= 4096         T = 256, n <= 16384: T = 1024: a workgroup per unit
-//   in all of these the unit's values stay in registers (KPT = ceil(n / T) <= 16 per thread): the spectrum is read ONCE.
-//   n > 16384         T = 1024, the unit re-read from memory in every pass and in the hit pass (5 reads of 128 / 256 KiB,
-//                     which L2 holds): the evaluated keys alone exceed what a workgroup can keep on chip.
-// Hit pass: the hits-only kernels' slot grab -- a wave counts its hits over all its bins (ballots), takes that many slots of
-// the unit's region with one LDS atomic, and its lanes store their records at ballot-prefix positions.  A region holds
-// hit_region = M records, as many as there are evaluated bins: it cannot overflow, and the stores go through a buffer
-// descriptor of exactly the region, as the loads go through one of exactly the unit's spectrum.
+// Sizes: n <= 512: T = 64, n <= 4096: T = 256, n <= 16384: T = 1024, and in all of these the unit's values stay in registers
+// (KPT = ceil(n / T) <= 16 per thread): the spectrum is read ONCE.  n > 16384: T = 1024, the unit re-read from memory in every pass
+// and in the hit pass (5 reads of 128 / 256 KiB, which L2 holds): the evaluated keys alone exceed what a workgroup can keep on chip.
+// The wave counts its hits over all its bins before its one slot grab.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "scn_device.h"
+#include "scn_detect.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t floor_key(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u); }
-__device__ __forceinline__ uint32_t floor_unkey(uint32_t key) { return (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key; }
-
-template <int T>
-__device__ __forceinline__ void team_sync() {
-  if constexpr (T == 64) {  // a wave: its LDS operations complete in order
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  } else {
-    __syncthreads();
-  }
-}
 
 // hist[digit] += 1 for the active lanes (called by whole waves)
 __device__ __forceinline__ void hist_add(uint32_t *hist, bool active, uint32_t digit, uint32_t lane) {
@@ -99,24 +79,23 @@ __device__ __forceinline__ uint32_t pick_digit(const uint32_t *hist, uint32_t &r
 
 template <int T, int KPT, bool REREAD>
 __global__ __launch_bounds__(T == 64 ? 256 : T) void scn_floor_kernel(ScnFloorArgs a) {
-  constexpr int BLOCK = T == 64 ? 256 : T, TEAMS = BLOCK / T;
+  typedef Team<T> G;
+  constexpr uint32_t TEAMS = G::TEAMS;
   __shared__ __attribute__((aligned(16))) uint32_t s_hist[TEAMS][4][256];  // one histogram per pass: zeroed once per unit
   __shared__ uint32_t s_count[TEAMS];
-  const uint32_t t = threadIdx.x % T, team = threadIdx.x / T, lane = threadIdx.x & 63u;
-  const uint32_t n = a.n, to_i = n - n / 2u;  // i = (j + n - n / 2) % n is the i with (i + n / 2) % n == j (process.cpp:47)
+  const uint32_t t = G::t(), team = G::team(), lane = G::lane();
+  const uint32_t n = a.n, to_i = n - n / 2u;
   const uint32_t trips = REREAD ? (n + T - 1u) / T : (uint32_t)KPT;
   uint32_t(*const hist)[256] = s_hist[team];
   uint32_t *const hist_all = &s_hist[team][0][0];  // the team's four histograms, 4 x 256 words in a row
   for (uint32_t u0 = blockIdx.x * TEAMS + team; u0 < a.n_units; u0 += gridDim.x * TEAMS) {
     const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)u0);  // (the same in every lane of a wave)
-    const __amdgpu_buffer_rsrc_t rin = make_rsrc(a.power_db + (size_t)u * n, n * 4u);
-    const __amdgpu_buffer_rsrc_t rhit = make_rsrc(a.hits + (size_t)u * a.hit_region, a.hit_region * (uint32_t)sizeof(ScnDevHit));
+    const __amdgpu_buffer_rsrc_t rin = spectrum_rsrc(a, u), rhit = region_rsrc(a, u);
     // bin j = t + k T of the unit: its value's bits, and whether the mask lets it through
     auto load = [&](uint32_t k, uint32_t &bits, uint32_t &i) -> bool {
       const uint32_t j = t + k * T;
       bits = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rin, j * 4u, 0, 0);  // (j >= n: outside the descriptor, reads 0)
-      i = j + to_i;
-      i = i >= n ? i - n : i;
+      i = shift_of_bin(j, to_i, n);
       return j < n && scn_bin_evaluated(j, i, n, a);
     };
     uint32_t val[REREAD ? 1 : KPT];
@@ -168,31 +147,20 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void scn_floor_kernel(ScnFloorAr
 #pragma unroll
       for (int k = 0; k < KPT; k++) total += (uint32_t)__popcll(__ballot(((valid >> k) & 1u) && __uint_as_float(val[k]) > cut));
     }
-    uint32_t base = 0;
     if (total) {
-      if (lane == 0) base = atomicAdd(&s_count[team], total);
-      base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+      uint32_t base = grab_slots(&s_count[team], total, lane);
       const unsigned long long below = (1ull << lane) - 1ull;
-      auto record = [&](bool hit, uint32_t bits, uint32_t i) {
-        const unsigned long long m = __ballot(hit);
-        const uint32_t pos = base + (uint32_t)__popcll(m & below);
-        typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-        // (a lane without a hit stores outside the descriptor: dropped)
-        __builtin_amdgcn_raw_buffer_store_b64(u2{i, bits}, rhit, hit ? pos * (uint32_t)sizeof(ScnDevHit) : 0x80000000u, 0, 0);
-        base += (uint32_t)__popcll(m);
-      };
       if constexpr (REREAD) {
         for (uint32_t k = 0; k < trips; k++) {
           uint32_t bits, i;
-          const bool ok = load(k, bits, i);
-          record(ok && __uint_as_float(bits) > cut, bits, i);
+          const bool hit = load(k, bits, i) && __uint_as_float(bits) > cut;
+          store_record(rhit, base, __ballot(hit), hit, below, i, bits);
         }
       } else {
 #pragma unroll
         for (int k = 0; k < KPT; k++) {
-          uint32_t i = t + (uint32_t)k * T + to_i;
-          i = i >= n ? i - n : i;
-          record(((valid >> k) & 1u) && __uint_as_float(val[k]) > cut, val[k], i);
+          const bool hit = ((valid >> k) & 1u) && __uint_as_float(val[k]) > cut;
+          store_record(rhit, base, __ballot(hit), hit, below, shift_of_bin(t + (uint32_t)k * T, to_i, n), val[k]);
         }
       }
     }
@@ -207,24 +175,8 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void scn_floor_kernel(ScnFloorAr
 
 template <int T, int KPT, bool REREAD>
 hipError_t launch(const ScnFloorArgs &a, int num_cus, hipStream_t stream) {
-  constexpr uint32_t block = T == 64 ? 256u : (uint32_t)T, teams = block / (uint32_t)T;
-  // persistent teams: as many workgroups as the runtime says are resident at once for this instantiation's registers and LDS
-  // (asked once per instantiation; at most 8 of 256 threads or 2 of 1024 per CU, the fallback should the query fail); no more
-  // workgroups than there are units to walk.  The workgroups share nothing: the grid's size is a matter of speed only.
-  static int per_cu = 0;  // (plans of several threads may race to the same answer)
-  if (per_cu <= 0) {
-    int q = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, scn_floor_kernel<T, KPT, REREAD>, (int)block, 0) != hipSuccess || q <= 0) {
-      (void)hipGetLastError();
-      q = block == 256u ? 8 : 2;
-    }
-    per_cu = q;
-  }
-  const uint32_t resident = (uint32_t)(num_cus > 0 ? num_cus : 256) * (uint32_t)per_cu;
-  uint32_t blocks = (a.n_units + teams - 1u) / teams;
-  if (blocks > resident) blocks = resident;
-  hipLaunchKernelGGL((scn_floor_kernel<T, KPT, REREAD>), dim3(blocks), dim3(block), 0, stream, a);
-  return hipGetLastError();
+  typedef Team<T> G;  // (the fallback: 8 workgroups of 256 threads or 2 of 1024 per CU)
+  return launch_teams<scn_floor_kernel<T, KPT, REREAD>, G::BLOCK, G::TEAMS>(0, G::BLOCK == 256u ? 8 : 2, a, num_cus, stream);
 }
 
 }  // namespace

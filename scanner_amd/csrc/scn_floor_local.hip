@@ -1,9 +1,8 @@
 // scn_floor_local.hip -- the floor detector with a floor window (scn_plan_set_floor_window; definition: scanner_hip.h, "Floor window").
 //
-// The same place as scn_floor.hip's kernel -- one kernel behind the transform, on the dB spectrum the spectrum-only specialisations
-// store -- and the same output: {i, power_db} records in the unit's region, in any order, and the unit's count.  Here every bin has
-// a floor of its own: the value of rank r_i among its reference cells, the evaluated bins guard < |i' - i| <= guard + train away in
-// fftshift order.  No FFT kernel is touched.
+// One kernel behind the transform, on the dB spectrum the spectrum-only specialisations store; its output: {i, power_db} records in
+// the unit's region, in any order, and the unit's count.  Every bin has a floor of its own: the value of rank r_i among its reference
+// cells, the evaluated bins guard < |i' - i| <= guard + train away in fftshift order.  The team model and the hit pass are scn_detect.h's.
 //
 // No selection is needed.  With the cells' values in key order v_(0) <= v_(1) <= ... and w_(k) = fl(v_(k) + threshold),
 //     power_db[j] > fl(v_(r_i) + threshold)   <=>   #{cells c : fl(c + threshold) < power_db[j]} >= r_i + 1,
@@ -14,9 +13,7 @@
 // r_i + 1 depends on (n, mask, train, guard, permille) alone: the host makes the table need[i] once per window (floor_window_ranks,
 // scn_host.hip: M_i from the mask, never from the values), 0 for a bin the mask removes, and the kernel reads 2 bytes per bin of it.
 //
-// Geometry (a TEAM of T threads per unit, persistent: teams walk units with the grid's stride), scn_floor.hip's:
-//   n <= 512          T = 64: a wave per unit, four units per 256-thread workgroup, wave barriers only
-//   n <= 4096         T = 256, above: T = 1024: a workgroup per unit
+// Sizes: n <= 512: T = 64, n <= 4096: T = 256, above: T = 1024.
 // Per unit and TILE of CAP = 4 T RUNS consecutive fftshift indices (one tile up to 16384 points, four at 65536), the team stages
 //   w[i] = evaluated ? fl(power_db + threshold) : +inf      (+inf is below nothing: a bin that is not a cell counts for nothing)
 // into LDS in fftshift order, with a halo of 192 = SCN_FLOOR_TRAIN_MAX + SCN_FLOOR_GUARD_MAX slots on either side -- the
@@ -26,35 +23,23 @@
 // bins of a run share their reads: a 16-byte chunk of cells is read once and held against all four.  Whether cell e of chunk q
 // belongs to bin k's window depends on 4 q + e - k, guard and train only -- the same in every lane, so the membership tests are
 // scalar, and a chunk that lies inside all four windows (most of them once train >= 8) takes 16 compare-and-count pairs straight.
-// Hit pass: scn_floor.hip's -- the wave counts its hits (ballots), takes that many slots of the unit's region with one LDS atomic,
-// and its lanes store their records at ballot-prefix positions through a buffer descriptor of exactly the region (hit_region = M
-// records: it cannot overflow); the loads go through descriptors of exactly the unit's spectrum and the table.
+// One slot grab per wave and tile; the table is read through a descriptor of exactly its length, as the spectrum is.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "../../include/scanner_hip.h"
-#include "scn_device.h"
+#include "scn_detect.h"
 
 namespace {
 
 constexpr uint32_t kHalo = SCN_FLOOR_TRAIN_MAX + SCN_FLOOR_GUARD_MAX;  // slots on either side of a tile (a multiple of 4)
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-template <int T>
-__device__ __forceinline__ void team_sync() {
-  if constexpr (T == 64) {  // a wave: its LDS operations complete in order
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  } else {
-    __syncthreads();
-  }
-}
-
 template <int T, int RUNS>
-struct LocalGeo {
-  static constexpr uint32_t BLOCK = T == 64 ? 256u : (uint32_t)T, TEAMS = BLOCK / (uint32_t)T;
+struct LocalGeo : Team<T> {
+  using Team<T>::TEAMS;
   static constexpr uint32_t CAP = 4u * (uint32_t)T * (uint32_t)RUNS;  // bins per tile
   static constexpr uint32_t SLOTS = CAP + 2u * kHalo;                 // floats of LDS per team
   static constexpr uint32_t LDS_BYTES = TEAMS * SLOTS * 4u + TEAMS * 4u;
@@ -64,7 +49,7 @@ template <int T, int RUNS>
 __global__ __launch_bounds__(T == 64 ? 256 : T) void scn_floor_local_kernel(ScnFloorLocalArgs a) {
   typedef LocalGeo<T, RUNS> G;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const uint32_t t = threadIdx.x % T, team = threadIdx.x / T, lane = threadIdx.x & 63u;
+  const uint32_t t = G::t(), team = G::team(), lane = G::lane();
   float *const s_w = reinterpret_cast<float *>(smem_raw) + team * G::SLOTS + kHalo;  // s_w[il]: the tile's bin il, -kHalo <= il < CAP + kHalo
   uint32_t *const s_count = reinterpret_cast<uint32_t *>(smem_raw + G::TEAMS * G::SLOTS * 4u) + team;
   const uint32_t n = a.n, half = n / 2u;
@@ -73,13 +58,11 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void scn_floor_local_kernel(ScnF
   const __amdgpu_buffer_rsrc_t rneed = make_rsrc(a.need, ((n + 3u) & ~3u) * 2u);
   for (uint32_t u0 = blockIdx.x * G::TEAMS + team; u0 < a.n_units; u0 += gridDim.x * G::TEAMS) {
     const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)u0);  // (the same in every lane of a wave)
-    const __amdgpu_buffer_rsrc_t rin = make_rsrc(a.power_db + (size_t)u * n, n * 4u);
-    const __amdgpu_buffer_rsrc_t rhit = make_rsrc(a.hits + (size_t)u * a.hit_region, a.hit_region * (uint32_t)sizeof(ScnDevHit));
+    const __amdgpu_buffer_rsrc_t rin = spectrum_rsrc(a, u), rhit = region_rsrc(a, u);
     // the bin at fftshift index i (which may lie outside the band): its value's bits, and whether it is a cell
     auto cell = [&](int i, uint32_t &bits) -> bool {
       const bool inside = (uint32_t)i < n;
-      uint32_t j = (inside ? (uint32_t)i : 0u) + half;  // j = (i + n / 2) % n (process.cpp:47)
-      j = j >= n ? j - n : j;
+      const uint32_t j = bin_of_shift(inside ? (uint32_t)i : 0u, half, n);
       bits = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rin, j * 4u, 0, 0);
       return inside && scn_bin_evaluated(j, (uint32_t)i, n, a);
     };
@@ -148,20 +131,13 @@ __global__ __launch_bounds__(T == 64 ? 256 : T) void scn_floor_local_kernel(ScnF
 #pragma unroll
       for (int b = 0; b < 4 * RUNS; b++) total += (uint32_t)__popcll(__ballot((hm >> b) & 1u));
       if (total) {
-        uint32_t slot = 0;
-        if (lane == 0) slot = atomicAdd(s_count, total);
-        slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot);
+        uint32_t slot = grab_slots(s_count, total, lane);
         const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
         for (int b = 0; b < 4 * RUNS; b++) {
           const bool hit = (hm >> b) & 1u;
-          const unsigned long long m = __ballot(hit);
-          const uint32_t pos = slot + (uint32_t)__popcll(m & below);
           const uint32_t i = tile0 + 4u * ((uint32_t)(b / 4) * T + t) + (uint32_t)(b % 4);
-          typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-          // (a lane without a hit stores outside the descriptor: dropped)
-          __builtin_amdgcn_raw_buffer_store_b64(u2{i, x[b / 4][b % 4]}, rhit, hit ? pos * (uint32_t)sizeof(ScnDevHit) : 0x80000000u, 0, 0);
-          slot += (uint32_t)__popcll(m);
+          store_record(rhit, slot, __ballot(hit), hit, below, i, x[b / 4][b % 4]);
         }
       }
       team_sync<T>();  // every wave is done with the tile's cells, and its grab is in s_count
@@ -179,24 +155,9 @@ hipError_t launch(const ScnFloorLocalArgs &a, int num_cus, hipStream_t stream) {
                                        (int)G::LDS_BYTES);
     if (e != hipSuccess) return e;
   }
-  // persistent teams: as many workgroups as the runtime says are resident at once for this instantiation's registers and LDS
-  // (asked once per instantiation; the fallback should the query fail: what its LDS alone allows, at most 8 of 256 threads or 2 of
-  // 1024 per CU); no more workgroups than there are units to walk.  The workgroups share nothing: the grid's size is a matter of
-  // speed only.
-  static int per_cu = 0;  // (plans of several threads may race to the same answer)
-  if (per_cu <= 0) {
-    int q = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, scn_floor_local_kernel<T, RUNS>, (int)G::BLOCK, G::LDS_BYTES) != hipSuccess || q <= 0) {
-      (void)hipGetLastError();
-      q = (int)std::min<uint32_t>(G::BLOCK == 256u ? 8u : 2u, std::max<uint32_t>(1u, 163840u / G::LDS_BYTES));
-    }
-    per_cu = q;
-  }
-  const uint32_t resident = (uint32_t)(num_cus > 0 ? num_cus : 256) * (uint32_t)per_cu;
-  uint32_t blocks = (a.n_units + G::TEAMS - 1u) / G::TEAMS;
-  if (blocks > resident) blocks = resident;
-  hipLaunchKernelGGL((scn_floor_local_kernel<T, RUNS>), dim3(blocks), dim3(G::BLOCK), G::LDS_BYTES, stream, a);
-  return hipGetLastError();
+  // (the fallback: what the LDS alone allows, at most 8 workgroups of 256 threads or 2 of 1024 per CU)
+  const int fallback = (int)std::min<uint32_t>(G::BLOCK == 256u ? 8u : 2u, std::max<uint32_t>(1u, 163840u / G::LDS_BYTES));
+  return launch_teams<scn_floor_local_kernel<T, RUNS>, G::BLOCK, G::TEAMS>(G::LDS_BYTES, fallback, a, num_cus, stream);
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// scn_mask.h -- the kernel-side arithmetic the host restates, K5's mask and the baseline row of a unit: shared by the kernels (through
+// scn_mask.h -- the kernel-side arithmetic the host restates, K5's mask, the baseline row of a unit and the detectors' grid: shared by the kernels (through
 // scn_kernels.h) and by the plan arithmetic of scn_host.hip, which a plain C++ compiler builds without a HIP header in sight.
 #pragma once
 #include <stdint.h>
@@ -21,4 +21,12 @@ SCN_HOST_DEVICE bool scn_bin_evaluated(uint32_t j, uint32_t i, uint32_t n, const
 SCN_HOST_DEVICE uint32_t scn_baseline_row(uint32_t first, uint32_t u, uint32_t rows) {
   const uint32_t s = first + u;
   return s < rows ? s : s % rows;
+}
+
+// The grid of a launch of persistent teams (scn_detect.h): ceil(n_units / teams) workgroups of `teams` teams each, capped at what is
+// resident at once, per_cu workgroups on each of num_cus CUs (256 CUs where the count is unknown).
+SCN_HOST_DEVICE uint32_t scn_team_grid(uint32_t n_units, uint32_t teams, int num_cus, int per_cu) {
+  const uint32_t resident = (uint32_t)(num_cus > 0 ? num_cus : 256) * (uint32_t)per_cu;
+  const uint32_t blocks = n_units / teams + (n_units % teams != 0u ? 1u : 0u);  // (n_units + teams - 1 wraps from 2^32 - teams + 1 units up)
+  return blocks < resident ? blocks : resident;
 }

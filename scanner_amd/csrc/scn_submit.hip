@@ -132,34 +132,13 @@ int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float
   }
 }
 
-// Floor plans: the detect kernel on the spectrum the transform has just stored, behind it on the slot's stream; nu units
-int launch_floor(scn_plan *p, Slot &s, const float *d_power, uint32_t nu) {
-  if (p->floor_train) {  // a floor window: every bin against the rank among its own reference cells (scn_floor_local.hip)
-    ScnFloorLocalArgs a;
-    memset(&a, 0, sizeof(a));
-    a.power_db = d_power;
-    a.n = p->d.n;
-    a.n_units = nu;
-    a.train = p->floor_train;
-    a.guard = p->floor_guard;
-    a.permille = p->floor_permille;
-    a.need = p->d_floor_need.get();
-    a.threshold = p->d.threshold;
-    a.dc_ignore = p->d.dc_ignore_bins;
-    a.i_lo = p->i_lo;
-    a.i_hi = p->i_hi;
-    a.hits = s.d_hits[s.gen].get();
-    a.hit_region = p->hit_region;
-    a.counts = s.d_buf_hits[s.gen].get();
-    SCN_HIP(scn_launch_floor_local(a, p->num_cus, s.stream));
-    return SCN_OK;
-  }
-  ScnFloorArgs a;
+// The spectrum, the mask and the hit outputs: the fields every detect kernel's argument struct carries under the same names
+template <class A>
+void set_detect_args(A &a, const scn_plan *p, const Slot &s, const float *d_power, uint32_t nu) {
   memset(&a, 0, sizeof(a));
   a.power_db = d_power;
   a.n = p->d.n;
   a.n_units = nu;
-  a.rank = p->floor_rank;
   a.threshold = p->d.threshold;
   a.dc_ignore = p->d.dc_ignore_bins;
   a.i_lo = p->i_lo;
@@ -167,6 +146,23 @@ int launch_floor(scn_plan *p, Slot &s, const float *d_power, uint32_t nu) {
   a.hits = s.d_hits[s.gen].get();
   a.hit_region = p->hit_region;
   a.counts = s.d_buf_hits[s.gen].get();
+}
+
+// Floor plans: the detect kernel on the spectrum the transform has just stored, behind it on the slot's stream; nu units
+int launch_floor(scn_plan *p, Slot &s, const float *d_power, uint32_t nu) {
+  if (p->floor_train) {  // a floor window: every bin against the rank among its own reference cells (scn_floor_local.hip)
+    ScnFloorLocalArgs a;
+    set_detect_args(a, p, s, d_power, nu);
+    a.train = p->floor_train;
+    a.guard = p->floor_guard;
+    a.permille = p->floor_permille;
+    a.need = p->d_floor_need.get();
+    SCN_HIP(scn_launch_floor_local(a, p->num_cus, s.stream));
+    return SCN_OK;
+  }
+  ScnFloorArgs a;
+  set_detect_args(a, p, s, d_power, nu);
+  a.rank = p->floor_rank;
   a.floor_db = s.d_floor.get();
   SCN_HIP(scn_launch_floor(a, p->num_cus, s.stream));
   return SCN_OK;
@@ -175,20 +171,10 @@ int launch_floor(scn_plan *p, Slot &s, const float *d_power, uint32_t nu) {
 // Baseline plans: the detect kernel in the same place, unit u against row (first + u) % rows of the plan's baseline
 int launch_baseline(scn_plan *p, Slot &s, const float *d_power, uint32_t nu, uint32_t first) {
   ScnBaselineArgs a;
-  memset(&a, 0, sizeof(a));
-  a.power_db = d_power;
+  set_detect_args(a, p, s, d_power, nu);
   a.baseline_db = p->d_baseline.get();
-  a.n = p->d.n;
-  a.n_units = nu;
   a.rows = p->baseline_rows;
   a.first = first % p->baseline_rows;  // (begin_submit refused a plan without rows)
-  a.threshold = p->d.threshold;
-  a.dc_ignore = p->d.dc_ignore_bins;
-  a.i_lo = p->i_lo;
-  a.i_hi = p->i_hi;
-  a.hits = s.d_hits[s.gen].get();
-  a.hit_region = p->hit_region;
-  a.counts = s.d_buf_hits[s.gen].get();
   SCN_HIP(scn_launch_baseline_detect(a, p->num_cus, s.stream));
   return SCN_OK;
 }

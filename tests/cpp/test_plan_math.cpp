@@ -248,6 +248,26 @@ static void test_floor_from_spectrum() {
   CHECK(floor_permille_of(1000, &permille) && permille == 1000 && !floor_permille_of(1001, &permille));
 }
 
+// The detect kernels' grid (scn_mask.h): ceil(n_units / teams) workgroups, capped at num_cus * per_cu, 256 CUs where the count is unknown
+static void test_team_grid() {
+  for (int num_cus : {0, 64, 256, 304})
+    for (int per_cu : {1, 2, 8}) {
+      for (uint32_t nu = 1; nu <= 4; nu++) CHECK(scn_team_grid(nu, 4, num_cus, per_cu) == 1);
+      CHECK(scn_team_grid(5, 4, num_cus, per_cu) == 2);
+      CHECK(scn_team_grid(9, 1, num_cus, per_cu) == 9);
+    }
+  CHECK(scn_team_grid(1000000, 4, 256, 8) == 2048);  // capped
+  for (int num_cus : {0, -1, -256}) CHECK(scn_team_grid(10000, 1, num_cus, 2) == 512);
+  // the largest submit the C-ABI carries: scn_plan_desc.max_batch is a uint32_t with a lower bound only, and a submit may fill it.
+  // n_units + teams - 1 would wrap there (to 2, a grid of 0 workgroups): the quotient and the remainder do not.
+  const uint32_t max_batch = UINT32_MAX;
+  for (int num_cus : {0, 64, 256}) CHECK(scn_team_grid(max_batch, 4, num_cus, 8) == (uint32_t)(num_cus > 0 ? num_cus : 256) * 8u);
+  CHECK(scn_team_grid(max_batch, 4, 1 << 20, 1 << 10) == (1u << 30));  // ceil((2^32 - 1) / 4), under a cap that equals it
+  for (uint32_t back = 0; back < 3; back++) CHECK(scn_team_grid(max_batch - back, 4, 1 << 20, 1 << 11) == (1u << 30));  // the three that would wrap
+  CHECK(scn_team_grid(max_batch - 3u, 4, 1 << 20, 1 << 11) == (1u << 30) - 1u);  // 2^32 - 4: whole workgroups, the last that does not
+  CHECK(scn_team_grid(max_batch, 1, 1 << 20, 1 << 11) == (1u << 31));  // capped by 2^31 resident
+}
+
 int main() {
   test_host_fft();
   test_twiddles();
@@ -263,6 +283,7 @@ int main() {
   test_hackrf_fixup();
   test_signals_from_hits();
   test_floor_from_spectrum();
+  test_team_grid();
   CHECK(std::strcmp(scn_error_name(SCN_E_TRUNCATED), "SCN_E_TRUNCATED") == 0 && scn_abi_version() == SCN_ABI_VERSION);
   if (g_failed) return 1;
   std::printf("plan math tests ok\n");
