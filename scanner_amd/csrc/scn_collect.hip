@@ -11,15 +11,15 @@ namespace {
 // structs: the regions, the hits' offsets, and the submit's header fields where they lie (the slot's pinned copy or the plan's table)
 template <class A>
 void set_list_source(A &a, const scn_plan *p, const Slot &s) {
-  a.regions = s.d_hits[s.gen].get();
+  const SlotGen &g = s.cur();
+  a.regions = g.d_hits.get();
   a.hit_region = p->hit_region;
   a.offsets = s.d_offsets.get();
-  const double *const h_fc = s.h_meta.get() + (size_t)2u * p->d.max_batch * s.gen;
-  const bool table = s.table_first[s.gen] >= 0;
-  a.center_freq = table ? p->d_table.get() : h_fc;
+  const bool table = g.table_first >= 0;
+  a.center_freq = table ? p->d_table.get() : s.centres(p->d.max_batch);
   a.table_count = table ? p->table_count : 0u;
-  a.table_first = table ? (uint32_t)s.table_first[s.gen] : 0u;
-  a.seq_id = s.seq_given[s.gen] ? reinterpret_cast<const uint64_t *>(h_fc + p->d.max_batch) : nullptr;
+  a.table_first = table ? (uint32_t)g.table_first : 0u;
+  a.seq_id = g.seq_given ? s.seq_ids(p->d.max_batch) : nullptr;
   a.n_buffers = s.n_buffers;
   a.n = p->d.n;
   a.sample_rate = p->d.sample_rate;
@@ -32,7 +32,7 @@ hipStream_t topup_stream_of(const scn_plan *p, const Slot &s) { return s.own_str
 int fetch_list(scn_plan *p, Slot &s, uint32_t count) {
   if (!s.list_built)
     if (int st = build_list(p, s, false)) return st;
-  SCN_HIP(hipEventSynchronize(s.list_done[s.gen].get()));
+  SCN_HIP(hipEventSynchronize(s.cur().list_done.get()));
   count = std::min(count, p->d.max_hits);
   if (count > s.prefetched) {
     // the prediction was short: copy the rest now.  NOT on the list stream: the other slot's list may be queued there
@@ -52,7 +52,7 @@ int fetch_list(scn_plan *p, Slot &s, uint32_t count) {
 ScnCompactArgs compact_args(const scn_plan *p, const Slot &s, uint32_t first, uint32_t cap, void *out) {
   ScnCompactArgs c;
   set_list_source(c, p, s);
-  c.counts = s.d_buf_hits[s.gen].get();
+  c.counts = s.cur().d_buf_hits.get();
   c.out = out;
   c.first = first;
   c.out_cap = std::min<uint32_t>(cap, 0x7fffffffu - first);  // first + out_cap must not wrap
@@ -79,14 +79,14 @@ int build_list(scn_plan *p, Slot &s, bool prefetch) {
   hipStream_t last = aux;
   if (s.prefetched) {
     if (!s.own_stream) {  // (a slot with a stream of its own keeps its whole chain there: its next kernel is several submits away)
-      SCN_HIP(hipEventRecord(s.list_done[s.gen].get(), aux));
-      SCN_HIP(hipStreamWaitEvent(p->d2h_stream.get(), s.list_done[s.gen].get(), 0));
+      SCN_HIP(hipEventRecord(s.cur().list_done.get(), aux));
+      SCN_HIP(hipStreamWaitEvent(p->d2h_stream.get(), s.cur().list_done.get(), 0));
       last = p->d2h_stream.get();
     }
     SCN_HIP(hipMemcpyAsync(s.h_list.get(), s.d_list.get(), sizeof(scn_hit) * (size_t)s.prefetched, hipMemcpyDeviceToHost, last));
   }
-  SCN_HIP(hipEventRecord(s.list_done[s.gen].get(), last));
-  s.list_used[s.gen] = true;
+  SCN_HIP(hipEventRecord(s.cur().list_done.get(), last));
+  s.cur().list_used = true;
   s.list_built = true;
   return SCN_OK;
 }
@@ -134,7 +134,7 @@ int scn_collect(scn_plan *p, int slot, float *power_db, scn_hit *hits, uint32_t 
   if (power_db && !s.cur_power) return scn_fail(SCN_E_INVALID, "plan was created without SCN_OUT_SPECTRUM");
 
   uint64_t total = 0;
-  if (have_hits && nb && s.total_ready) {
+  if (have_hits && nb && s.route.counts == Counts::Reduced) {
     total = *s.h_total;
     if (trigger)  // process.cpp:62, one bit per buffer from the GPU
       for (uint32_t b = 0; b < nb; b++) trigger[b] = (uint8_t)((s.h_buf_hits.get()[b >> 5] >> (b & 31u)) & 1u);
@@ -298,8 +298,8 @@ int scn_plan_device_hits(scn_plan *p, int slot, const scn_hit **d_list, uint32_t
   if (s.total_hits) {
     if (!s.list_built)
       if ((st = build_list(p, s, false))) return st;
-    if (list_ready) *list_ready = (void *)s.list_done[s.gen].get();
-    else SCN_HIP(hipEventSynchronize(s.list_done[s.gen].get()));
+    if (list_ready) *list_ready = (void *)s.cur().list_done.get();
+    else SCN_HIP(hipEventSynchronize(s.cur().list_done.get()));
   }
   *d_list = s.d_list.get();
   *n = s.total_hits;

@@ -46,3 +46,35 @@ int check_baseline_range(uint32_t have, uint32_t first_row, uint32_t rows);
 int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc);
 uint32_t group_headers(uint32_t k, bool sweeps, uint32_t nb, const double *&fc, const uint64_t *&seq, std::vector<double> &group_fc,
                        std::vector<uint64_t> &group_seq);
+
+// The route of a submit: what follows the transform, on which stream, behind which event -- decided once by submit_route from the
+// numbers below and only executed by submit_common (scn_submit.hip); tests/cpp/test_submit_route.cpp enumerates the table.
+// The thresholds (each measured: the notes stand at the branches of submit_route, scn_host.hip):
+#ifndef SCN_TOTAL_KERNEL_FROM
+#define SCN_TOTAL_KERNEL_FROM (1u << 18)
+#endif
+constexpr uint32_t kTotalKernelFrom = SCN_TOTAL_KERNEL_FROM;  // units per launch from which a reduction on the GPU replaces the counts' DMA
+constexpr uint32_t kStoredCountsUpTo = 4096;                  // units per launch up to which a fused kernel stores the counts to pinned memory itself
+constexpr uint64_t kPacketEventFrom = 1ull << 25;             // samples per launch from which a fused kernel's own dispatch packet completes the event
+
+struct SubmitShape {
+  bool hits;           // the plan reports hits (SCN_OUT_HITS)
+  bool fused;          // the transform is the submit's last kernel and can store counts and complete an event itself: a fused path, not averaged, no detect kernel behind it
+  bool direct_counts;  // the plan's (scn_plan::direct_counts; fused plans only)
+  bool own_stream;     // the slot has a stream of its own (SCN_PLAN_OVERLAP_SLOTS)
+  bool list_wanted;    // the plan's previous collect took records or a device list
+  uint32_t n, units;   // points per transform; buffers per launch, or groups on an averaged plan
+};
+enum class Counts { None, Stored, Dma, Reduced };  // no hits or no units; by the kernel's own stores to pinned memory; by a DMA; the total + trigger bitmap of scn_hit_total_kernel
+enum class RouteStream { Slot, D2H };
+enum class KernelEnd { None, Done, KernelDone };  // the event that marks the end of the submit's last compute kernel
+struct SubmitRoute {
+  Counts counts = Counts::None;
+  RouteStream counts_stream = RouteStream::Slot;  // carries the counts, a floor plan's floors and `done` behind them; D2H waits for `end`
+  bool list_behind = false;                       // the ordered list is built behind the launch ...
+  bool list_forks = false;                        // ... on the plan's list stream, which waits for `end` (else: on the slot's own)
+  KernelEnd end = KernelEnd::None;
+  bool end_in_packet = false;                     // the kernel's dispatch packet completes `end` (else a marker behind the kernel on the slot's stream)
+  bool done_behind_counts = false;                // `done` is recorded on counts_stream behind the counts (else `end` is `done`)
+};
+SubmitRoute submit_route(const SubmitShape &in);

@@ -246,6 +246,56 @@ uint32_t group_headers(uint32_t k, bool sweeps, uint32_t nb, const double *&fc, 
   return ng;
 }
 
+// What follows the kernel of a submit: the counts (a DMA on the d2h stream: needs no CU -- or nothing, when the kernel stores them
+// to pinned memory itself) and, when the caller is known to want records, the ordered list (two small kernels + a DMA on the list
+// stream, beside the next launch).  With overlapped slots both follow the kernel on the slot's own stream -- its next kernel is
+// two submits away, and fewer streams keep both compute streams on hardware queues of their own (HIP maps streams onto 4 queues
+// by default; with a fifth active stream the two compute streams ended up sharing one).
+SubmitRoute submit_route(const SubmitShape &in) {
+  SubmitRoute r;
+  const bool counted = in.hits && in.units != 0;
+  r.list_behind = counted && in.list_wanted;  // (an eager submit)
+  r.list_forks = r.list_behind && !in.own_stream;
+  // The per-buffer counts reach the host either by a DMA behind the kernel or by the kernel's own stores to pinned memory.
+  // Both have a price (profiles/r04_experiments.md section 10).  A store over PCIe holds its wave's in-order memory returns up:
+  // ~0.4 ns per buffer on the launch (8192 buffers: 73.5 -> 76.7 us; 32768 1024-point buffers: 75 -> 96 us).  A DMA that waits
+  // for a kernel or for another DMA starts ~20 us after it (the runtime resolves the dependency on the host): nothing in a
+  // steady loop of long launches, but the whole difference for short ones (2048 buffers per launch, three in flight: 25.5
+  // -> 19.3 us per step), and fatal when the ordered list's DMA shares the D2H stream with it (two per submit: 92 us per submit
+  // on that stream against 73 us of FFT; records read in place, three in flight: 373 .. 403 -> 429 Gsamples/s).  So the kernel
+  // stores the counts itself when the launch has few buffers or the list follows eagerly, and a DMA carries them otherwise.
+  // (floor and baseline plans take the route of the paths that are not fused: the detect kernel, not the transform, is the submit's last
+  //  kernel, and it stores the counts to device memory only -- counts by DMA or scn_hit_total_kernel, a marker event behind it)
+  const bool stored = in.fused && (in.direct_counts || in.units <= kStoredCountsUpTo || r.list_behind);
+  // Launches of very many small buffers: the total and the trigger flags (a bit per buffer) by themselves -- the counts stay on
+  // the GPU, where the list kernels read them: units / 8 bytes cross PCIe instead of 4 units, and a collect walks nothing.  The
+  // reduction (scn_hit_total_kernel) runs behind the kernel ON ITS STREAM and stores into pinned memory itself: such a step is bound
+  // by the HOST's calls (a 16-point launch of 524288 buffers takes 27 us on the GPU, every HIP call 4 .. 5 us in a torch process),
+  // and this way a submit is three of them -- kernel, reduction, event -- where the route over the side stream took six (event,
+  // wait, reduction, DMA, event: 72 -> 56 us per step, profiles/r06_experiments.md section 5).  The reduction takes ~6 us of the
+  // compute stream per launch; the counts' DMA it replaces runs beside the next launch but costs three more host calls and 4 bytes
+  // per buffer of PCIe.  Measured on one box (profiles/r06_total_ab.txt, us per step of the spectrum + hits leg, counts by DMA ->
+  // reduction): 524288 x 16 points 56.5 -> 37.1, 262144 x 64: 74.0 -> 51.5, 262144 x 128: 88.1 -> 82.6, but 131072 x 256: 75.0 ->
+  // 81.8, 65536 x 512: 75.0 -> 80.9, 32768 x 1024: 74.8 -> 81.9 -- it pays from 2^18 buffers per launch.  (Round 5's form -- the
+  // reduction on a side stream behind an event, the flags still by DMA -- paid only from 2^19: profiles/r05_table_ab.txt.)
+  // Not when the list forks: this way records no event behind the kernel, and the list stream would wait for none.  Such a submit
+  // takes the DMA way of the same plans below the threshold; what that costs at 2^18 units has never been measured.
+  const bool reduced = counted && !stored && in.units >= kTotalKernelFrom && !r.list_forks;
+  r.counts = !counted ? Counts::None : stored ? Counts::Stored : reduced ? Counts::Reduced : Counts::Dma;
+  r.counts_stream = (r.counts == Counts::Dma && !in.own_stream) ? RouteStream::D2H : RouteStream::Slot;
+  // ONE event marks the kernel's end for whoever waits for it: the host (`done`, when nothing else follows on the compute
+  // stream: counts stored by the kernel, or no counts at all) or the side streams (`kernel_done`); none where everything that
+  // follows stays on the slot's stream.  For LARGE launches it is completed by the kernel's own dispatch packet
+  // (hipExtLaunchKernel's stopEvent), otherwise by a marker packet behind the kernel.
+  // Measured (scripts/stop_event_check.sh, profiles/r02_stop_event.txt), us per step marker -> in-packet: 33.5 M-sample
+  // launches 75.6 -> 73.1 (4096-pt cfloat), 77 -> 74.5 (2048-pt), 60.2 -> 59.3 (int16); 67 M samples 144.5 -> 140.8; but
+  // 16.8 M samples 44 -> 46..58 and 8.4 M 31 -> 29..56 (erratic: short kernels that carry an event get serialised).
+  if (in.units != 0 && !in.own_stream && !reduced) r.end = r.counts_stream == RouteStream::D2H ? KernelEnd::KernelDone : KernelEnd::Done;
+  r.end_in_packet = r.end != KernelEnd::None && in.fused && (uint64_t)in.units * in.n >= kPacketEventFrom;
+  r.done_behind_counts = r.end != KernelEnd::Done;
+  return r;
+}
+
 extern "C" {
 
 const char *scn_error_name(int status) {

@@ -24,6 +24,19 @@
                       hipGetErrorString(e_));                                                      \
   } while (0)
 
+// Everything the FFT kernel writes for the hit list has TWO generations per slot, alternating per submit: the
+// compaction of submit k may still be running (beside launch k+1) when launch k+2 starts writing -- with a
+// generation of its own nothing has to wait, neither the host at submit nor the compute stream behind a barrier
+// packet (measured: ~10 us per launch even when the barrier is already satisfied, ~16 us when it is not).
+struct SlotGen {
+  ScnDeviceMem<ScnDevHit> d_hits;     // [max_batch][hit_region] per-buffer hit regions (unordered, scn_kernels.hip)
+  ScnDeviceMem<uint32_t> d_buf_hits;  // [max_batch] hits per buffer
+  ScnEvent list_done;                 // scan + compaction (+ prefetch) finished
+  bool list_used = false;             // ... and whether that event has ever been recorded
+  bool seq_given = false;             // the submit came with sequence ids (else: the buffer's index)
+  int64_t table_first = -1;           // the submit named a range of the plan's frequency table (else -1: its own centres in h_meta)
+};
+
 struct Slot {
   ScnStream owned_stream;           // SCN_PLAN_OVERLAP_SLOTS, slots 1 ... : `stream` below when own_stream (first: destroyed last)
   ScnDeviceMem<char> d_gen_work[2];  // scratch of the four-step and Bluestein paths (launch_transform)
@@ -33,22 +46,21 @@ struct Slot {
   ScnDeviceMem<float> d_power;      // [max_batch][N] dB spectra (plan-owned destination)
   float *cur_power = nullptr;       // destination of the pending submit (d_power or the caller's; nullptr: the caller collects none)
   ScnPinnedMem<float> h_td;         // time-domain mode: [2][max_batch] max / min dB, pinned, kernel-written
-  // [max_batch] hits per buffer.  The kernel writes device memory; a 4*n_buffers-byte D2H copy on
+  SlotGen gen_state[2];             // the hit outputs, one record per generation
+  uint32_t gen = 0;                 // generation of the pending / last submit
+  SlotGen &cur() { return gen_state[gen]; }
+  const SlotGen &cur() const { return gen_state[gen]; }
+  // [max_batch] hits per buffer.  The kernel writes device memory (SlotGen::d_buf_hits); a 4*n_buffers-byte D2H copy on
   // the plan's d2h stream (ordered behind the kernel by an event) brings them to the pinned copy,
   // so the compute stream carries nothing but the kernel.  (Letting the kernel store to pinned
   // host memory directly was measured: the PCIe acknowledgements delay every kernel's completion
   // by ~4 us, 5 % of a C2 launch.)
-  // Everything the FFT kernel writes for the hit list has TWO generations per slot, alternating per submit: the
-  // compaction of submit k may still be running (beside launch k+1) when launch k+2 starts writing -- with a
-  // generation of its own nothing has to wait, neither the host at submit nor the compute stream behind a barrier
-  // packet (measured: ~10 us per launch even when the barrier is already satisfied, ~16 us when it is not).
-  uint32_t gen = 0;                 // generation of the pending / last submit
-  ScnDeviceMem<uint32_t> d_buf_hits[2];
   ScnPinnedMem<uint32_t> h_buf_hits;
   unsigned long long *h_total = nullptr;  // pinned (the tail of h_buf_hits): the batch's total, stored by scn_hit_total_kernel
   ScnDeviceMem<unsigned long long> d_total_acc;  // its two device words
-  bool total_ready = false;         // the pending / last submit's total is (going to be) in *h_total and its trigger flags, one bit per buffer, in the
-                                    // front of h_buf_hits: the counts themselves stayed on the GPU and scn_collect walks nothing
+  // the route of the pending / last submit.  counts == Counts::Reduced: its total is (going to be) in *h_total and its trigger flags, one
+  // bit per buffer, in the front of h_buf_hits: the counts themselves stayed on the GPU and scn_collect walks nothing
+  SubmitRoute route;
   ScnEvent kernel_done, staged;
   hipStream_t stream = nullptr;     // where this slot's kernels run: the plan's compute stream, or its own (SCN_PLAN_OVERLAP_SLOTS)
   // buffer-queue heads of the persistent workgroups (ScnFftArgs::work_counter; 8 heads, never reset) and their values
@@ -56,20 +68,17 @@ struct Slot {
   ScnDeviceMem<uint32_t> d_work_counter;
   uint32_t work_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool own_stream = false;
-  ScnDeviceMem<ScnDevHit> d_hits[2];  // [max_batch][hit_region] per-buffer hit regions (unordered, scn_kernels.hip)
   // the ordered list (scn_hits.hip): offsets = exclusive scan of the counts; h_meta = the submit's MessageHeader
   // fields, pinned, read by the compaction kernel in place; d_list = the first max_hits completed records; h_list =
   // their pinned host copy (prefetched of them are there); d_window = where scn_collect_more re-runs the compaction
   // for a window beyond max_hits
   ScnDeviceMem<uint32_t> d_offsets;
-  ScnPinnedMem<double> h_meta;      // pinned, two generations of {[max_batch] doubles, [max_batch] u64}
+  ScnPinnedMem<double> h_meta;      // pinned, two generations of {[max_batch] doubles, [max_batch] u64}: the current one's arrays
+  double *centres(uint32_t max_batch) const { return h_meta.get() + (size_t)2u * max_batch * gen; }
+  uint64_t *seq_ids(uint32_t max_batch) const { return reinterpret_cast<uint64_t *>(centres(max_batch) + max_batch); }
   ScnDeviceMem<scn_hit> d_list;     // device [max_hits]
   ScnPinnedMem<scn_hit> h_list;     // pinned [max_hits]
   uint32_t prefetched = 0;          // leading records of the current list that are (being) copied to h_list
-  ScnEvent list_done[2];                         // per generation: scan + compaction (+ prefetch) finished
-  bool list_used[2] = {false, false};            // ... and whether that event has ever been recorded
-  bool seq_given[2] = {false, false};            // per generation: the submit came with sequence ids (else: the buffer's index)
-  int64_t table_first[2] = {-1, -1};             // per generation: the submit named a range of the plan's frequency table (else -1: its own centres in h_meta)
   bool list_valid = false;          // regions, counts and offsets of the last collected submit are still on the device
   bool list_built = false;          // the scan + compaction of the pending / last submit have been enqueued
   uint32_t total_hits = 0;          // of the last collected submit

@@ -96,10 +96,10 @@ int ensure_slot_outputs(scn_plan *p, Slot &s, uint32_t gen) {
   if (p->d.flags & SCN_OUT_HITS) {
     // every resource under its own check: a failed allocation leaves a state the next call completes or fails on again
     const size_t mb = p->d.max_batch;
-    const uint32_t g = gen & 1u;
-    SCN_HIP(s.d_hits[g].alloc(p->hit_region * mb));
-    SCN_HIP(s.d_buf_hits[g].alloc(mb));
-    SCN_HIP(s.list_done[g].create());
+    SlotGen &g = s.gen_state[gen & 1u];
+    SCN_HIP(g.d_hits.alloc(p->hit_region * mb));
+    SCN_HIP(g.d_buf_hits.alloc(mb));
+    SCN_HIP(g.list_done.create());
     if (!s.h_buf_hits) {
       SCN_HIP(s.h_buf_hits.alloc(mb + 4u));
       s.h_total = reinterpret_cast<unsigned long long *>(s.h_buf_hits.get() + ((mb + 1u) & ~(size_t)1u));

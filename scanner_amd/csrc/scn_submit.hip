@@ -9,18 +9,6 @@
 
 namespace {
 
-// Buffers per launch from which the batch's total and its trigger flags come from a reduction on the GPU (scn_hit_total_kernel, on the
-// launch's own stream, storing into pinned memory) instead of the counts crossing PCIe and the host walking them.  The reduction takes
-// ~6 us of the compute stream per launch; the counts' DMA it replaces runs beside the next launch but costs three more host calls and
-// 4 bytes per buffer of PCIe.  Measured on one box (profiles/r06_total_ab.txt, us per step of the spectrum + hits leg, counts by DMA ->
-// reduction): 524288 x 16 points 56.5 -> 37.1, 262144 x 64: 74.0 -> 51.5, 262144 x 128: 88.1 -> 82.6, but 131072 x 256: 75.0 -> 81.8,
-// 65536 x 512: 75.0 -> 80.9, 32768 x 1024: 74.8 -> 81.9 -- it pays from 2^18 buffers per launch.  (Round 5's form -- the reduction on
-// a side stream behind an event, the flags still by DMA -- paid only from 2^19: profiles/r05_table_ab.txt.)
-#ifndef SCN_TOTAL_KERNEL_FROM
-#define SCN_TOTAL_KERNEL_FROM (1u << 18)
-#endif
-constexpr uint32_t kTotalKernelFrom = SCN_TOTAL_KERNEL_FROM;
-
 // The input, the window and the K4 / K5 epilogue: the fields every transform's argument struct carries under the same names
 template <class A>
 void set_common_args(A &a, const scn_plan *p, const Slot &s, const void *d_raw, uint32_t nb, float *d_power) {
@@ -33,15 +21,23 @@ void set_common_args(A &a, const scn_plan *p, const Slot &s, const void *d_raw, 
   a.dc_ignore = p->d.dc_ignore_bins;
   a.i_lo = p->i_lo;
   a.i_hi = p->i_hi;
-  a.hits = s.d_hits[s.gen].get();
+  a.hits = s.cur().d_hits.get();
   a.hit_region = p->hit_region;
-  a.per_buffer_hits = s.d_buf_hits[s.gen].get();
+  a.per_buffer_hits = s.cur().d_buf_hits.get();
 }
 
+// The slot's handles for the names of its route (SubmitRoute, scn_host.h)
+hipEvent_t end_event_of(const Slot &s) {
+  return s.route.end == KernelEnd::Done ? s.done.get() : s.route.end == KernelEnd::KernelDone ? s.kernel_done.get() : nullptr;
+}
+hipStream_t counts_stream_of(const scn_plan *p, const Slot &s) { return s.route.counts_stream == RouteStream::D2H ? p->d2h_stream.get() : s.stream; }
+
 // The transform of a submit on the slot's stream: the only code that knows which launcher and which argument struct a path
-// uses.  host_hits: where a fused kernel stores the counts as well (or nullptr); stop: an event a fused kernel's own
-// dispatch packet completes (or nullptr)
-int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float *d_power, uint32_t *host_hits, hipEvent_t stop) {
+// uses.  From the slot's route: where a fused kernel stores the counts as well (host_hits, or nullptr), and the event a fused
+// kernel's own dispatch packet completes (stop, or nullptr)
+int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float *d_power) {
+  uint32_t *const host_hits = s.route.counts == Counts::Stored ? s.h_buf_hits.get() : nullptr;
+  const hipEvent_t stop = s.route.end_in_packet ? end_event_of(s) : nullptr;
   const uint32_t n = p->d.n;
   const int kind = (int)p->d.sample_kind;
   // (a floor or baseline plan's transform reports the spectrum only: its hits come from the detect kernel behind it, launch_floor / launch_baseline)
@@ -70,9 +66,9 @@ int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float
     a.dc_ignore = p->d.dc_ignore_bins;
     a.i_lo = p->i_lo;
     a.i_hi = p->i_hi;
-    a.hits = s.d_hits[s.gen].get();
+    a.hits = s.cur().d_hits.get();
     a.hit_region = p->hit_region;
-    a.per_group_hits = s.d_buf_hits[s.gen].get();
+    a.per_group_hits = s.cur().d_buf_hits.get();
     SCN_HIP(scn_launch_average(kind, dc && kind != SCN_KIND_FLOAT_COMPLEX, hits, d_power != nullptr, a, p->num_cus, s.stream));
     return SCN_OK;
   }
@@ -143,9 +139,9 @@ void set_detect_args(A &a, const scn_plan *p, const Slot &s, const float *d_powe
   a.dc_ignore = p->d.dc_ignore_bins;
   a.i_lo = p->i_lo;
   a.i_hi = p->i_hi;
-  a.hits = s.d_hits[s.gen].get();
+  a.hits = s.cur().d_hits.get();
   a.hit_region = p->hit_region;
-  a.counts = s.d_buf_hits[s.gen].get();
+  a.counts = s.cur().d_buf_hits.get();
 }
 
 // Floor plans: the detect kernel on the spectrum the transform has just stored, behind it on the slot's stream; nu units
@@ -227,7 +223,6 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   s.list_valid = false;
   const bool hits = (p->d.flags & SCN_OUT_HITS) != 0;
   s.list_built = false;
-  s.total_ready = false;
   if (hits && nb) {
     // this submit's generation; the only thing that can still be using it is the list (compaction + copy) of the submit TWO
     // submits back ON THIS SLOT -- 2 x (slots in use) launches back on the plan -- wait for it on the host, where it never
@@ -237,85 +232,42 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
     // next compaction must not start while it may still be reading d_list (a caller that collected counts only has not
     // waited for it).  Both waits are host-side queries of events that completed long ago in any steady loop.
     s.gen ^= 1u;
-    for (uint32_t g = 0; g < 2; g++)
-      if (s.list_used[g] && hipEventQuery(s.list_done[g].get()) != hipSuccess) SCN_HIP(hipEventSynchronize(s.list_done[g].get()));
+    for (const SlotGen &g : s.gen_state)
+      if (g.list_used && hipEventQuery(g.list_done.get()) != hipSuccess) SCN_HIP(hipEventSynchronize(g.list_done.get()));
     // the header fields: read by the compaction kernel in place, over PCIe (two 8-byte reads per buffer that has hits;
     // staging copies cost ~7 us each plus ~10 us of cross-engine hand-off, on the list's critical path)
-    double *h_fc = s.h_meta.get() + (size_t)2u * p->d.max_batch * s.gen;
-    uint64_t *h_seq = reinterpret_cast<uint64_t *>(h_fc + p->d.max_batch);
     // the centres: copied when given; a submit that names a range of the plan's device-resident table writes none (the other
     // 8 header bytes per buffer: 2 MB per launch of 262144 128-point buffers, written and then read back over PCIe)
-    s.table_first[s.gen] = fc ? -1 : (int64_t)table_first;
-    if (fc) memcpy(h_fc, fc, sizeof(double) * nb);
+    s.cur().table_first = fc ? -1 : (int64_t)table_first;
+    if (fc) memcpy(s.centres(p->d.max_batch), fc, sizeof(double) * nb);
     // sequence ids: copied when given; otherwise a buffer's id is its index and the compaction kernel computes it -- 8 of the
     // 16 header bytes per buffer that made the 16 .. 128-point steps host-bound (524288 buffers per launch: 4 MB less to write)
-    s.seq_given[s.gen] = seq != nullptr;
-    if (seq) memcpy(h_seq, seq, sizeof(uint64_t) * nb);
+    s.cur().seq_given = seq != nullptr;
+    if (seq) memcpy(s.seq_ids(p->d.max_batch), seq, sizeof(uint64_t) * nb);
   }
 
-  // The per-buffer counts reach the host either by a DMA behind the kernel or by the kernel's own stores to pinned memory.
-  // Both have a price (profiles/r04_experiments.md section 10).  A store over PCIe holds its wave's in-order memory returns up:
-  // ~0.4 ns per buffer on the launch (8192 buffers: 73.5 -> 76.7 us; 32768 1024-point buffers: 75 -> 96 us).  A DMA that waits
-  // for a kernel or for another DMA starts ~20 us after it (the runtime resolves the dependency on the host): nothing in a
-  // steady loop of long launches, but the whole difference for short ones (2048 buffers per launch, three in flight: 25.5
-  // -> 19.3 us per step), and fatal when the ordered list's DMA shares the D2H stream with it (two per submit: 92 us per submit
-  // on that stream against 73 us of FFT; records read in place, three in flight: 373 .. 403 -> 429 Gsamples/s).  So the kernel
-  // stores the counts itself when the launch has few buffers or the list follows eagerly, and a DMA carries them otherwise.
-  const bool eager = hits && nb && (p->records_wanted || p->device_list_wanted);
-  // (floor and baseline plans take the route of the paths that are not fused: the detect kernel, not the transform, is the submit's last
-  //  kernel, and it stores the counts to device memory only -- counts by DMA or scn_hit_total_kernel, a marker event behind it)
+  // what follows the transform, decided once (submit_route, scn_host.hip: the table and the measurements behind it)
   const bool fused = (p->path == Path::FusedPow2 || p->path == Path::FusedMixed) && p->avg == 1u && !detects_behind(p);
-  const bool direct = fused && (p->direct_counts || nb <= 4096u || eager);
-  // What follows the kernel: the counts (a DMA on the d2h stream: needs no CU -- or nothing, when the kernel stores them to
-  // pinned memory itself) and, when the caller is known to want records, the ordered list (two small kernels + a DMA on
-  // the list stream, beside the next launch).  With overlapped slots both follow the kernel on the slot's own stream --
-  // its next kernel is two submits away, and fewer streams keep both compute streams on hardware queues of their own
-  // (HIP maps streams onto 4 queues by default; with a fifth active stream the two compute streams ended up sharing one).
-  // launches of very many small buffers (total_path): the counts stay on the GPU -- a reduction behind the kernel, ON ITS STREAM, leaves the
-  // batch's total and one trigger bit per buffer in pinned memory (below)
-  const bool total_path = hits && !direct && nb >= kTotalKernelFrom;
-  hipStream_t cnt = (s.own_stream || direct || total_path) ? s.stream : p->d2h_stream.get();
-  hipStream_t lst = list_stream_of(p, s);
-  const bool fork_list = eager && lst != s.stream;
-  // ONE event marks the kernel's end for whoever waits for it: the host (`done`, when nothing else follows on the compute
-  // stream: counts stored by the kernel) or the side streams (`kernel_done`).  For LARGE launches it is completed by the
-  // kernel's own dispatch packet (hipExtLaunchKernel's stopEvent), otherwise by a marker packet behind the kernel.
-  // Measured (scripts/stop_event_check.sh, profiles/r02_stop_event.txt), us per step marker -> in-packet: 33.5 M-sample
-  // launches 75.6 -> 73.1 (4096-pt cfloat), 77 -> 74.5 (2048-pt), 60.2 -> 59.3 (int16); 67 M samples 144.5 -> 140.8; but
-  // 16.8 M samples 44 -> 46..58 and 8.4 M 31 -> 29..56 (erratic: short kernels that carry an event get serialised).
-  const bool after_is_done = cnt == s.stream && !s.own_stream;  // direct counts on the plan's stream
-  hipEvent_t after = (!nb || s.own_stream || total_path) ? nullptr : !hits ? s.done.get() : after_is_done ? s.done.get() : s.kernel_done.get();
-  const bool in_packet = after && fused && (uint64_t)nb * n >= (1u << 25);
-  st = launch_transform(p, s, d_raw, n_raw, d_power, (hits && direct) ? s.h_buf_hits.get() : nullptr, in_packet ? after : nullptr);
+  const SubmitRoute r = s.route = submit_route({hits, fused, p->direct_counts, s.own_stream, p->records_wanted || p->device_list_wanted, n, nb});
+  const hipEvent_t end = end_event_of(s);
+  const hipStream_t cnt = counts_stream_of(p, s);
+  st = launch_transform(p, s, d_raw, n_raw, d_power);
   if (st) return st;
   if (p->floor && nb && (st = launch_floor(p, s, d_power, nb))) return st;
   if (p->baseline && nb && (st = launch_baseline(p, s, d_power, nb, table_first))) return st;
-  if (hits && nb) {
-    if (after && !in_packet) SCN_HIP(hipEventRecord(after, s.stream));
-    if (cnt != s.stream) SCN_HIP(hipStreamWaitEvent(cnt, after, 0));
-    if (fork_list) SCN_HIP(hipStreamWaitEvent(lst, after, 0));
-    // launches of very many small buffers: the total and the trigger flags (a bit per buffer) by themselves -- the counts stay on
-    // the GPU, where the list kernels read them: nb / 8 bytes cross PCIe instead of 4 nb, and a collect walks nothing.  The
-    // reduction runs on the launch's own stream and stores into pinned memory itself: such a step is bound by the HOST's calls
-    // (a 16-point launch of 524288 buffers takes 27 us on the GPU, every HIP call 4 .. 5 us in a torch process), and this way a
-    // submit is three of them -- kernel, reduction, event -- where the route over the side stream took six (event, wait, reduction,
-    // DMA, event: 72 -> 56 us per step, profiles/r06_experiments.md section 5)
-    s.total_ready = total_path;
-    if (total_path) {
-      SCN_HIP(scn_launch_hit_total(s.d_buf_hits[s.gen].get(), nb, p->d.trigger_count, s.d_total_acc.get(), s.h_total, s.h_buf_hits.get(), cnt));
-    } else if (!direct) {
-      SCN_HIP(hipMemcpyAsync(s.h_buf_hits.get(), s.d_buf_hits[s.gen].get(), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, cnt));
-    }
-    // (the way the counts go; a windowed submit has no per-unit floor)
-    if (p->floor && !s.floor_windowed) SCN_HIP(hipMemcpyAsync(s.h_floor.get(), s.d_floor.get(), sizeof(float) * nb, hipMemcpyDeviceToHost, cnt));
-    if (!(after_is_done && after)) SCN_HIP(hipEventRecord(s.done.get(), cnt));
-    if (eager) {
-      int st2 = build_list(p, s, p->records_wanted);  // (the prefetch to pinned memory only for a caller that reads the records on the host)
-      if (st2) return st2;
-    }
-  } else if (!(after && in_packet)) {  // spectrum-only plans: `done` follows the kernel on its stream
-    SCN_HIP(hipEventRecord(s.done.get(), s.stream));
-  }
+  if (end && !r.end_in_packet) SCN_HIP(hipEventRecord(end, s.stream));
+  if (cnt != s.stream) SCN_HIP(hipStreamWaitEvent(cnt, end, 0));
+  if (r.list_forks) SCN_HIP(hipStreamWaitEvent(p->list_stream.get(), end, 0));
+  if (r.counts == Counts::Reduced)
+    SCN_HIP(scn_launch_hit_total(s.cur().d_buf_hits.get(), nb, p->d.trigger_count, s.d_total_acc.get(), s.h_total, s.h_buf_hits.get(), cnt));
+  if (r.counts == Counts::Dma)
+    SCN_HIP(hipMemcpyAsync(s.h_buf_hits.get(), s.cur().d_buf_hits.get(), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, cnt));
+  // (the way the counts go; a windowed submit has no per-unit floor)
+  if (p->floor && r.counts != Counts::None && !s.floor_windowed)
+    SCN_HIP(hipMemcpyAsync(s.h_floor.get(), s.d_floor.get(), sizeof(float) * nb, hipMemcpyDeviceToHost, cnt));
+  if (r.done_behind_counts) SCN_HIP(hipEventRecord(s.done.get(), cnt));
+  if (r.list_behind)  // (the prefetch to pinned memory only for a caller that reads the records on the host)
+    if ((st = build_list(p, s, p->records_wanted))) return st;
   s.pending = true;
   return SCN_OK;
 }

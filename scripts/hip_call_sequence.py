@@ -21,7 +21,9 @@ SHAPES = [("direct counts 4096 cfloat x 2048", 4096, 4, 2048, {}, False),
           ("total_path 16 cfloat x 262144", 16, 4, 262144, {}, False),
           ("average 2, 1024 x 8", 1024, 4, 8, {"average": 2}, False),
           ("floor 64 x 8", 64, 4, 8, {"detect": 1, "threshold": 6.0}, False),
-          ("overlapped slots 4096 int16 x 64", 4096, 3, 64, {"flags": 1 | 2 | 4}, False)]
+          ("overlapped slots 4096 int16 x 64", 4096, 3, 64, {"flags": 1 | 2 | 4}, False),
+          ("floor 64 x 3000, records", 64, 4, 3000, {"detect": 1, "threshold": 6.0}, True),  # not fused, eager, counts by DMA
+          ("spectrum only 4096 cfloat x 8192", 4096, 4, 8192, {"flags": 1}, False)]  # `done` completed by the dispatch packet
 
 
 def run():

@@ -949,7 +949,7 @@ def test_ragged_batches(torch_cuda, oracle_mod, nb):
 
 def test_counts_by_kernel_stores_and_by_dma_agree(torch_cuda, oracle_mod):
     """The per-buffer counts reach the host by the kernel's own stores to pinned memory for launches of up to 4096 buffers
-    (and whenever the ordered list follows eagerly) and by a DMA above (scn_submit.hip, submit_common): both sides of that
+    (and whenever the ordered list follows eagerly) and by a DMA above (scn_host.hip, submit_route): both sides of that
     line, on one plan, counts-only collects first (no eager list), then with records (eager list: stores again)."""
     n, nb = 1024, 4200
     x = synth.cfloat_batch(n, nb, seed=77, max_tones=2)
