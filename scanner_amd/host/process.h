@@ -22,6 +22,7 @@
 class SampleBuffer;
 class SignalSource;
 struct scn_hit;
+struct scn_plan_desc;
 
 class ProcessSamples {
  public:
@@ -73,7 +74,9 @@ class ProcessSamples {
   bool m_writeData;
 
  private:
+  class Worker;  // one consumer thread's plan and slot ring (process.cpp)
   void ThreadWorker(uint32_t threadId);
+  scn_plan_desc PlanDesc(uint32_t sampleKind, uint32_t correctDc) const;  // the fields every plan of this class shares
   void TimeToString(time_t time, char *buffer, uint32_t length);
   std::string GenerateFileName(std::string fileNameBase, time_t startTime, double_t centerFrequency);
   void WriteSamplesToFile(uint64_t sequenceId, double centerFrequency);

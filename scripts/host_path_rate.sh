@@ -4,10 +4,12 @@
 # scn_hits_view -> stdout (/dev/null).  Each configuration runs twice, N and 3N sweeps: the difference is the steady-state
 # rate (plan creation, pinning the slots and the discarded warm-up sweep are in both runs).
 cd "$GRAFT_REPO_ROOT/scanner_amd/host"
-run() { ./scan_synth "$@" --replay 64 --sigma 0.05 --threshold 30 --start 0 > /dev/null 2> /tmp/err.txt; grep -E "^seconds|^buffers|^producer|^staging" /tmp/err.txt; }
+# (a run that fails or hangs ends the script: nothing more is started on a GPU that has just faulted)
+run() { timeout -k 10 300 ./scan_synth "$@" --replay 64 --sigma 0.05 --threshold 30 --start 0 > /dev/null 2> /tmp/err.txt || return 1; grep -E "^seconds|^buffers|^producer|^staging" /tmp/err.txt; }
 pair() { n=$1; it=$2; shift 2
-  a=$(run --n $n "$@" --niterations $it); b=$(run --n $n "$@" --niterations $((3 * it)))
-  python3 - "$n" "$a" "$b" "$*" <<'PY'
+  a=$(run --n $n "$@" --niterations $it) || { cat /tmp/err.txt >&2; exit 1; }
+  b=$(run --n $n "$@" --niterations $((3 * it))) || { cat /tmp/err.txt >&2; exit 1; }
+  python3 - "$n" "$a" "$b" "$*" <<'PY' || exit 1
 import re, sys
 n = int(sys.argv[1]); a, b, what = sys.argv[2], sys.argv[3], sys.argv[4]
 f = lambda s: (int(re.search(r"buffers (\d+)", s).group(1)), float(re.search(r"seconds ([\d.]+)", s).group(1)))

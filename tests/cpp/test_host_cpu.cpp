@@ -17,6 +17,7 @@
 #include "sampleBuffer.h"
 #include "fileSource.h"
 #include "syntheticSource.h"
+#include "tableRun.h"
 
 static int g_fail = 0;
 #define CHECK(c)                                                      \
@@ -348,7 +349,49 @@ static void test_staging_rings() {
   CHECK(q.GetNextSamples() == nullptr);
 }
 
+// TableRun (tableRun.h): which run of the sweep's table a batch's centre frequencies are -- exact cases
+static void test_table_run() {
+  typedef std::vector<double> V;
+  const V table = {10, 20, 30, 40, 50};
+  uint32_t first = 99;
+  {
+    TableRun t(table);
+    CHECK(t.Run(V{10, 20, 30}, 3, &first) && first == 0);
+    CHECK(t.Run(V{40, 50}, 2, &first) && first == 3);          // goes on at the cursor
+    CHECK(t.Run(V{10}, 1, &first) && first == 0);              // ... which wrapped
+    CHECK(t.Run(V{40, 50, 10, 20}, 4, &first) && first == 3);  // after a gap (20, 30 went elsewhere): looked up; the run wraps
+    CHECK(t.Run(V{30, 40}, 2, &first) && first == 2);          // ... and the cursor followed it
+    CHECK(t.Run(V{50, 10, 20, 30, 40, 50, 10, 20, 30, 40, 50, 10}, 12, &first) && first == 4);  // longer than the table: wraps more than once
+    CHECK(t.Run(V{20}, 1, &first) && first == 1);              // (4 + 12) % 5
+    CHECK(t.Run(V{30, 40, 50, 10, 20}, 5, &first) && first == 2);  // exactly the table's length: the cursor is back where it was
+    CHECK(t.Run(V{30, 40, 99}, 2, &first) && first == 2);      // only f[0 .. n) counts
+  }
+  {
+    TableRun t(table);
+    CHECK(t.Run(V{10, 20}, 2, &first) && first == 0);  // cursor at 2
+    first = 99;
+    CHECK(!t.Run(V{30, 40, 51}, 3, &first) && first == 99);    // a mismatch in the middle, at the cursor: nothing moves
+    CHECK(!t.Run(V{50, 10, 21}, 3, &first) && first == 99);    // ... and after a look-up
+    CHECK(!t.Run(V{35, 40}, 2, &first) && first == 99);        // f[0] is not in the table
+    CHECK(t.Run(V{30, 40}, 2, &first) && first == 2);          // the cursor is still where the last good run left it
+  }
+  {
+    const V dup = {10, 20, 10, 30};  // a centre twice: the look-up takes the first and tries no second
+    TableRun t(dup);
+    CHECK(t.Run(V{10, 20}, 2, &first) && first == 0);  // cursor at 2
+    CHECK(t.Run(V{10, 30}, 2, &first) && first == 2);  // at the cursor: the second 10, no look-up
+    CHECK(t.Run(V{10, 20, 10}, 3, &first) && first == 0);  // cursor at 3
+    first = 99;
+    CHECK(!t.Run(V{10, 30}, 2, &first) && first == 99);    // looked up: entry 0, whose run fails; entry 2 is not tried
+    CHECK(t.Run(V{30, 10}, 2, &first) && first == 3);      // the cursor did not move
+  }
+  const V none;
+  TableRun empty(none);
+  CHECK(!empty.Run(V{10}, 1, &first));
+}
+
 int main() {
+  test_table_run();
   test_staging_rings();
   test_capture_retrigger_while_draining();
   test_failures_are_reported();

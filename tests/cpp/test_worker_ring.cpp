@@ -29,6 +29,7 @@ struct FakeSlot {
   std::vector<double> fc;
   std::vector<uint64_t> seq;
   std::vector<scn_hit> list;  // the collected submit's records (scn_collect_more reads it)
+  int submitNo = 0;           // which of the run's submits this is (g_submits when it went out)
 };
 struct FakePlan {
   std::vector<double> table;  // scn_plan_set_table
@@ -52,6 +53,20 @@ int g_planCreateSleepUs = 0;           // a real plan takes hundreds of ms to cr
 uint64_t g_stagedAppends = 0, g_copiedAppends = 0, g_queuedAtAttach = 0, g_buffers = 0;
 uint32_t g_stagedWorkers = 0;
 int g_submits = 0, g_maxInFlight = 0, g_inFlight = 0;
+int g_failCollectAt = -1;              // fail the k-th collect (1-based) AFTER it has freed its slot and counted its ticket; -1: never
+int g_collects = 0, g_plansDestroyed = 0;
+std::vector<int> g_expectedSubmit;     // per g_expected entry, the submit it belongs to (a failed collect takes its batch's lines out)
+std::vector<std::string> g_expectedLines;  // time-domain mode: the "Sequence[...]" line of every buffer above the threshold, in submit order
+scn_plan_desc g_lastDesc;              // what the last scn_plan_create was handed
+// how run() sets ProcessSamples up beyond its arguments
+bool g_timeDomain = false;
+uint32_t g_pipeDepth = 0;              // SetPipelineDepth; 0: the default
+uint32_t g_processN = 0;               // a ProcessSamples built for another sample count than the queue; 0: the same
+gr::fft::window::win_type g_window = gr::fft::window::WIN_BLACKMAN_HARRIS;
+// what run() read back
+std::vector<std::string> g_gotLines;   // the "Sequence[...]" lines printed
+uint64_t g_hitCount = 0;
+std::string g_lastError;
 thread_local std::string g_err;
 
 void violation(const std::string &s) {
@@ -60,6 +75,34 @@ void violation(const std::string &s) {
 }
 FakePlan *P(scn_plan *p) { return reinterpret_cast<FakePlan *>(p); }
 const FakePlan *P(const scn_plan *p) { return reinterpret_cast<const FakePlan *>(p); }
+
+// time-domain mode: fixed figures per buffer, every third buffer above the threshold
+bool tdAbove(uint64_t seq) { return seq % 3 == 0; }
+float tdMax(uint64_t seq) { return 1.5f + (float)(seq % 4); }
+float tdMin(uint64_t seq) { return -20.25f - (float)(seq % 7); }
+
+// what every collect does first, g_m held: the slot is pending and its submit is this plan's oldest; the slot is free afterwards.
+// SCN_E_HIP for the collect that g_failCollectAt names -- its slot freed and its ticket counted all the same.
+int takeOldest(FakePlan *p, int slot) {
+  FakeSlot &s = p->slot[slot];
+  if (!s.pending) {
+    g_violations.push_back("collect on slot " + std::to_string(slot) + " which is not pending");
+    return SCN_E_STATE;
+  }
+  if (s.ticket != p->collected + 1)
+    g_violations.push_back("collect out of order: ticket " + std::to_string(s.ticket) + " after " + std::to_string(p->collected));
+  p->collected = s.ticket;
+  s.pending = false;
+  g_inFlight--;
+  if (++g_collects != g_failCollectAt) return SCN_OK;
+  for (size_t k = g_expectedSubmit.size(); k-- > 0;)  // nothing of this batch is printed
+    if (g_expectedSubmit[k] == s.submitNo) {
+      g_expected.erase(g_expected.begin() + k);
+      g_expectedSubmit.erase(g_expectedSubmit.begin() + k);
+    }
+  g_err = "injected collect failure";
+  return SCN_E_HIP;
+}
 }  // namespace
 
 extern "C" {
@@ -76,6 +119,7 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   {
     std::lock_guard<std::mutex> g(g_m);
     g_plans++;
+    g_lastDesc = *desc;
   }
   const size_t per = desc->sample_kind == SCN_KIND_FLOAT_COMPLEX ? 8 : desc->sample_kind == SCN_KIND_BYTE_COMPLEX ? 2 : 4;
   p->bufBytes = per * desc->n;
@@ -87,6 +131,8 @@ int scn_plan_destroy(scn_plan *plan) {
   for (int s = 0; s < SCN_NUM_SLOTS; s++)
     if (p->slot[s].pending) violation("plan destroyed with slot " + std::to_string(s) + " still pending");
   delete p;
+  std::lock_guard<std::mutex> g(g_m);
+  g_plansDestroyed++;
   return SCN_OK;
 }
 int scn_buffer_bytes(const scn_plan *plan, size_t *bytes) {
@@ -115,6 +161,7 @@ int scn_submit(scn_plan *plan, int slot, uint32_t n, const double *fc, const uin
   if (n == 0 || n > p->d.max_batch) g_violations.push_back("submit of " + std::to_string(n) + " buffers");
   s.pending = true;
   s.ticket = ++p->tickets;
+  s.submitNo = g_submits;
   s.fc.assign(fc, fc + n);
   s.seq.assign(seq, seq + n);
   for (uint32_t b = 0; b < n; b++) {  // a consumer sees the queue's sequence ids in increasing order
@@ -128,8 +175,21 @@ int scn_submit(scn_plan *plan, int slot, uint32_t n, const double *fc, const uin
   }
   g_inFlight++;
   if (g_inFlight > g_maxInFlight) g_maxInFlight = g_inFlight;
+  if (p->d.mode == SCN_MODE_TIME_DOMAIN) {
+    for (uint32_t b = 0; b < n; b++)
+      if (tdAbove(seq[b])) {
+        char line[256];
+        snprintf(line, sizeof(line), "Sequence[%llu]: Max signal %f above threshold %f frequency %.0f, min %f\n", (unsigned long long)seq[b], tdMax(seq[b]),
+                 p->d.threshold, fc[b], tdMin(seq[b]));
+        g_expectedLines.push_back(line);
+      }
+    return SCN_OK;
+  }
   for (uint32_t b = 0; b < n; b++)
-    for (uint32_t h = 0; h < g_hitsPerBuffer; h++) g_expected.push_back((uint64_t)fc[b] + h);
+    for (uint32_t h = 0; h < g_hitsPerBuffer; h++) {
+      g_expected.push_back((uint64_t)fc[b] + h);
+      g_expectedSubmit.push_back(s.submitNo);
+    }
   return SCN_OK;
 }
 int g_indexedSubmits = 0;
@@ -159,15 +219,8 @@ int scn_collect(scn_plan *plan, int slot, float *, scn_hit *hits, uint32_t cap, 
   FakeSlot &s = p->slot[slot];
   if (g_collectSleepUs) std::this_thread::sleep_for(std::chrono::microseconds(g_collectSleepUs));
   std::lock_guard<std::mutex> g(g_m);
-  if (!s.pending) {
-    g_violations.push_back("collect on slot " + std::to_string(slot) + " which is not pending");
-    return SCN_E_STATE;
-  }
-  if (s.ticket != p->collected + 1)
-    g_violations.push_back("collect out of order: ticket " + std::to_string(s.ticket) + " after " + std::to_string(p->collected));
-  p->collected = s.ticket;
-  s.pending = false;
-  g_inFlight--;
+  const int st = takeOldest(p, slot);
+  if (st != SCN_OK) return st;
   s.list.clear();
   for (size_t b = 0; b < s.seq.size(); b++) {
     if (trig) trig[b] = 0;
@@ -184,6 +237,21 @@ int scn_collect(scn_plan *plan, int slot, float *, scn_hit *hits, uint32_t cap, 
   const uint32_t c = *n_hits < cap ? *n_hits : cap;
   if (hits) memcpy(hits, s.list.data(), sizeof(scn_hit) * c);
   return (hits && c < *n_hits) ? SCN_E_TRUNCATED : SCN_OK;
+}
+int scn_collect_time_domain(scn_plan *plan, int slot, float *max_db, float *min_db, uint8_t *above) {
+  FakePlan *p = P(plan);
+  FakeSlot &s = p->slot[slot];
+  if (g_collectSleepUs) std::this_thread::sleep_for(std::chrono::microseconds(g_collectSleepUs));
+  std::lock_guard<std::mutex> g(g_m);
+  if (p->d.mode != SCN_MODE_TIME_DOMAIN) g_violations.push_back("scn_collect_time_domain on a frequency-domain plan");
+  const int st = takeOldest(p, slot);
+  if (st != SCN_OK) return st;
+  for (size_t b = 0; b < s.seq.size(); b++) {
+    if (max_db) max_db[b] = tdMax(s.seq[b]);
+    if (min_db) min_db[b] = tdMin(s.seq[b]);
+    if (above) above[b] = tdAbove(s.seq[b]);
+  }
+  return SCN_OK;
 }
 int scn_hits_view(scn_plan *plan, int slot, const scn_hit **hits, uint32_t *n) {
   FakePlan *p = P(plan);
@@ -225,6 +293,10 @@ std::vector<uint64_t> run(uint32_t n, uint32_t batch, uint32_t depth, uint32_t s
   g_seenSeq.clear();
   g_plans = 0;
   g_submits = g_maxInFlight = g_inFlight = 0;
+  g_collects = g_plansDestroyed = 0;
+  g_expectedSubmit.clear();
+  g_expectedLines.clear();
+  g_gotLines.clear();
   char path[] = "/tmp/scn_ring_XXXXXX";
   const int fd = mkstemp(path);
   fflush(stdout);
@@ -232,8 +304,10 @@ std::vector<uint64_t> run(uint32_t n, uint32_t batch, uint32_t depth, uint32_t s
   stdout = fdopen(fd, "w");
   {
     SyntheticSource source(8000000, n, 88e6, 130e6, SampleQueue::ShortComplex, 5, 0.02);
-    ProcessSamples process(n, 8000000, 12, 10.0f, gr::fft::window::WIN_BLACKMAN_HARRIS, ProcessSamples::FrequencyDomain, threads);
+    ProcessSamples process(g_processN ? g_processN : n, 8000000, 12, 10.0f, g_window, g_timeDomain ? ProcessSamples::TimeDomain : ProcessSamples::FrequencyDomain,
+                           threads);
     process.SetMaxBatch(batch);
+    if (g_pipeDepth) process.SetPipelineDepth(g_pipeDepth);
     if (withTable) {
       FrequencyTable table(8000000, 88e6, 130e6, 0.75, 0.0, true);
       std::vector<double> centres;
@@ -249,6 +323,8 @@ std::vector<uint64_t> run(uint32_t n, uint32_t batch, uint32_t depth, uint32_t s
     g_copiedAppends = q.GetCopiedAppendCount();
     g_queuedAtAttach = q.GetQueuedAtAttachCount();
     g_buffers = process.GetBufferCount();
+    g_hitCount = process.GetHitCount();
+    g_lastError = process.GetLastError();
   }
   fflush(stdout);
   fclose(stdout);
@@ -259,6 +335,7 @@ std::vector<uint64_t> run(uint32_t n, uint32_t batch, uint32_t depth, uint32_t s
   while (f && fgets(line, sizeof(line), f)) {
     unsigned long v;
     if (sscanf(line, "freq %lu power_db", &v) == 1) got.push_back(v);
+    if (!strncmp(line, "Sequence[", 9)) g_gotLines.push_back(line);
   }
   if (f) fclose(f);
   remove(path);
@@ -386,6 +463,85 @@ int main() {
     std::sort(a.begin(), a.end());
     std::sort(b.begin(), b.end());
     CHECK(!a.empty() && a == b);  // what was submitted was reported
+  }
+
+  // 6. time-domain mode: every buffer above the threshold prints its "Sequence[...]" line with its own sequence id, frequency and
+  //    figures, in submit order; those are the hits; a table that is set changes nothing (no upload, no indexed submit)
+  g_collectSleepUs = 300;
+  g_timeDomain = true;
+  got = run(256, 4, 64, 30, ok, 1, true);
+  g_timeDomain = false;
+  CHECK(ok);
+  for (const std::string &v : g_violations) fprintf(stderr, "violation (6): %s\n", v.c_str());
+  CHECK(g_violations.empty());
+  CHECK(got.empty() && g_buffers == 210 && g_expectedLines.size() == 70);  // seq 0, 3, ... of 30 sweeps of 7 centres
+  CHECK(g_gotLines == g_expectedLines);
+  CHECK(g_hitCount == g_expectedLines.size());
+  CHECK(g_indexedSubmits == 0 && g_submits > 10);
+
+  // 7. one collect in the middle fails: its batch's messages go back without lines (counted as buffers, not as hits), its slot goes
+  //    back to the producer and the worker goes on; the run ends -- the producer was not left blocked -- and says it failed
+  g_failCollectAt = 10;
+  got = run(256, 4, 64, 30, ok);
+  g_failCollectAt = -1;
+  CHECK(!ok && g_collects == g_submits && g_collects > 20);
+  for (const std::string &v : g_violations) fprintf(stderr, "violation (7): %s\n", v.c_str());
+  CHECK(g_violations.empty());
+  CHECK(got == g_expected && got.size() < 2 * 210 && got.size() >= 2 * (210 - 4));  // every line but the failed batch's (1 .. 4 buffers)
+  CHECK(g_hitCount == got.size());
+  CHECK(g_buffers == 210 && g_stagedAppends + g_copiedAppends == g_buffers);  // every buffer the source delivered
+  CHECK(g_lastError.find("injected collect failure") != std::string::npos);
+
+  // 8. the copying path (a pipeline of one slot: no staging attach): the worker copies every message, one submit at a time
+  g_pipeDepth = 1;
+  got = run(256, 4, 64, 30, ok);
+  g_pipeDepth = 0;
+  CHECK(ok);
+  for (const std::string &v : g_violations) fprintf(stderr, "violation (8): %s\n", v.c_str());
+  CHECK(g_violations.empty());
+  CHECK(g_stagedWorkers == 0 && g_stagedAppends == 0 && g_copiedAppends == g_buffers && g_buffers == 210);
+  CHECK(got.size() == 2 * 210 && got == g_expected);
+  CHECK(g_maxInFlight == 1);
+
+  // 9. a queue built for another buffer size than the ProcessSamples object: the worker says so, destroys its plan (nothing was
+  //    submitted) and empties the queue -- the run ends, so the producer was not left blocked
+  g_processN = 512;
+  got = run(256, 4, 64, 30, ok);
+  g_processN = 0;
+  CHECK(!ok && got.empty() && g_submits == 0 && g_buffers == 0);
+  CHECK(g_lastError.find("the queue's buffers are 1024 bytes, the plan's 2048 (sample kind or count mismatch)") != std::string::npos);
+  for (const std::string &v : g_violations) fprintf(stderr, "violation (9): %s\n", v.c_str());
+  CHECK(g_violations.empty() && g_plans == 1 && g_plansDestroyed == 1 && g_stagedWorkers == 0);
+
+  // 10. the worker's plan descriptor, field by field (a Hamming window is the one type whose number differs across the boundary;
+  //     max_batch is capped by the queue's depth)
+  g_window = gr::fft::window::WIN_HAMMING;
+  got = run(256, 100, 16, 3, ok);
+  g_window = gr::fft::window::WIN_BLACKMAN_HARRIS;
+  CHECK(ok && g_violations.empty() && got == g_expected && g_plans == 1);
+  {
+    scn_plan_desc want;
+    memset(&want, 0, sizeof(want));
+    want.struct_size = sizeof(want);
+    want.n = 256;
+    want.sample_rate = 8000000;
+    want.sample_kind = SCN_KIND_SHORT_COMPLEX;
+    want.enob = 12;
+    want.correct_dc = 0;
+    want.window_type = SCN_WIN_HAMMING;
+    want.mode = SCN_MODE_FREQUENCY_DOMAIN;
+    want.threshold = 10.0f;
+    want.use_bandwidth = 0.75;
+    want.max_batch = 16;         // min(SetMaxBatch(100), the queue's 16 buffers)
+    want.max_hits = 64 * 16;
+    want.flags = SCN_OUT_HITS;
+    want.device_id = 0;
+    const scn_plan_desc &d = g_lastDesc;
+    CHECK(d.struct_size == want.struct_size && d.n == want.n && d.sample_rate == want.sample_rate && d.sample_kind == want.sample_kind);
+    CHECK(d.enob == want.enob && d.correct_dc == want.correct_dc && d.window_type == want.window_type && d.mode == want.mode);
+    CHECK(d.threshold == want.threshold && d.dc_ignore_bins == 0 && d.use_bandwidth == want.use_bandwidth && d.trigger_count == 0);
+    CHECK(d.max_batch == want.max_batch && d.max_hits == want.max_hits && d.flags == want.flags && d.device_id == want.device_id);
+    CHECK(d.average == 0 && d.average_layout == 0 && d.detect == 0 && d.floor_permille == 0 && d.reserved[0] == 0);
   }
 
   if (g_failures) return 1;

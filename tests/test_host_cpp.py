@@ -79,7 +79,8 @@ def test_worker_slot_ring_against_a_fake_plan(host_build, tmp_path, san):
     """ProcessSamples::ThreadWorker keeps a ring of three submit slots in flight (process.cpp).  Against a fake of the C-ABI
     calls it makes (tests/cpp/test_worker_ring.cpp: protocol checks instead of DSP) on CPU: slots are only submitted when free,
     collected oldest first, every record is printed in submit order -- with the ring full, with the queue running empty, with
-    more records than one collect window, and when a submit fails half way.  Plain, and under TSan / ASan+UBSan."""
+    more records than one collect window, and when a submit fails half way; in time-domain mode, when a collect fails, on the
+    copying path, with a queue of another buffer size; the plan descriptor field by field.  Plain, and under TSan / ASan+UBSan."""
     exe = tmp_path / "test_worker_ring"
     srcs = [os.path.join(HOST, f) for f in ("frequencyTable.cpp", "messageQueue.cpp", "signalSource.cpp", "syntheticSource.cpp",
                                             "processInterface.cpp", "sampleBuffer.cpp", "process.cpp")]
