@@ -128,7 +128,7 @@ HOST = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HERE, "libscanner_host.so")
 HOST_DEMO = os.path.join(HOST, "scan_synth")
 ABI_BENCH = os.path.join(HOST, "abi_bench")
-HOST_SOURCES = ["frequencyTable.cpp", "messageQueue.cpp", "signalSource.cpp", "syntheticSource.cpp", "fileSource.cpp",
+HOST_SOURCES = ["frequencyTable.cpp", "messageQueue.cpp", "captureWriter.cpp", "signalSource.cpp", "syntheticSource.cpp", "fileSource.cpp",
                 "processInterface.cpp", "sampleBuffer.cpp", "process.cpp"]
 
 

@@ -278,7 +278,8 @@ static void test_failures_are_reported() {
 // The staging rings of SampleQueue::AttachStaging, single-threaded and deterministic: what is queued before the first attach is handed
 // out first (unstaged, with a slot reserved), then every append lands IN PLACE in a consumer's slot, the batches dealt to the rings in
 // turn, each ring seeing increasing sequence ids; a sealed slot makes the producer move on; a detached ring takes its queued messages
-// with it and the other ring goes on; with the last ring gone appends are pooled messages again.
+// with it and the other ring goes on; with the last ring gone appends are pooled messages again.  (The same scenario on the state
+// machine alone, stagingRings.h, and a long walk of it: test_staging_rings.cpp.)
 static void test_staging_rings() {
   const uint32_t n = 8, cap = 3, slots = 2;
   const size_t bytes = n * 4;

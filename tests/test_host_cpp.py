@@ -49,7 +49,7 @@ def test_host_classes_under_sanitizers(host_build, tmp_path, san):
     known data race on its shared FFT plan).  The host sources are compiled INTO the test
     binary so they are instrumented; libscanner_hip is only linked for scn_frequency_table."""
     exe = tmp_path / "test_host_san"
-    srcs = [os.path.join(HOST, f) for f in ("frequencyTable.cpp", "messageQueue.cpp", "signalSource.cpp",
+    srcs = [os.path.join(HOST, f) for f in ("frequencyTable.cpp", "messageQueue.cpp", "captureWriter.cpp", "signalSource.cpp",
                                             "syntheticSource.cpp", "fileSource.cpp", "processInterface.cpp", "sampleBuffer.cpp")]
     cmd = ["g++", "-std=gnu++11", "-O1", "-g", "-fno-omit-frame-pointer", f"-fsanitize={san}", "-pthread", "-I", HOST,
            os.path.join(ROOT, "tests", "cpp", "test_host_cpu.cpp")] + srcs + [
@@ -82,7 +82,7 @@ def test_worker_slot_ring_against_a_fake_plan(host_build, tmp_path, san):
     more records than one collect window, and when a submit fails half way; in time-domain mode, when a collect fails, on the
     copying path, with a queue of another buffer size; the plan descriptor field by field.  Plain, and under TSan / ASan+UBSan."""
     exe = tmp_path / "test_worker_ring"
-    srcs = [os.path.join(HOST, f) for f in ("frequencyTable.cpp", "messageQueue.cpp", "signalSource.cpp", "syntheticSource.cpp",
+    srcs = [os.path.join(HOST, f) for f in ("frequencyTable.cpp", "messageQueue.cpp", "captureWriter.cpp", "signalSource.cpp", "syntheticSource.cpp",
                                             "processInterface.cpp", "sampleBuffer.cpp", "process.cpp")]
     cmd = ["g++", "-std=gnu++11", "-O1", "-g", "-fno-omit-frame-pointer", "-pthread", "-I", HOST] + (
         [f"-fsanitize={san}"] if san else []) + [os.path.join(ROOT, "tests", "cpp", "test_worker_ring.cpp")] + srcs + [
@@ -97,6 +97,32 @@ def test_worker_slot_ring_against_a_fake_plan(host_build, tmp_path, san):
         pytest.skip("TSan cannot run under this kernel's address-space layout")
     assert out.returncode == 0, out.stderr[-3000:] + out.stdout[-500:]
     assert "worker ring tests ok" in out.stdout
+
+
+@pytest.mark.parametrize("san", ["", "address,undefined", "thread"])
+def test_staging_rings_stand_alone(tmp_path, san):
+    """The staging state machine of SampleQueue (scanner_amd/host/stagingRings.h: which place an append goes to, which slot a take
+    seals, what is reserved for the messages queued before the attach) in tests/cpp/test_staging_rings.cpp's own program -- no
+    thread, nothing of the project linked: the scenario of test_host_cpu.cpp's test_staging_rings place for place, then a
+    fixed-seed walk of 400 000 steps against a model of who holds every place, which must have met every kind of outcome.  Plain,
+    and under ASan + UBSan and TSan, which must report nothing."""
+    exe = tmp_path / "test_staging_rings"
+    cmd = ["g++", "-std=gnu++11", "-O1", "-g", "-fno-omit-frame-pointer"] + ([f"-fsanitize={san}"] if san else []) + [
+        "-Wall", "-Werror", "-I", HOST, os.path.join(ROOT, "tests", "cpp", "test_staging_rings.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1")
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, env=env)
+    if san == "thread" and out.returncode != 0 and "unexpected memory mapping" in out.stderr:
+        # ThreadSanitizer cannot lay out its shadow under this kernel's ASLR entropy: retry with ASLR off
+        import shutil
+        if not shutil.which("setarch"):
+            pytest.skip("ThreadSanitizer cannot run under this kernel's ASLR settings")
+        out = subprocess.run(["setarch", os.uname().machine, "-R", str(exe)], capture_output=True, text=True, timeout=60, env=env)
+        if out.returncode != 0 and ("unexpected memory mapping" in out.stderr or "setarch" in out.stderr):
+            pytest.skip("ThreadSanitizer cannot run under this kernel's ASLR settings")
+    assert out.returncode == 0 and "staging rings tests ok" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+    assert "runtime error" not in out.stderr and "Sanitizer" not in out.stderr, out.stderr[-3000:]
 
 
 @pytest.mark.parametrize("san", ["address,undefined", ""])
