@@ -430,8 +430,6 @@ hipError_t scn_launch_avg_unit<SCN_AVG_TU>(const ScnAvgLaunch &l) { return launc
 #endif
 
 #if SCN_AVG_IN_TU(3)
-bool scn_avg_size_supported(uint32_t n) { return n == 1024 || n == 2048 || n == 4096 || n == 8192; }
-
 uint32_t scn_avg_parts(uint32_t n, uint32_t n_groups, uint32_t k, int num_cus) {
   if (!n_groups || k <= 1u) return 1u;
   const uint32_t slots = (uint32_t)num_cus * avg_wg_per_cu(n);

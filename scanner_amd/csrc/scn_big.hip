@@ -388,8 +388,6 @@ __global__ __launch_bounds__(256, 3) void scn_big_rows32k_kernel(ScnBigArgs args
   }
 }
 
-bool scn_big_size_supported(uint32_t n) { return n == BN || n == 32768u; }
-
 template <uint32_t N>
 static hipError_t launch_cols(int kind, bool dc, const ScnBigArgs &a, uint32_t grid, size_t lds, hipStream_t s) {
   return scn_with_kind(kind, dc, [&](auto k, auto d) {

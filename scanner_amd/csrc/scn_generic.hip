@@ -177,8 +177,6 @@ __global__ __launch_bounds__(256) void scn_gen_finish_kernel(ScnGenericArgs a, c
 
 }  // namespace
 
-bool scn_bluestein_size_supported(uint32_t n) { return n >= 16u && n < 65536u && (n & (n - 1u)) != 0u; }  // transform length <= 131072
-
 hipError_t scn_launch_generic(int kind, bool dc, bool hits, const ScnGenericArgs &a, int num_cus, hipStream_t s) {
   if (a.n_buffers == 0) return hipSuccess;
   hipError_t e = hipSuccess;

@@ -1,5 +1,5 @@
-// scn_host.h -- the C-ABI layer's arithmetic that never touches HIP (scn_host.hip).  Plain C++: tests/cpp/test_plan_math.cpp
-// compiles the unit with g++ and no HIP header on the include path.
+// scn_host.h -- the C-ABI layer's arithmetic that never touches HIP (scn_host.hip).  Plain C++: tests/cpp/test_plan_math.cpp and
+// tests/cpp/test_plan_resolve.cpp compile the unit with g++ and no HIP header on the include path.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -8,6 +8,7 @@
 
 #include "../../include/scanner_hip.h"
 #include "scn_mask.h"
+#include "scn_sizes.h"
 
 // The layer's one error setter: formats the text scn_last_error returns (one thread_local for the whole library), returns `status`
 int scn_fail(int status, const char *fmt, ...);
@@ -26,9 +27,56 @@ struct ScnBluesteinTables {
   std::vector<double> twiddle, chirp, bfilter;
 };
 ScnBluesteinTables bluestein_tables(uint32_t n);
+// A fused plan's ScnFftArgs::tw1_table, `rows` x `threads` (scn_tw1_layout / scn_mixed_layout): the values of twiddles<float>(n)
+// regrouped per thread of the kernel, entry (p-1, t) = W_n^((stride t p) mod n)
+std::vector<float> fused_tw1_table(uint32_t n, uint32_t rows, uint32_t threads, uint32_t stride = 1);
+// What an averaged 8192-point plan reads besides: the tw1 table of the 4096-point transform of each half, [15][256], entry (p-1, t)
+// = W_4096^(t p) = W_8192^((2 t p) mod 8192), and W_8192^k, k < 4096, in double (the radix-2 step that joins the halves)
+struct ScnAvgHalfTables {
+  std::vector<float> half;
+  std::vector<double> join;
+};
+ScnAvgHalfTables avg_half_tables();
 
 bool floor_permille_of(uint32_t given, uint32_t *permille);
 uint32_t evaluated_bins(uint32_t n, uint32_t dc_ignore, double use_bandwidth, uint32_t *i_lo, uint32_t *i_hi);
+
+// Everything of a plan that follows from its descriptor alone: resolve_plan applies the defaults, checks the descriptor and derives
+// the rest, before scn_plan_create opens a device (tests/cpp/test_plan_resolve.cpp holds every field and every rejection).
+struct PlanShape {
+  scn_plan_desc d;  // with every default applied
+  Path path = Path::Unsupported;
+  uint32_t avg = 1, avg_layout = SCN_AVG_DWELL;  // scn_plan_desc.average / average_layout with the defaults applied
+  size_t buf_bytes = 0;
+  float scale = 1.0f;
+  uint32_t i_lo = 0, i_hi = 0;
+  uint32_t hit_region = 0;  // hit slots each buffer owns = the bins the mask of process.cpp:46-52 evaluates (cannot overflow)
+  bool floor = false;       // scn_plan_desc.detect == SCN_DETECT_FLOOR: the transform stores the spectrum only, scn_floor.hip detects on it
+  uint32_t floor_rank = 0;  // ... and the floor is the value of this rank among the hit_region evaluated bins
+  uint32_t floor_permille = 0;  // ... (floor_permille with its default applied: what a floor window's ranks are made from)
+  // scn_plan_desc.detect == SCN_DETECT_BASELINE: as a floor plan's, the transform stores the spectrum only and scn_baseline.hip detects
+  // on it, against scn_plan::d_baseline
+  bool baseline = false;
+  // How the per-buffer counts reach the host.  false: a 4*n_buffers-byte copy on the d2h stream behind the kernel -- on
+  // this ROCm a blit KERNEL, which runs beside the next launch when that leaves it room (up to 4096 points: yes, ~6 us)
+  // and otherwise waits until that launch drains (8192 points: 254 VGPRs x 2 waves per SIMD; the copy took 46 us, the
+  // host learned the counts late and submitted the launch after next ~10 us late, every other launch).  true: the FFT
+  // kernel stores each count to pinned host memory as well (one 4-byte PCIe write per buffer; costs a 4096-point launch
+  // ~4 us of completion latency, measured in round 1, and the 8192-point ones less than the late copy did).
+  bool direct_counts = false;  // the fused kernels from 8192 points up
+};
+int resolve_plan(const scn_plan_desc *desc, PlanShape *out);  // SCN_OK, or the status with the error text set
+
+// The same for a Welch plan (scn_welch_plan.hip)
+struct WelchShape {
+  scn_welch_desc d;  // with every default applied
+  uint32_t hop = 0, bytes_per_sample = 0;
+  float scale = 1.0f;  // K1's 1/max
+  bool dc = false;     // correct_dc on an integer wire format
+};
+int resolve_welch(const scn_welch_desc *desc, WelchShape *out);
+// workgroups that share the K segments of one PSD's row tile
+uint32_t welch_parts(uint32_t max_psd, uint32_t segments_per_psd, int num_cus);
 // The floor window (scanner_hip.h, "Floor window") on a mask with the defaults applied: need[i] = r_i + 1 -- the number of reference
 // cells that must lie below bin i for it to be a hit -- for every evaluated fftshift index i, 0 for the others.  SCN_E_INVALID (with
 // the error text set, `need` unspecified) for a window outside the limits or one that leaves an evaluated bin without a cell.
@@ -60,7 +108,7 @@ constexpr uint64_t kPacketEventFrom = 1ull << 25;             // samples per lau
 struct SubmitShape {
   bool hits;           // the plan reports hits (SCN_OUT_HITS)
   bool fused;          // the transform is the submit's last kernel and can store counts and complete an event itself: a fused path, not averaged, no detect kernel behind it
-  bool direct_counts;  // the plan's (scn_plan::direct_counts; fused plans only)
+  bool direct_counts;  // the plan's (PlanShape::direct_counts; fused plans only)
   bool own_stream;     // the slot has a stream of its own (SCN_PLAN_OVERLAP_SLOTS)
   bool list_wanted;    // the plan's previous collect took records or a device list
   uint32_t n, units;   // points per transform; buffers per launch, or groups on an averaged plan

@@ -1,6 +1,6 @@
-// scn_host.hip -- the part of the C-ABI layer that never touches HIP: the error text, the arithmetic behind a plan, the entry
-// points that are host arithmetic only.  Plain C++17: no HIP header here or in scn_host.h (tests/cpp/test_plan_math.cpp builds the
-// unit with g++ under the sanitizers); the .hip suffix only puts it through the same compiler as the rest of the library.
+// scn_host.hip -- the part of the C-ABI layer that never touches HIP: the error text, what a descriptor resolves to, the tables, the
+// entry points that are host arithmetic only.  Plain C++17: no HIP header here or in scn_host.h (tests/cpp/test_plan_math.cpp and
+// test_plan_resolve.cpp build the unit with g++ under the sanitizers); the .hip suffix only puts it through the library's compiler.
 #include "scn_host.h"
 
 #include "scn_wire.h"
@@ -141,6 +141,27 @@ ScnBluesteinTables bluestein_tables(uint32_t n) {
   return t;
 }
 
+// rows p = 1 ... `rows` of `threads` entries, each W_n^((stride t p) mod n) as twiddles<float>(n) holds it
+std::vector<float> fused_tw1_table(uint32_t n, uint32_t rows, uint32_t threads, uint32_t stride) {
+  const std::vector<float> tw = twiddles<float>(n);
+  std::vector<float> out(2 * (size_t)rows * threads);
+  for (uint32_t p = 1; p <= rows; p++)
+    for (uint32_t t = 0; t < threads; t++) {
+      const uint32_t k = (uint32_t)(((uint64_t)stride * t * p) % n);
+      out[2 * ((size_t)(p - 1) * threads + t)] = tw[2 * k];
+      out[2 * ((size_t)(p - 1) * threads + t) + 1] = tw[2 * k + 1];
+    }
+  return out;
+}
+
+ScnAvgHalfTables avg_half_tables() {
+  ScnAvgHalfTables t;
+  t.half = fused_tw1_table(8192, 15, 256, 2);  // W_4096^(t p) = W_8192^(2 t p)
+  t.join = twiddles<double>(8192);
+  t.join.resize(8192);  // k < 4096
+  return t;
+}
+
 // scn_plan_desc.floor_permille with its default applied (0 -> 500, SCN_FLOOR_MIN -> 0); false for a value outside the descriptor's
 bool floor_permille_of(uint32_t given, uint32_t *permille) {
   if (given == SCN_FLOOR_MIN) *permille = 0;
@@ -164,6 +185,91 @@ uint32_t evaluated_bins(uint32_t n, uint32_t dc_ignore, double use_bandwidth, ui
   if (i_lo) *i_lo = mask.i_lo;
   if (i_hi) *i_hi = mask.i_hi;
   return kept;
+}
+
+int resolve_plan(const scn_plan_desc *desc, PlanShape *out) {
+  if (desc->struct_size != sizeof(scn_plan_desc))
+    return scn_fail(SCN_E_INVALID, "scn_plan_desc.struct_size %u != %zu (ABI mismatch)", desc->struct_size, sizeof(scn_plan_desc));
+  PlanShape s;
+  scn_plan_desc &d = s.d = *desc;
+  if (!d.window_type) d.window_type = SCN_WIN_BLACKMAN_HARRIS;
+  if (!d.mode) d.mode = SCN_MODE_FREQUENCY_DOMAIN;
+  if (!d.dc_ignore_bins) d.dc_ignore_bins = 4;  // process.cpp:87
+  if (d.dc_ignore_bins == SCN_DC_IGNORE_NONE) d.dc_ignore_bins = 0;
+  if (d.use_bandwidth == 0.0) d.use_bandwidth = 0.75;  // scan.cpp:65
+  if (!d.trigger_count) d.trigger_count = 1047;        // process.cpp:62
+  if (!(d.flags & (SCN_OUT_SPECTRUM | SCN_OUT_HITS))) d.flags |= SCN_OUT_SPECTRUM | SCN_OUT_HITS;
+  if (!d.max_batch) return scn_fail(SCN_E_INVALID, "max_batch must be >= 1");
+  if (!d.max_hits) d.max_hits = (uint32_t)std::min<uint64_t>((uint64_t)d.max_batch * 64u, 1u << 28);
+  if (bytes_per_sample(d.sample_kind) == 0) return scn_fail(SCN_E_INVALID, "unknown sample_kind %u", d.sample_kind);
+  if (d.sample_kind != SCN_KIND_FLOAT_COMPLEX && (d.enob < 1 || d.enob > 32)) return scn_fail(SCN_E_INVALID, "enob %u out of range", d.enob);
+  if (d.window_type < SCN_WIN_HANN || d.window_type > SCN_WIN_HAMMING) return scn_fail(SCN_E_INVALID, "unsupported window_type %u", d.window_type);
+  if (d.mode != SCN_MODE_FREQUENCY_DOMAIN && d.mode != SCN_MODE_TIME_DOMAIN) return scn_fail(SCN_E_INVALID, "unsupported mode %u", d.mode);
+  s.path = path_of(d.mode, d.n);
+  if (s.path == Path::Unsupported) return scn_fail(SCN_E_INVALID, "unsupported FFT size %u (16 to 65536)", d.n);
+  if (d.n == 0 || d.n > (1u << 24)) return scn_fail(SCN_E_INVALID, "bad sample count %u", d.n);
+  if (d.sample_rate == 0) return scn_fail(SCN_E_INVALID, "sample_rate must be > 0");
+  s.avg = d.average ? d.average : 1u;
+  if (s.avg > 1u) {
+    if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return scn_fail(SCN_E_INVALID, "average %u needs a frequency-domain plan", s.avg);
+    if (!scn_avg_size_supported(d.n)) return scn_fail(SCN_E_INVALID, "average %u: n = %u is not supported (1024, 2048, 4096, 8192)", s.avg, d.n);
+    if (d.max_batch % s.avg) return scn_fail(SCN_E_INVALID, "average %u does not divide max_batch %u", s.avg, d.max_batch);
+    if (d.average_layout != SCN_AVG_DWELL && d.average_layout != SCN_AVG_SWEEPS) return scn_fail(SCN_E_INVALID, "unknown average_layout %u", d.average_layout);
+  }
+  const uint32_t kept = evaluated_bins(d.n, d.dc_ignore_bins, d.use_bandwidth, &s.i_lo, &s.i_hi);
+  if (d.detect != SCN_DETECT_FIXED && d.detect != SCN_DETECT_FLOOR && d.detect != SCN_DETECT_BASELINE) return scn_fail(SCN_E_INVALID, "unknown detect %u", d.detect);
+  if (d.detect == SCN_DETECT_BASELINE) {  // (floor_permille is not read)
+    if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_BASELINE needs a frequency-domain plan");
+    // (the caller's own flags: a baseline plan names its outputs, the default of "neither -> both" does not apply to it)
+    if (!(desc->flags & SCN_OUT_HITS)) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_BASELINE needs SCN_OUT_HITS set in flags");
+  }
+  if (d.detect == SCN_DETECT_FLOOR) {
+    if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR needs a frequency-domain plan");
+    if (!(d.flags & SCN_OUT_HITS)) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR needs SCN_OUT_HITS");
+    if (!floor_permille_of(d.floor_permille, &s.floor_permille))
+      return scn_fail(SCN_E_INVALID, "floor_permille %u: 0 (the median), 1 ... 1000 or SCN_FLOOR_MIN", d.floor_permille);
+    if (!kept) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR: the mask (dc_ignore_bins, use_bandwidth) lets no bin through");
+  }
+  s.avg_layout = s.avg > 1u ? d.average_layout : (uint32_t)SCN_AVG_DWELL;
+  s.buf_bytes = bytes_per_sample(d.sample_kind) * d.n;
+  s.scale = convert_scale(d.sample_kind, d.enob);
+  s.hit_region = std::max<uint32_t>(kept, 1u);
+  s.floor = d.detect == SCN_DETECT_FLOOR;
+  if (s.floor) s.floor_rank = (uint32_t)((uint64_t)s.floor_permille * (kept - 1u) / 1000u);
+  s.baseline = d.detect == SCN_DETECT_BASELINE;
+  s.direct_counts = d.n >= 8192 && (s.path == Path::FusedPow2 || s.path == Path::FusedMixed);
+  *out = s;
+  return SCN_OK;
+}
+
+int resolve_welch(const scn_welch_desc *desc, WelchShape *out) {
+  if (desc->struct_size != sizeof(scn_welch_desc)) return scn_fail(SCN_E_INVALID, "scn_welch_desc.struct_size mismatch");
+  WelchShape s;
+  scn_welch_desc &d = s.d = *desc;
+  if (!d.window_type) d.window_type = SCN_WIN_BLACKMAN_HARRIS;
+  // (sample_kind, enob, correct_dc were reserved words until ABI version 5: a version-4 caller's zeros mean float samples)
+  if (!d.sample_kind) d.sample_kind = SCN_KIND_FLOAT_COMPLEX;
+  if (d.sample_kind < SCN_KIND_BYTE_COMPLEX || d.sample_kind > SCN_KIND_FLOAT_COMPLEX) return scn_fail(SCN_E_INVALID, "unsupported sample_kind %u", d.sample_kind);
+  if (!d.enob) d.enob = d.sample_kind == SCN_KIND_BYTE_COMPLEX ? 8u : 12u;
+  if (d.sample_kind != SCN_KIND_FLOAT_COMPLEX && (d.enob < 1 || d.enob > (d.sample_kind == SCN_KIND_BYTE_COMPLEX ? 8u : 16u)))
+    return scn_fail(SCN_E_INVALID, "enob %u out of range for sample_kind %u", d.enob, d.sample_kind);
+  if (d.n != 65536) return scn_fail(SCN_E_INVALID, "unsupported Welch segment length %u (65536)", d.n);
+  if (d.segments_per_psd < 1 || d.max_psd < 1) return scn_fail(SCN_E_INVALID, "segments_per_psd and max_psd must be >= 1");
+  if (d.window_type < SCN_WIN_HANN || d.window_type > SCN_WIN_HAMMING) return scn_fail(SCN_E_INVALID, "unsupported window_type %u", d.window_type);
+  s.hop = d.n / 2;
+  s.bytes_per_sample = (uint32_t)bytes_per_sample(d.sample_kind);
+  s.scale = convert_scale(d.sample_kind, d.enob);
+  s.dc = d.correct_dc && d.sample_kind != SCN_KIND_FLOAT_COMPLEX;
+  *out = s;
+  return SCN_OK;
+}
+
+// enough row workgroups for one per CU: 16 tiles x max_psd x parts >= CUs, parts <= 4 and <= K (measured, 8 PSDs per
+// submit: 68.5 / 75.9 / 73.7 Gsamples/s with 1 / 2 / 4 parts; from 16 PSDs per submit up the split only costs)
+uint32_t welch_parts(uint32_t max_psd, uint32_t segments_per_psd, int num_cus) {
+  uint32_t parts = 1;
+  while (parts < 4u && parts * 2u <= segments_per_psd && 16u * max_psd * parts < (uint32_t)num_cus) parts *= 2u;
+  return parts;
 }
 
 int floor_window_ranks(uint32_t n, uint32_t dc_ignore, uint32_t i_lo, uint32_t i_hi, uint32_t permille, uint32_t train, uint32_t guard,

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "scn_mask.h"  // scn_bin_evaluated: K5's mask, shared with the host arithmetic
+#include "scn_sizes.h"  // scn_*_size_supported, scn_tw1_layout, scn_mixed_layout: which family takes a size, HIP-free
 #include "scn_wire.h"  // SCN_K_*, scn_v2f, Wire<KIND>: K1's wire formats
 
 typedef double double2_scn __attribute__((ext_vector_type(2)));
@@ -42,7 +43,7 @@ struct ScnFftArgs {
   uint32_t hit_region;
   uint32_t *per_buffer_hits;  // [n_buffers] total hits of each buffer (device memory)
   uint32_t *host_hits;        // optional second copy of the same counts in pinned HOST memory, written by the kernel (see
-                              // scn_plan::direct_counts in scn_plan.h for when that beats a copy behind the kernel)
+                              // PlanShape::direct_counts in scn_host.h for when that beats a copy behind the kernel)
   // buffer queue of the persistent workgroups: 8 heads, 32 words (one 128-byte line) apart, never reset; head x
   // serves the buffers b = 8 j + x; work_base[x] is its value before this launch and a launch adds exactly the
   // number of such buffers (scn_work_shard_count) to it
@@ -205,7 +206,6 @@ struct ScnGenericArgs {
   uint32_t *per_buffer_hits;  // [n_buffers], zeroed by the launcher
 };
 hipError_t scn_launch_generic(int kind, bool correct_dc, bool hits, const ScnGenericArgs &args, int num_cus, hipStream_t stream);
-bool scn_bluestein_size_supported(uint32_t n);  // the sizes from 16 to 65535 that are not powers of two
 
 // Plain 65536- / 32768-point plans through the four-step pair of scn_big.hip (columns -> tiled work buffer -> rows + K4 + K5)
 struct ScnBigArgs {
@@ -224,7 +224,6 @@ struct ScnBigArgs {
   int *dc_sums;               // [n_buffers][2] scratch for DC removal of integer samples (zeroed by the launcher), or nullptr
 };
 hipError_t scn_launch_big(uint32_t n, int kind, bool correct_dc, bool hits, bool spectrum, const ScnBigArgs &args, int num_cus, hipStream_t stream);
-bool scn_big_size_supported(uint32_t n);  // 65536, 32768
 
 // Averaged plans (scn_average.hip, scn_plan_desc.average = K > 1): n_groups groups of k buffers, each buffer through K1 + K2 +
 // K3 as in the fused kernels, the group's powers summed in float, divided by k, then K4 + K5 once per group
@@ -246,7 +245,6 @@ struct ScnAvgArgs {
   uint32_t hit_region;
   uint32_t *per_group_hits;   // [n_groups], zeroed by the launcher
 };
-bool scn_avg_size_supported(uint32_t n);  // 1024, 2048, 4096, 8192
 // workgroups that share the k buffers of one group (1 <= parts <= max(1, ceil(k / 2)))
 uint32_t scn_avg_parts(uint32_t n, uint32_t n_groups, uint32_t k, int num_cus);
 // floats of the partial-sum buffer a launch of up to max_groups groups needs
@@ -271,7 +269,6 @@ static inline float scn_hit_prefilter(float threshold) {
   if ((double)f > p) f = __builtin_nextafterf(f, 0.0f);
   return f;
 }
-bool scn_fft_size_supported(uint32_t n);
 // a fused launch on its way from scn_launch_fft / scn_launch_mixed to the translation unit that holds the size's kernels
 struct ScnFftLaunch {
   int kind;
@@ -281,11 +278,8 @@ struct ScnFftLaunch {
   hipStream_t stream;
   hipEvent_t stop;
 };
-void scn_tw1_layout(uint32_t n, uint32_t *rows, uint32_t *threads);  // shape of ScnFftArgs::tw1_table for a fused size
 
 // The fused kernels for the sizes 2^a 3^b 5^c that are not powers of two (scn_mixed.hip, scn_mixed_plans.h): same arguments, same
 // outputs.  tw1_table: `rows` rows of `threads` entries, entry (p - 1, t) = W_n^(t p) (scn_mixed_layout); twiddle: W_n^m, m < n.
-bool scn_mixed_size_supported(uint32_t n);
-bool scn_mixed_layout(uint32_t n, uint32_t *rows, uint32_t *threads);
 hipError_t scn_launch_mixed(uint32_t n, int kind, bool correct_dc, bool hits, bool spectrum, const ScnFftArgs &args, int num_cus,
                             hipStream_t stream, hipEvent_t stop = nullptr);

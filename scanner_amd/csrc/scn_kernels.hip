@@ -1661,13 +1661,4 @@ hipError_t scn_launch_fft(uint32_t n, int kind, bool dc, bool hits, bool spec, c
   const int lg = __builtin_ctz(n);  // 16 / 32, 64 / 128, 256 / 512, 1024 / 2048 share a unit; 4096, 8192, 16384 have one each
   return units[lg < 12 ? (lg - 4) / 2 : lg - 8](n, ScnFftLaunch{kind, dc, hits, spec, args, num_cus, stream, stop});
 }
-
-bool scn_fft_size_supported(uint32_t n) { return n >= 16 && n <= 16384 && (n & (n - 1u)) == 0u; }
-
-// layout of ScnFftArgs::tw1_table for size n: `rows` rows of `threads` entries, row p-1 = W_n^(t p): 15 rows of n/16 for the
-// 16 x 16 x M kernels, 31 rows of 512 for the 32 x 16 x 32 form of 16384 points
-void scn_tw1_layout(uint32_t n, uint32_t *rows, uint32_t *threads) {
-  *rows = n == 16384 ? 31u : 15u;
-  *threads = n == 16384 ? 512u : n / 16u;
-}
 #endif  // SCN_IN_TU(7)

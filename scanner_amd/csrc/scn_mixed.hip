@@ -546,21 +546,6 @@ hipError_t scn_launch_mixed_unit<SCN_MIXED_TU>(uint32_t n, const ScnFftLaunch &l
 #endif
 
 #if SCN_MIXED_IN_TU(0)
-// the plan of size n, or false: its smallest radix R1 (the tw1 table has R1 - 1 rows) and the pass-1 thread count T1 (its row length)
-#define SCN_MIXED_LOOKUP(N, R1, R2, R3, PAD1, PAD2, UNIT) \
-  if (n == N) {                                            \
-    if (rows) *rows = R1 - 1;                              \
-    if (threads) *threads = R2 * R3;                       \
-    return true;                                           \
-  }
-#define SCN_MIXED_BIG_LOOKUP(N, R1, R2, R3, PAD1, UNIT) SCN_MIXED_LOOKUP(N, R1, R2, R3, PAD1, 0, UNIT)
-bool scn_mixed_layout(uint32_t n, uint32_t *rows, uint32_t *threads) {
-  SCN_MIXED_PLANS(SCN_MIXED_LOOKUP)
-  SCN_MIXED_BIG_PLANS(SCN_MIXED_BIG_LOOKUP)
-  return false;
-}
-bool scn_mixed_size_supported(uint32_t n) { return scn_mixed_layout(n, nullptr, nullptr); }
-
 #define SCN_MIXED_UNIT_OF(N, R1, R2, R3, PAD1, PAD2, UNIT) \
   if (n == N) unit = UNIT;
 hipError_t scn_launch_mixed(uint32_t n, int kind, bool dc, bool hits, bool spec, const ScnFftArgs &args, int num_cus, hipStream_t stream,

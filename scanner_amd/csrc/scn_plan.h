@@ -1,6 +1,8 @@
 // scn_plan.h -- what the units of the C-ABI layer share: the plan and its slots, and the helpers more than one of them calls.
-// scn_host.hip: arithmetic and entry points that never touch HIP; scn_plan.hip: create, tables, first-use allocation, destroy,
-// getters; scn_submit.hip / scn_collect.hip: the two sides of a slot; scn_welch_plan.hip: the Welch plan.
+// scn_sizes.h: which sizes each kernel family takes, the path of a size (no HIP header).  scn_host.hip: arithmetic and entry points that
+// never touch HIP -- a descriptor's defaults, checks and everything derived from it (resolve_plan, resolve_welch) and the contents of
+// the tables; scn_plan.hip: the device side of create (streams, uploads), first-use allocation, destroy, getters;
+// scn_submit.hip / scn_collect.hip: the two sides of a slot; scn_welch_plan.hip: the Welch plan.
 //
 // A plan owns: one HIP stream, the window and twiddle tables, and SCN_NUM_SLOTS independent result slots (double buffering:
 // the host fills / drains one slot while the GPU works on the other -- the replacement for the reference's MemoryPool + bounded
@@ -105,21 +107,19 @@ struct Slot {
   uint32_t n_buffers = 0;
 };
 
-// How a plan computes its spectrum: decided once, by path_of, and read by everything that depends on it
-enum class Path { TimeDomain, FusedPow2, FusedMixed, FourStep, Bluestein, Unsupported };
-
 // Where the ordered hit list of a submit is built: behind the kernel on the list stream, overlapping the next launch (plus a
 // DMA of the expected number of records to pinned host memory), IF the plan's previous collect asked for records; otherwise
 // on demand, when a collect call asks -- callers that only want counts / trigger flags pay nothing.  (Measured alternatives,
 // profiles/r02_compact_modes5.txt: always in order on the compute stream costs 60 us per step; always on demand puts the
 // list on the caller's critical path.)
-struct scn_plan {
+// What the descriptor alone decides -- d, path, avg, the mask, hit_region, the detector's numbers, direct_counts -- is the PlanShape
+// that resolve_plan made (scn_host.h); the rest is what the plan owns on the device and what its collects have learned.
+struct scn_plan : PlanShape {
   // (the streams first: destroyed after the slots, the memory and the events that were used on them)
   ScnStream stream;       // compute
   ScnStream h2d_stream;   // staging copies of scn_submit (overlap the other slot's kernel)
   ScnStream d2h_stream;   // per-buffer hit counts back to the host
   ScnStream list_stream;  // the ordered hit list: scan + compaction kernels, the list's DMA
-  scn_plan_desc d;
   int num_cus = 0;
   bool records_wanted = false;  // does the caller take hit records? (decides where the next list is built: scn_collect sets it)
   // Callers that read the records in place (scn_collect for the counts, then scn_hits_view -- only when there ARE hits) never
@@ -132,25 +132,11 @@ struct scn_plan {
   bool device_list_wanted = false;         // the ordered list is built behind every launch, without the prefetch to pinned memory
   uint32_t predict = 0;         // records the next list is expected to hold (last total + a margin, scn_collect): the prefetch size
   uint32_t last_total = 0;      // the total before that: the margin grows with the change between consecutive batches
-  // How the per-buffer counts reach the host.  false: a 4*n_buffers-byte copy on the d2h stream behind the kernel -- on
-  // this ROCm a blit KERNEL, which runs beside the next launch when that leaves it room (up to 4096 points: yes, ~6 us)
-  // and otherwise waits until that launch drains (8192 points: 254 VGPRs x 2 waves per SIMD; the copy took 46 us, the
-  // host learned the counts late and submitted the launch after next ~10 us late, every other launch).  true: the FFT
-  // kernel stores each count to pinned host memory as well (one 4-byte PCIe write per buffer; costs a 4096-point launch
-  // ~4 us of completion latency, measured in round 1, and the 8192-point ones less than the late copy did).
-  bool direct_counts = false;
-  Path path = Path::Unsupported;
-  uint32_t avg = 1, avg_layout = SCN_AVG_DWELL;  // scn_plan_desc.average / average_layout with the defaults applied
-  bool floor = false;       // scn_plan_desc.detect == SCN_DETECT_FLOOR: the transform stores the spectrum only, scn_floor.hip detects on it
-  uint32_t floor_rank = 0;  // ... and the floor is the value of this rank among the hit_region evaluated bins
-  uint32_t floor_permille = 0;  // ... (floor_permille with its default applied: what a floor window's ranks are made from)
   // the floor window (scn_plan_set_floor_window, scn_floor_local.hip): train 0 = none, the unit-wide floor above; with one, the
   // table r_i + 1 by fftshift index (floor_window_ranks), padded with zeros to a multiple of 4 entries
   uint32_t floor_train = 0, floor_guard = 0;
   ScnDeviceMem<uint16_t> d_floor_need;
-  // scn_plan_desc.detect == SCN_DETECT_BASELINE: as a floor plan's, the transform stores the spectrum only and scn_baseline.hip detects
-  // on it, against d_baseline [baseline_rows][n] (scn_plan_set_baseline; kept allocated when dropped, as d_table)
-  bool baseline = false;
+  // baseline plans: what scn_baseline.hip detects against, [baseline_rows][n] (scn_plan_set_baseline; kept allocated when dropped, as d_table)
   ScnDeviceMem<float> d_baseline;
   uint32_t baseline_rows = 0;  // 0: none, every submit is refused
   uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
@@ -159,10 +145,6 @@ struct scn_plan {
   uint32_t table_count = 0;          // entries in use
   ScnDeviceMem<double> d_chirp;      // Bluestein: [n][2], w[i] = exp(-i pi i^2 / n)
   ScnDeviceMem<double> d_bfilter;    // Bluestein: [fft_m][2], FFT_m of the chirp filter / m
-  size_t buf_bytes = 0;
-  float scale = 1.0f;
-  uint32_t i_lo = 0, i_hi = 0;
-  uint32_t hit_region = 0;  // hit slots each buffer owns = the bins the mask of process.cpp:46-52 evaluates (cannot overflow)
   std::vector<float> h_window;
   ScnDeviceMem<float> d_window;
   ScnDeviceMem<scn_v2f> d_twiddle;

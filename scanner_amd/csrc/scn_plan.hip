@@ -1,21 +1,12 @@
-// scn_plan.hip -- a plan's lifecycle: what it is made from (the path, the tables), what a slot allocates at its first use, its
-// end (the members release themselves, scn_resource.h), and the getters.
-#include <algorithm>
+// scn_plan.hip -- a plan's lifecycle: the device side of its creation (the streams and the tables' uploads: what they hold and every
+// number of the plan is resolve_plan's, scn_host.hip), what a slot allocates at its first use, its end (the members release
+// themselves, scn_resource.h), and the getters.
 #include <cstring>
 #include <new>
 
 #include "scn_plan.h"
 
 namespace {
-
-Path path_of(uint32_t mode, uint32_t n) {
-  if (mode == SCN_MODE_TIME_DOMAIN) return Path::TimeDomain;
-  if (scn_fft_size_supported(n)) return Path::FusedPow2;    // scn_kernels.hip: the powers of two 16 ... 16384
-  if (scn_mixed_size_supported(n)) return Path::FusedMixed;  // scn_mixed.hip: the sizes 2^a 3^b 5^c of scn_mixed_plans.h
-  if (scn_big_size_supported(n)) return Path::FourStep;      // scn_big.hip: 32768, 65536
-  if (scn_bluestein_size_supported(n)) return Path::Bluestein;  // scn_generic.hip: every other size from 16 to 65535
-  return Path::Unsupported;
-}
 
 // The window and the tables the plan's path reads (a time-domain plan reads none)
 hipError_t build_tables(scn_plan *p) {
@@ -26,32 +17,15 @@ hipError_t build_tables(scn_plan *p) {
   switch (p->path) {
     case Path::FusedPow2:
     case Path::FusedMixed: {
-      const std::vector<float> tw = twiddles<float>(n);
-      // the same values, regrouped per thread of the fused kernel: entry (p-1, t) = W_n^(t p)
       uint32_t rows, threads;
       if (p->path == Path::FusedMixed) scn_mixed_layout(n, &rows, &threads);
       else scn_tw1_layout(n, &rows, &threads);
-      std::vector<float> tw1(2 * (size_t)rows * threads);
-      for (uint32_t pp = 1; pp <= rows; pp++)
-        for (uint32_t t = 0; t < threads; t++) {
-          const uint32_t m = (uint32_t)(((uint64_t)t * pp) % n);
-          tw1[2 * ((size_t)(pp - 1) * threads + t)] = tw[2 * m];
-          tw1[2 * ((size_t)(pp - 1) * threads + t) + 1] = tw[2 * m + 1];
-        }
-      if ((e = upload(p->d_twiddle, tw)) != hipSuccess) return e;
+      if ((e = upload(p->d_twiddle, twiddles<float>(n))) != hipSuccess) return e;
       if (p->avg > 1u && n == 8192) {  // the averaged kernel's two 4096-point halves and the radix-2 step that joins them
-        std::vector<float> half(2 * 15 * 256);
-        for (uint32_t pp = 1; pp <= 15; pp++)
-          for (uint32_t t = 0; t < 256; t++) {
-            const uint32_t m = (2u * t * pp) % n;  // W_4096^(t p) = W_8192^(2 t p)
-            half[2 * ((pp - 1) * 256 + t)] = tw[2 * m];
-            half[2 * ((pp - 1) * 256 + t) + 1] = tw[2 * m + 1];
-          }
-        std::vector<double> join = twiddles<double>(n);
-        join.resize(n);  // k < 4096
-        if ((e = upload(p->d_avg_tw1, half)) != hipSuccess || (e = upload(p->d_avg_tw, join)) != hipSuccess) return e;
+        const ScnAvgHalfTables t = avg_half_tables();
+        if ((e = upload(p->d_avg_tw1, t.half)) != hipSuccess || (e = upload(p->d_avg_tw, t.join)) != hipSuccess) return e;
       }
-      return upload(p->d_tw1_table, tw1);
+      return upload(p->d_tw1_table, fused_tw1_table(n, rows, threads));
     }
     case Path::FourStep:  // W_n in float; W_256 in double: the row transform of scn_big.hip
       if ((e = upload(p->d_twiddle, twiddles<float>(n))) != hipSuccess) return e;
@@ -149,53 +123,9 @@ int scn_size_path(uint32_t n, uint32_t *path) {
 int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   if (!desc || !out) return scn_fail(SCN_E_INVALID, "null argument");
   *out = nullptr;
-  if (desc->struct_size != sizeof(scn_plan_desc))
-    return scn_fail(SCN_E_INVALID, "scn_plan_desc.struct_size %u != %zu (ABI mismatch)", desc->struct_size,
-                sizeof(scn_plan_desc));
-  scn_plan_desc d = *desc;
-  if (!d.window_type) d.window_type = SCN_WIN_BLACKMAN_HARRIS;
-  if (!d.mode) d.mode = SCN_MODE_FREQUENCY_DOMAIN;
-  if (!d.dc_ignore_bins) d.dc_ignore_bins = 4;  // process.cpp:87
-  if (d.dc_ignore_bins == SCN_DC_IGNORE_NONE) d.dc_ignore_bins = 0;
-  if (d.use_bandwidth == 0.0) d.use_bandwidth = 0.75;  // scan.cpp:65
-  if (!d.trigger_count) d.trigger_count = 1047;        // process.cpp:62
-  if (!(d.flags & (SCN_OUT_SPECTRUM | SCN_OUT_HITS))) d.flags |= SCN_OUT_SPECTRUM | SCN_OUT_HITS;
-  if (!d.max_batch) return scn_fail(SCN_E_INVALID, "max_batch must be >= 1");
-  if (!d.max_hits) d.max_hits = (uint32_t)std::min<uint64_t>((uint64_t)d.max_batch * 64u, 1u << 28);
-  if (bytes_per_sample(d.sample_kind) == 0) return scn_fail(SCN_E_INVALID, "unknown sample_kind %u", d.sample_kind);
-  if (d.sample_kind != SCN_KIND_FLOAT_COMPLEX && (d.enob < 1 || d.enob > 32))
-    return scn_fail(SCN_E_INVALID, "enob %u out of range", d.enob);
-  if (d.window_type < SCN_WIN_HANN || d.window_type > SCN_WIN_HAMMING) return scn_fail(SCN_E_INVALID, "unsupported window_type %u", d.window_type);
-  if (d.mode != SCN_MODE_FREQUENCY_DOMAIN && d.mode != SCN_MODE_TIME_DOMAIN)
-    return scn_fail(SCN_E_INVALID, "unsupported mode %u", d.mode);
-  const Path path = path_of(d.mode, d.n);
-  if (path == Path::Unsupported) return scn_fail(SCN_E_INVALID, "unsupported FFT size %u (16 to 65536)", d.n);
-  if (d.n == 0 || d.n > (1u << 24)) return scn_fail(SCN_E_INVALID, "bad sample count %u", d.n);
-  if (d.sample_rate == 0) return scn_fail(SCN_E_INVALID, "sample_rate must be > 0");
-  const uint32_t avg = d.average ? d.average : 1u;
-  if (avg > 1u) {  // (checked before the device: these are properties of the descriptor alone)
-    if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return scn_fail(SCN_E_INVALID, "average %u needs a frequency-domain plan", avg);
-    if (!scn_avg_size_supported(d.n)) return scn_fail(SCN_E_INVALID, "average %u: n = %u is not supported (1024, 2048, 4096, 8192)", avg, d.n);
-    if (d.max_batch % avg) return scn_fail(SCN_E_INVALID, "average %u does not divide max_batch %u", avg, d.max_batch);
-    if (d.average_layout != SCN_AVG_DWELL && d.average_layout != SCN_AVG_SWEEPS)
-      return scn_fail(SCN_E_INVALID, "unknown average_layout %u", d.average_layout);
-  }
-  uint32_t i_lo = 0, i_hi = 0, floor_permille = 0;
-  const uint32_t kept = evaluated_bins(d.n, d.dc_ignore_bins, d.use_bandwidth, &i_lo, &i_hi);
-  if (d.detect != SCN_DETECT_FIXED && d.detect != SCN_DETECT_FLOOR && d.detect != SCN_DETECT_BASELINE)
-    return scn_fail(SCN_E_INVALID, "unknown detect %u", d.detect);
-  if (d.detect == SCN_DETECT_BASELINE) {  // (floor_permille is not read)
-    if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_BASELINE needs a frequency-domain plan");
-    // (the caller's own flags: a baseline plan names its outputs, the default of "neither -> both" does not apply to it)
-    if (!(desc->flags & SCN_OUT_HITS)) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_BASELINE needs SCN_OUT_HITS set in flags");
-  }
-  if (d.detect == SCN_DETECT_FLOOR) {  // (as the average's: properties of the descriptor alone)
-    if (d.mode != SCN_MODE_FREQUENCY_DOMAIN) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR needs a frequency-domain plan");
-    if (!(d.flags & SCN_OUT_HITS)) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR needs SCN_OUT_HITS");
-    if (!floor_permille_of(d.floor_permille, &floor_permille))
-      return scn_fail(SCN_E_INVALID, "floor_permille %u: 0 (the median), 1 ... 1000 or SCN_FLOOR_MIN", d.floor_permille);
-    if (!kept) return scn_fail(SCN_E_INVALID, "detect = SCN_DETECT_FLOOR: the mask (dc_ignore_bins, use_bandwidth) lets no bin through");
-  }
+  PlanShape shape;
+  if (int st = resolve_plan(desc, &shape)) return st;
+  const scn_plan_desc &d = shape.d;
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return scn_fail(SCN_E_NO_DEVICE, "no HIP device visible");
@@ -204,19 +134,7 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
 
   scn_plan *p = new (std::nothrow) scn_plan();
   if (!p) return scn_fail(SCN_E_NOMEM, "out of host memory");
-  p->d = d;
-  p->path = path;
-  p->avg = avg;
-  p->avg_layout = avg > 1u ? d.average_layout : (uint32_t)SCN_AVG_DWELL;
-  p->buf_bytes = bytes_per_sample(d.sample_kind) * d.n;
-  p->scale = convert_scale(d.sample_kind, d.enob);
-  p->i_lo = i_lo;
-  p->i_hi = i_hi;
-  p->hit_region = std::max<uint32_t>(kept, 1u);
-  p->floor = d.detect == SCN_DETECT_FLOOR;
-  if (p->floor) p->floor_rank = (uint32_t)((uint64_t)floor_permille * (kept - 1u) / 1000u);
-  p->floor_permille = floor_permille;
-  p->baseline = d.detect == SCN_DETECT_BASELINE;
+  static_cast<PlanShape &>(*p) = shape;
   build_window(d.window_type, d.n, p->h_window);
 
   hipDeviceProp_t prop;
@@ -229,8 +147,6 @@ int scn_plan_create(const scn_plan_desc *desc, scn_plan **out) {
   }
     SCN_TRY(hipGetDeviceProperties(&prop, d.device_id));
     p->num_cus = prop.multiProcessorCount;
-    // (the fused kernels from 8192 points up store the counts to pinned memory themselves)
-    p->direct_counts = d.n >= 8192 && (path == Path::FusedPow2 || path == Path::FusedMixed);
     SCN_TRY(p->stream.create());
     SCN_TRY(p->h2d_stream.create());
     SCN_TRY(p->d2h_stream.create());

@@ -6,6 +6,14 @@
 #include "scn_plan.h"
 
 namespace {
+// What the two kernels of a submit pass between them
+struct WelchWork {
+  ScnDeviceMem<char> d_work;      // [max_psd*K][n] complex
+  ScnDeviceMem<float> d_partial;  // [parts][max_psd][n] partial power sums (row kernel -> combine kernel), parts > 1
+  ScnDeviceMem<int> d_dc;         // [max_psd*K + 1][2] block sums (correct_dc on an integer wire format)
+  hipError_t alloc(const scn_welch *w);
+};
+
 struct WelchSlot {
   ~WelchSlot() {
     if (graph) (void)hipGraphExecDestroy(graph);
@@ -18,9 +26,7 @@ struct WelchSlot {
   float *cur_psd = nullptr;        // device location of the pending results (d_psd or the caller's)
   bool via_graph = false;
   hipGraphExec_t graph = nullptr;  // captured H2D -> kernel A -> kernel B -> D2H for graph_npsd PSDs
-  ScnDeviceMem<char> d_work;       // ... which needs a work buffer of its own ([max_psd*K][n] complex)
-  ScnDeviceMem<float> d_partial;   // ... and its own partial sums
-  ScnDeviceMem<int> d_dc;          // ... and its own block sums (correct_dc)
+  WelchWork work;                  // ... which needs a work set of its own
   uint32_t graph_npsd = 0;
   ScnEvent done;
   bool pending = false;
@@ -28,42 +34,41 @@ struct WelchSlot {
 };
 }  // namespace
 
-struct scn_welch {
+struct scn_welch : WelchShape {  // (resolve_welch, scn_host.hip: the descriptor and what follows from it alone)
   ScnStream stream;  // (first: destroyed after the slots and the memory used on it)
-  scn_welch_desc d;
   int num_cus = 0;
-  uint32_t hop = 0;
   ScnDeviceMem<float> d_window;
   ScnDeviceMem<scn_v2f> d_twiddle;
-  ScnDeviceMem<char> d_work;  // [max_psd*K][n] complex
-  ScnDeviceMem<float> d_partial;  // [parts][max_psd][n] partial power sums (row kernel -> combine kernel); shared by the slots
-                                  // through stream order on the device path, per-slot copies on the pinned path
+  WelchWork work;  // the device path's: shared by the slots through stream order (the pinned path's slots own theirs)
   uint32_t parts = 1;
-  uint32_t bytes_per_sample = scn_wire_bytes(SCN_K_FLOAT_COMPLEX);
-  float scale = 1.0f;      // K1's 1/max
-  bool dc = false;         // correct_dc on an integer wire format
-  ScnDeviceMem<int> d_dc;  // [max_psd*K + 1][2] block sums (device path; the pinned path's slots own theirs)
   ScnDeviceMem<double> d_tw256;  // W_256^m in double (the row transform)
   WelchSlot slot[SCN_NUM_SLOTS];
 };
 
 namespace {
+hipError_t WelchWork::alloc(const scn_welch *w) {
+  const size_t segments = (size_t)w->d.max_psd * w->d.segments_per_psd;
+  hipError_t e = d_work.alloc(sizeof(float) * 2 * w->d.n * segments);
+  if (e == hipSuccess && w->parts > 1) e = d_partial.alloc((size_t)w->d.n * w->d.max_psd * w->parts);
+  if (e == hipSuccess && w->dc) e = d_dc.alloc(2u * (segments + 1u));
+  return e;
+}
+
 size_t welch_samples(const scn_welch *w, uint32_t n_psd) {
   return ((size_t)n_psd * w->d.segments_per_psd + 1u) * w->hop;
 }
 
-int welch_enqueue(scn_welch *w, const void *d_in, uint32_t n_psd, float *d_psd, hipStream_t stream, void *d_work,
-                  float *d_partial, int *d_dc) {
+int welch_enqueue(scn_welch *w, const void *d_in, uint32_t n_psd, float *d_psd, hipStream_t stream, const WelchWork &work) {
   ScnWelchArgs a;
   a.scale = w->scale;
-  a.dc_sums = d_dc;
+  a.dc_sums = work.d_dc.get();
   a.tw256 = reinterpret_cast<const double2_scn *>(w->d_tw256.get());
-  a.partial = d_partial;
+  a.partial = work.d_partial.get();
   a.parts = w->parts;
   a.in = d_in;
   a.window = w->d_window.get();
   a.twiddle = w->d_twiddle.get();
-  a.work = d_work;
+  a.work = work.d_work.get();
   a.psd_db = d_psd;
   a.n_segments = n_psd * w->d.segments_per_psd;
   a.hop = w->hop;
@@ -86,29 +91,16 @@ extern "C" {
 int scn_welch_create(const scn_welch_desc *desc, scn_welch **out) {
   if (!desc || !out) return scn_fail(SCN_E_INVALID, "null argument");
   *out = nullptr;
-  if (desc->struct_size != sizeof(scn_welch_desc)) return scn_fail(SCN_E_INVALID, "scn_welch_desc.struct_size mismatch");
-  scn_welch_desc d = *desc;
-  if (!d.window_type) d.window_type = SCN_WIN_BLACKMAN_HARRIS;
-  // (sample_kind, enob, correct_dc were reserved words until ABI version 5: a version-4 caller's zeros mean float samples)
-  if (!d.sample_kind) d.sample_kind = SCN_KIND_FLOAT_COMPLEX;
-  if (d.sample_kind < SCN_KIND_BYTE_COMPLEX || d.sample_kind > SCN_KIND_FLOAT_COMPLEX) return scn_fail(SCN_E_INVALID, "unsupported sample_kind %u", d.sample_kind);
-  if (!d.enob) d.enob = d.sample_kind == SCN_KIND_BYTE_COMPLEX ? 8u : 12u;
-  if (d.sample_kind != SCN_KIND_FLOAT_COMPLEX && (d.enob < 1 || d.enob > (d.sample_kind == SCN_KIND_BYTE_COMPLEX ? 8u : 16u)))
-    return scn_fail(SCN_E_INVALID, "enob %u out of range for sample_kind %u", d.enob, d.sample_kind);
-  if (d.n != 65536) return scn_fail(SCN_E_INVALID, "unsupported Welch segment length %u (65536)", d.n);
-  if (d.segments_per_psd < 1 || d.max_psd < 1) return scn_fail(SCN_E_INVALID, "segments_per_psd and max_psd must be >= 1");
-  if (d.window_type < SCN_WIN_HANN || d.window_type > SCN_WIN_HAMMING) return scn_fail(SCN_E_INVALID, "unsupported window_type %u", d.window_type);
+  WelchShape shape;
+  if (int st = resolve_welch(desc, &shape)) return st;
+  const scn_welch_desc &d = shape.d;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return scn_fail(SCN_E_NO_DEVICE, "no HIP device visible");
   if (d.device_id < 0 || d.device_id >= ndev) return scn_fail(SCN_E_INVALID, "device_id %d out of range", d.device_id);
   SCN_HIP(hipSetDevice(d.device_id));
   scn_welch *w = new (std::nothrow) scn_welch();
   if (!w) return scn_fail(SCN_E_NOMEM, "out of host memory");
-  w->d = d;
-  w->hop = d.n / 2;
-  w->bytes_per_sample = (uint32_t)bytes_per_sample(d.sample_kind);
-  w->scale = convert_scale(d.sample_kind, d.enob);
-  w->dc = d.correct_dc && d.sample_kind != SCN_KIND_FLOAT_COMPLEX;
+  static_cast<WelchShape &>(*w) = shape;
   std::vector<float> win;
   build_window(d.window_type, d.n, win);
   hipDeviceProp_t prop;
@@ -120,12 +112,8 @@ int scn_welch_create(const scn_welch_desc *desc, scn_welch **out) {
     if ((e = upload(w->d_window, win)) != hipSuccess) break;
     if ((e = upload(w->d_twiddle, twiddles<float>(d.n))) != hipSuccess) break;
     if ((e = upload(w->d_tw256, twiddles<double>(256))) != hipSuccess) break;
-    if ((e = w->d_work.alloc(sizeof(float) * 2 * (size_t)d.n * d.max_psd * d.segments_per_psd)) != hipSuccess) break;
-    // enough row workgroups for one per CU: 16 tiles x max_psd x parts >= CUs, parts <= 4 and <= K (measured, 8 PSDs per
-    // submit: 68.5 / 75.9 / 73.7 Gsamples/s with 1 / 2 / 4 parts; from 16 PSDs per submit up the split only costs)
-    while (w->parts < 4u && w->parts * 2u <= d.segments_per_psd && 16u * d.max_psd * w->parts < (uint32_t)w->num_cus) w->parts *= 2u;
-    if (w->parts > 1 && (e = w->d_partial.alloc((size_t)d.n * d.max_psd * w->parts)) != hipSuccess) break;
-    if (w->dc && (e = w->d_dc.alloc(2u * ((size_t)d.max_psd * d.segments_per_psd + 1u))) != hipSuccess) break;
+    w->parts = welch_parts(d.max_psd, d.segments_per_psd, w->num_cus);
+    e = w->work.alloc(w);
   } while (0);
   if (e != hipSuccess) {
     int st = scn_fail(e == hipErrorOutOfMemory ? SCN_E_NOMEM : SCN_E_HIP, "scn_welch_create: %s", hipGetErrorString(e));
@@ -187,9 +175,7 @@ int scn_welch_submit(scn_welch *w, int slot, uint32_t n_psd) {
   SCN_HIP(s.h_psd.alloc(psd_floats));
   SCN_HIP(s.done.create());
   SCN_HIP(s.stream.create());
-  SCN_HIP(s.d_work.alloc(sizeof(float) * 2 * (size_t)w->d.n * w->d.max_psd * w->d.segments_per_psd));
-  if (w->parts > 1) SCN_HIP(s.d_partial.alloc((size_t)w->d.n * w->d.max_psd * w->parts));
-  if (w->dc) SCN_HIP(s.d_dc.alloc(2u * ((size_t)w->d.max_psd * w->d.segments_per_psd + 1u)));
+  SCN_HIP(s.work.alloc(w));
   hipStream_t stream = s.stream.get();
   if (!s.graph || s.graph_npsd != n_psd) {
     // capture the slot's inner loop once per batch size: H2D -> columns -> rows -> D2H
@@ -201,7 +187,7 @@ int scn_welch_submit(scn_welch *w, int slot, uint32_t n_psd) {
     SCN_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
     hipError_t e = hipMemcpyAsync(s.d_in.get(), s.h_in.get(), welch_samples(w, n_psd) * w->bytes_per_sample, hipMemcpyHostToDevice, stream);
     int inner = SCN_OK;
-    if (e == hipSuccess) inner = welch_enqueue(w, s.d_in.get(), n_psd, s.d_psd.get(), stream, s.d_work.get(), s.d_partial.get(), s.d_dc.get());
+    if (e == hipSuccess) inner = welch_enqueue(w, s.d_in.get(), n_psd, s.d_psd.get(), stream, s.work);
     if (e == hipSuccess && inner == SCN_OK)
       e = hipMemcpyAsync(s.h_psd.get(), s.d_psd.get(), sizeof(float) * (size_t)w->d.n * n_psd, hipMemcpyDeviceToHost, stream);
     hipError_t e2 = hipStreamEndCapture(stream, &graph);
@@ -237,7 +223,7 @@ int scn_welch_submit_device(scn_welch *w, int slot, const void *d_samples, uint3
     d_psd_db = s.d_psd.get();
   }
   SCN_HIP(s.done.create());
-  st = welch_enqueue(w, d_samples, n_psd, d_psd_db, w->stream.get(), w->d_work.get(), w->d_partial.get(), w->d_dc.get());
+  st = welch_enqueue(w, d_samples, n_psd, d_psd_db, w->stream.get(), w->work);
   if (st) return st;
   SCN_HIP(hipEventRecord(s.done.get(), w->stream.get()));
   s.pending = true;
