@@ -195,9 +195,13 @@ enum {
  *   r_i = (uint64)permille * (M_i - 1) / 1000 in integer arithmetic, permille from floor_permille exactly as above (0 -> 500,
  *     SCN_FLOOR_MIN -> 0); floor_i = the value of rank r_i among the cells in the key order above;
  *   cut_i = floor_i + threshold, ONE float addition; bin i is a hit iff power_db[u][j] > cut_i, strictly.
- * Records, their power_db, freq_hz, seq_id, their order and trigger are those of a plan that cut bin i at cut_i.  A NaN is placed
- * as the key places it and is otherwise unspecified; a unit that is all -inf has no hits.  No float sum is involved: the hit list
- * is exact, the same bits on every run and every route, as the unit-wide floor's.
+ * Records, their power_db, freq_hz, seq_id, their order and trigger are those of a plan that cut bin i at cut_i.  A NaN cell counts
+ * as below nothing, whatever its sign: bin i is a hit iff at least r_i + 1 of its cells c have fl(c + threshold) < power_db[u][j],
+ * which is the rank wording above for every window without a NaN cell -- and differs from it for a NaN whose sign bit is set, which
+ * the key alone would place under every value.  (No transform of this library stores a unit that mixes NaN with other values: a NaN
+ * sample makes the whole unit NaN, and such a unit has no hits.  scn_local_floor_from_spectrum, a host form of the ranks, places a
+ * NaN as the key does.)  A unit that is all -inf has no hits.  No float sum is involved: the hit list is exact, the same bits on
+ * every run and every route, as the unit-wide floor's.
  * Limits: 1 <= train <= SCN_FLOOR_TRAIN_MAX, guard <= SCN_FLOOR_GUARD_MAX.  A window under which some evaluated bin has M_i = 0
  * is SCN_E_INVALID: n = 16 with the default mask evaluates i in {2, 3, 4, 12, 13, 14}; (train 1, guard 0) is valid, (1, 1) is not
  * (bin 3's only candidates are i = 1, out of band, and i = 5, in the DC window).  That is a property of (n, mask, train, guard)

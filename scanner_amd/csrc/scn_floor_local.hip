@@ -10,6 +10,11 @@
 // changes no comparison): if x > w_(r) then w_(0) ... w_(r) are all below x, r + 1 of them; and if r + 1 cells lie below x, one of
 // them has a rank k >= r, so w_(r) <= w_(k) < x.  Integer counts and float compares only: no atomics on floats, no float sums --
 // the hit set is the same whatever order the waves run in.
+// The argument holds for cells that are not NaN.  A NaN cell counts as below nothing here, whatever its sign -- fl(NaN + threshold)
+// is below no x --, while the key puts a NaN with its sign bit set under every value: for a window that mixed such cells with finite
+// ones the count and a rank taken in key order would differ, and the count is the definition (scanner_hip.h, "Floor window";
+// tests/local_floor_ref.py, hit_bins_by_count).  No transform here stores such a mix: a NaN sample makes its whole unit NaN
+// (tests/test_plan_sequences_gpu.py asserts it of every NaN unit it submits), and a unit that is all NaN has no hits either way.
 // r_i + 1 depends on (n, mask, train, guard, permille) alone: the host makes the table need[i] once per window (floor_window_ranks,
 // scn_host.hip: M_i from the mask, never from the values), 0 for a bin the mask removes, and the kernel reads 2 bytes per bin of it.
 //

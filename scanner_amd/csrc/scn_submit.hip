@@ -38,6 +38,10 @@ hipStream_t counts_stream_of(const scn_plan *p, const Slot &s) { return s.route.
 int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float *d_power) {
   uint32_t *const host_hits = s.route.counts == Counts::Stored ? s.h_buf_hits.get() : nullptr;
   const hipEvent_t stop = s.route.end_in_packet ? end_event_of(s) : nullptr;
+  if (!nb) {  // an empty submit launches nothing, on any path: a hits-only floor or baseline plan has then not even a spectrum buffer to
+    if (stop) SCN_HIP(hipEventRecord(stop, s.stream));  // name, which the fused launchers refused (tests/test_plan_sequences_gpu.py)
+    return SCN_OK;
+  }
   const uint32_t n = p->d.n;
   const int kind = (int)p->d.sample_kind;
   // (a floor or baseline plan's transform reports the spectrum only: its hits come from the detect kernel behind it, launch_floor / launch_baseline)

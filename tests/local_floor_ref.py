@@ -1,7 +1,13 @@
 """The floor window (scanner_hip.h, "Floor window") restated in numpy, vectorised: the keys of tests/floor_ref.py in fftshift order,
 a sliding window over them, the cells the mask removes (and the slots beyond the band's edges: no wrap) mapped to the top key, a
 row sort, and per row the rank from M_i -- the number of cells, counted on the mask and never on the values.  What
-scn_local_floor_from_spectrum and the GPU's windowed detect kernel (scn_floor_local.hip) are held to, bit for bit."""
+scn_local_floor_from_spectrum and the GPU's windowed detect kernel (scn_floor_local.hip) are held to, bit for bit.
+
+NaN cells: the header's decision is the count of hit_bins_by_count -- a NaN cell counts as below nothing, whatever its sign --, which
+the sort reproduces for every window without a NaN cell and for NaN cells whose sign bit is clear (their key is above +inf's).  A NaN
+with its sign bit set has the lowest key: in a window that mixed such cells with finite ones the sort (and the host form, which ranks
+by the key) would place it under every value, the count and the kernel above every value.  No transform stores such a unit -- a NaN
+sample makes the whole unit NaN, which has no hits in either form -- so the two are held together on whole-NaN units only."""
 import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
 
