@@ -525,6 +525,11 @@ SCN_API int scn_hackrf_sweep_fixup(void *transfer, uint32_t valid_length, uint32
  * n samples every n/2 (50 % overlap), |X|^2 averaged over segments_per_psd consecutive
  * segments, output psd_db[k] = 5*log10(mean |X[k]|^2), natural bin order.  A submit of n_psd
  * PSDs consumes (n_psd*segments_per_psd + 1) * n/2 contiguous samples.
+ * The mean is a float, defined as the PRODUCT  sum * (1.0f / (float)segments_per_psd)  of the float sum of the segments' float
+ * powers (added in segment order within a row part, the parts in order) with the float reciprocal -- one float, whichever
+ * kernel finishes the PSD (scn_welch_partition's *parts == 1 or > 1); the dB map of every plan is applied to that float.  A
+ * division by segments_per_psd (the CPU oracle's form) gives the same float where segments_per_psd is a power of two and a
+ * float at most one ulp away otherwise: about 2.6e-7 dB, under the map's own bound (tests/test_welch_exact_gpu.py).
  * Wire formats: the stream arrives as a device front-end delivers it (int8 HackRF
  * hackRFSource.cpp:261, int16 bladeRF bladerfSource.cpp:297, planar int16 SDRplay
  * sdrplaySource.cpp:197, float Airspy airspySource.cpp:197), in DELIVERY BLOCKS of n/2 samples

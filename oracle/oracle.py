@@ -404,7 +404,10 @@ def ref64_spectrum(x_c64, window_f32):
 
 
 def welch(x_c64, n=65536, k=16, n_psd=1):
-    """BASELINE C5: float32 Welch PSD (dB) of a complex64 stream; see scn_oracle_welch."""
+    """BASELINE C5: float32 Welch PSD (dB) of a complex64 stream; see scn_oracle_welch.
+    The mean is formed as acc / (float)k.  The library's definition (include/scanner_hip.h) is the product acc * (1.0f / (float)k):
+    the same float for k a power of two, at most one ulp of the mean away otherwise -- about 2.6e-7 dB, under the dB map's own
+    bound, and far inside compare_spectra (tests/test_welch_probes_cpu.py measures it, tests/test_welch_exact_gpu.py pins the product)."""
     x = np.ascontiguousarray(x_c64, np.complex64)
     assert x.size >= (n_psd * k + 1) * (n // 2)
     out = np.empty((n_psd, n), np.float32)

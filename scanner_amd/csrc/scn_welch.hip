@@ -5,6 +5,10 @@
 // window (the same Blackman-Harris as process.cpp:14-21), forward FFT (fft.cpp:20-25
 // semantics: unnormalised, sign -1), |X|^2 averaged over K consecutive segments in linear
 // power, then the reference's dB map (utility.cpp:86-98): 5*log10(mean |X|^2).
+// THE MEAN is the float  sum * inv_k,  inv_k = 1.0f / (float)K  (welch_enqueue): the PRODUCT form, in the row kernel's
+// parts == 1 epilogue and in the combine kernel alike, so that one sum gives one float whichever of them finishes the PSD
+// (include/scanner_hip.h states it; tests/test_welch_exact_gpu.py holds both to the bit).  The CPU oracle's Welch divides by (float)K:
+// the same float for K a power of two, at most one ulp of the mean away otherwise (about 2.6e-7 dB, under the map's own bound).
 //
 // 512 KiB per segment does not fit LDS, so the FFT is a four-step 256 x 256:
 //   n = 256 n1 + n2,  k = k1 + 256 k2

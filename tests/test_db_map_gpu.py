@@ -3,7 +3,8 @@ whose bin powers are known exactly (tests/db_probes.py, pinned on the host by te
 removal off, so that the FFT drops out of the picture and a test can say which float the map owes.
 
 Per kernel family of DESIGN.md section 3.1 (16 ... 512, 1024 ... 8192, 16384, the mixed-radix sizes 1000 / 6000 / 12000, the
-four-step sizes 32768 / 65536, the averaged plans at 1024 ... 8192 with K = 2 and 4 identical copies):
+four-step sizes 32768 / 65536, the averaged plans at 1024 ... 8192 with K = 2 and 4 identical copies; the Welch plan's two
+epilogues -- separate code sites that no launch of this module reaches -- are held the same way by tests/test_welch_exact_gpu.py):
   * one float per flat buffer: all N bins of a flat probe hold the same bits (no reference needed);
   * the bound (tests/tolerances.py db_map_bound*): every value within max(4.2e-6 dB, 2.2 ulp) of the float64 value 5 log10 P below
     SCN_P_EXACT_FROM, within 1.0 ulp at and above it -- on a sweep over the whole float range of powers that walks EVERY float
