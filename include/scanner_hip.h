@@ -46,7 +46,9 @@ extern "C" {
                              still 6 (additions only): the floor window -- SCN_FLOOR_TRAIN_MAX, SCN_FLOOR_GUARD_MAX,
                              scn_plan_set_floor_window, scn_local_floor_from_spectrum;
                              still 6 (additions only): the baseline detector -- SCN_DETECT_BASELINE, SCN_BASELINE_*,
-                             scn_plan_set_baseline, scn_plan_update_baseline, scn_plan_get_baseline */
+                             scn_plan_set_baseline, scn_plan_update_baseline, scn_plan_get_baseline;
+                             still 6 (additions only): the hit history -- scn_plan_set_history, scn_plan_update_history,
+                             scn_plan_get_history, scn_collect_confirmed, scn_history_fold_hits, scn_confirm_hits */
 
 /* status codes */
 enum {
@@ -235,6 +237,28 @@ enum {
   SCN_BASELINE_MAX = 1  /* per bin the larger of the two in the floor detector's key order (max-hold): exact, whatever the order */
 };
 
+/* Hit history (scn_plan_set_history): M-of-N confirmation, the binary integration that goes with a constant-false-alarm-rate
+ * threshold -- a record counts only if its bin was a hit in at least M of the last N visits of its table entry.  Every detector above
+ * decides on one unit alone; the history is what the plan remembers from one visit of a table entry to the next, across submits.
+ * A plan may own a hit history: history[rows][n] of uint32_t and visits[rows] of uint32_t, device memory; it has none at first.  The
+ * history is indexed by the FFTSHIFT index i of scn_hit.i (not by the natural bin).  Bit 0 of a word is the row's most recent visit,
+ * bit k the visit k visits before it.  Open to every frequency-domain plan with SCN_OUT_HITS -- every detector, every size
+ * scn_size_path supports, averaged plans (the unit is the group); a time-domain plan or one without SCN_OUT_HITS: SCN_E_INVALID.
+ *   Row of a unit: unit u of a submit has row (first + u) % rows, first = the submit's first_index for the indexed submits and 0
+ *     otherwise -- the baseline's rule.
+ *   Fold (scn_plan_update_history): for every unit u of the slot's last collected submit, r its row, and for EVERY i in [0, n):
+ *     history[r][i] = (history[r][i] << 1) | hit(u, i), hit(u, i) = 1 exactly when the submit's hit list holds a record (u, i) --
+ *     a bin the mask removes shifts in 0 --, and visits[r] grows by one, saturating at 0xffffffff.  Rows no unit maps to are
+ *     untouched.  All of the submit's hits take part, however many max_hits keeps.
+ *   Confirmed: for 1 <= m <= window <= 32, a record (u, i) of the slot's ordered hit list is confirmed exactly when
+ *     popcount(history[row(u)][i] & (window == 32 ? 0xffffffff : (1u << window) - 1)) >= m.  The zeros from before a row's first
+ *     visit count as misses.  The confirmed list (scn_collect_confirmed) is the subsequence of the slot's full ordered hit list that
+ *     passes: the same records bit for bit (seq_id, i, the bits of power_db, freq_hz), in the same order; m = window = 1 returns the
+ *     full list.
+ * Integers and compares only: the history and the confirmed list are exact, the same bits on every run and on every route.  No
+ * kernel of a submit reads or writes the history: it changes only through scn_plan_set_history and scn_plan_update_history, both
+ * allowed while other slots are pending.  A plan on which scn_plan_set_history is never called allocates nothing for it. */
+
 /* Signals (scn_collect_signals, scn_signals_from_hits): runs of nearby hits merged into one record each.  A plan's buffer is
  * its unit of output (for an averaged plan: the group).  The hits of one unit, in increasing i, are split into signals: a hit
  * starts a new signal when it is the unit's first hit or when its i exceeds the previous hit's i by more than max_gap + 1.
@@ -402,6 +426,48 @@ SCN_API int scn_plan_update_baseline(scn_plan *plan, int slot, uint32_t op);
 /* Copies rows [first_row, first_row + rows) of the baseline to out (host, rows * n floats): what a caller stores to keep a learnt
  * baseline across runs.  A range outside the baseline is SCN_E_INVALID. */
 SCN_API int scn_plan_get_baseline(scn_plan *plan, uint32_t first_row, uint32_t rows, float *out);
+
+/* Frequency-domain plans with SCN_OUT_HITS only (SCN_E_INVALID otherwise; so the four calls below).  Gives the plan a hit history of
+ * `rows` rows ("Hit history" above), all words and visits zero; rows == 0 drops it (the allocation is kept for the next one).
+ * Allowed at any time, pending slots or not: nothing asynchronous ever touches the history.  Every call starts a new epoch: slots
+ * folded before it can no longer be confirmed. */
+SCN_API int scn_plan_set_history(scn_plan *plan, uint32_t rows);
+
+/* Folds the hits of the slot's last COLLECTED submit into the rows of its units, on the GPU, and returns when that is complete.
+ * Refused before anything is queued: a pending slot, or one without a collected submit whose list is still on the device
+ * (SCN_E_STATE); a plan without a history (SCN_E_STATE); more units than rows (SCN_E_INVALID: a row would be visited twice in one
+ * call); an indexed submit with rows neither the table's count nor 1 (SCN_E_STATE); a submit that was already folded
+ * (SCN_E_STATE).  OTHER slots may be pending: with several submits in flight a caller folds every sweep without draining its
+ * pipeline.  A submit of zero units is SCN_OK and no visit. */
+SCN_API int scn_plan_update_history(scn_plan *plan, int slot);
+
+/* Copies rows [first_row, first_row + rows) of the history (rows * n words, by fftshift index) and of the visits (rows words) to
+ * host memory; either pointer may be NULL.  A range outside the history is SCN_E_INVALID. */
+SCN_API int scn_plan_get_history(scn_plan *plan, uint32_t first_row, uint32_t rows, uint32_t *history, uint32_t *visits);
+
+/* The confirmed list of the slot's last collected submit: *n_confirmed = the number of its records confirmed at (m, window), records
+ * [first, first + cap) of the confirmed list are stored; SCN_E_TRUNCATED when first + cap < *n_confirmed (the records stored are
+ * valid), hits may be NULL with cap 0 to learn the total -- as scn_collect_signals.  m or window outside 1 <= m <= window <= 32:
+ * SCN_E_INVALID.  The slot's submit must have been folded (scn_plan_update_history) and that fold must be the plan's LATEST -- no
+ * other fold and no scn_plan_set_history since -- SCN_E_STATE otherwise; that is stricter than slots whose rows do not overlap would
+ * need, and cannot be wrong.  May be called repeatedly with different (m, window); runs beside pending submits of other slots
+ * without disturbing them. */
+SCN_API int scn_collect_confirmed(scn_plan *plan, int slot, uint32_t m, uint32_t window, uint32_t first, scn_hit *hits, uint32_t cap,
+                                  uint32_t *n_confirmed);
+
+/* The same fold and the same confirmation on host memory (for a gathered list on the root, and the definition the GPU forms are held
+ * to: the same bits).  Need no device.  history: rows * n words, visits: rows words; first as a submit's first_index (reduced modulo
+ * rows).  hits is an ordered hit list as scn_collect returns it, walked unit by unit: unit u owns the maximal run of records at the
+ * cursor whose seq_id equals unit_seq_ids[u] -- with unit_seq_ids == NULL the id is u, as a submit without ids gives it -- so the ids
+ * of CONSECUTIVE units must differ (a unit without hits owns an empty run).  Records left over behind the last unit's run, or a
+ * record with i >= n, are SCN_E_INVALID, and then nothing has been changed.  scn_history_fold_hits needs n_units <= rows
+ * (SCN_E_INVALID).  scn_confirm_hits stores the first min(total, cap) confirmed records, *n_out = the total, SCN_E_TRUNCATED when
+ * cap < total; out may be NULL with cap 0. */
+SCN_API int scn_history_fold_hits(uint32_t *history, uint32_t *visits, uint32_t rows, uint32_t n, uint32_t first, uint32_t n_units,
+                                  const uint64_t *unit_seq_ids, const scn_hit *hits, uint64_t n_hits);
+SCN_API int scn_confirm_hits(const uint32_t *history, uint32_t rows, uint32_t n, uint32_t first, uint32_t n_units,
+                             const uint64_t *unit_seq_ids, const scn_hit *hits, uint64_t n_hits, uint32_t m, uint32_t window,
+                             scn_hit *out, uint64_t cap, uint64_t *n_out);
 
 /* Time-domain plans (mode = SCN_MODE_TIME_DOMAIN; ProcessSamples::DoTimeDomainThresholding,
  * process.cpp:203-237): wait for the slot's submit and fetch, per buffer, the maximum and

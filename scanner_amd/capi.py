@@ -115,6 +115,13 @@ SYMBOLS = {
     "scn_plan_set_baseline": (C.c_int, [_vp, C.c_uint32, _vp]),
     "scn_plan_update_baseline": (C.c_int, [_vp, C.c_int, C.c_uint32]),
     "scn_plan_get_baseline": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    "scn_plan_set_history": (C.c_int, [_vp, C.c_uint32]),
+    "scn_plan_update_history": (C.c_int, [_vp, C.c_int]),
+    "scn_plan_get_history": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "scn_collect_confirmed": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "scn_history_fold_hits": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64]),
+    "scn_confirm_hits": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32,
+                                   _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "scn_collect_time_domain": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "scn_convert_raw": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "scn_wait": (C.c_int, [_vp, C.c_int]),
@@ -229,6 +236,40 @@ def signals_from_hits(hits, n, sample_rate, max_gap=0):
         check(L.scn_signals_from_hits(hits.ctypes.data_as(_vp), hits.size, int(n), int(sample_rate), int(max_gap),
                                       out.ctypes.data_as(_vp), out.size, C.byref(total)), "scn_signals_from_hits")
     return out
+
+
+def _unit_ids(n_units, unit_seq_ids):
+    if unit_seq_ids is None:
+        return None, None
+    ids = np.ascontiguousarray(unit_seq_ids, np.uint64)
+    assert ids.size == n_units, f"{ids.size} unit ids for {n_units} units"
+    return ids, ids.ctypes.data_as(_vp)
+
+
+def history_fold_hits(history, visits, hits, n_units, first=0, unit_seq_ids=None):
+    """scn_history_fold_hits: one submit's ordered hit list (HIT_DTYPE) folded IN PLACE into history (uint32 [rows, n], by fftshift
+    index) and visits (uint32 [rows]) -- every word of the units' rows shifts left by one and takes the bin's hit bit.  Unit u has
+    row (first + u) % rows and owns the run of records whose seq_id is unit_seq_ids[u] (None: u).  Needs no device."""
+    assert history.dtype == np.uint32 and history.ndim == 2 and history.flags.c_contiguous and history.flags.writeable
+    assert visits.dtype == np.uint32 and visits.shape == (history.shape[0],) and visits.flags.c_contiguous and visits.flags.writeable
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    ids, ids_ptr = _unit_ids(n_units, unit_seq_ids)
+    check(lib().scn_history_fold_hits(history.ctypes.data_as(_vp), visits.ctypes.data_as(_vp), history.shape[0], history.shape[1], int(first),
+                                      int(n_units), ids_ptr, hits.ctypes.data_as(_vp), hits.size), "scn_history_fold_hits")
+
+
+def confirm_hits(history, hits, n_units, m, window, first=0, unit_seq_ids=None):
+    """scn_confirm_hits: the records of an ordered hit list (HIT_DTYPE) whose history word has at least m of its `window` lowest bits
+    set, in the list's order (HIT_DTYPE); history, first and unit_seq_ids as history_fold_hits takes them.  Needs no device."""
+    history = np.ascontiguousarray(history, np.uint32)
+    assert history.ndim == 2
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    ids, ids_ptr = _unit_ids(n_units, unit_seq_ids)
+    out, total = np.zeros(hits.size, HIT_DTYPE), C.c_uint64()
+    check(lib().scn_confirm_hits(history.ctypes.data_as(_vp), history.shape[0], history.shape[1], int(first), int(n_units), ids_ptr,
+                                 hits.ctypes.data_as(_vp), hits.size, int(m), int(window), out.ctypes.data_as(_vp), out.size, C.byref(total)),
+          "scn_confirm_hits")
+    return out[: total.value]
 
 
 def floor_from_spectrum(power_db, dc_ignore_bins=4, use_bandwidth=0.75, floor_permille=0):

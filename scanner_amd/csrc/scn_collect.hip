@@ -5,29 +5,6 @@
 
 #include "scn_plan.h"
 
-namespace {
-
-// What the list kernels and the signal kernels read of a slot's pending / last submit, under the same names in both argument
-// structs: the regions, the hits' offsets, and the submit's header fields where they lie (the slot's pinned copy or the plan's table)
-template <class A>
-void set_list_source(A &a, const scn_plan *p, const Slot &s) {
-  const SlotGen &g = s.cur();
-  a.regions = g.d_hits.get();
-  a.hit_region = p->hit_region;
-  a.offsets = s.d_offsets.get();
-  const bool table = g.table_first >= 0;
-  a.center_freq = table ? p->d_table.get() : s.centres(p->d.max_batch);
-  a.table_count = table ? p->table_count : 0u;
-  a.table_first = table ? (uint32_t)g.table_first : 0u;
-  a.seq_id = g.seq_given ? s.seq_ids(p->d.max_batch) : nullptr;
-  a.n_buffers = s.n_buffers;
-  a.n = p->d.n;
-  a.sample_rate = p->d.sample_rate;
-}
-
-// where work on an already complete list goes (top-up copies, scn_collect_more's windows): a stream with nothing queued
-hipStream_t topup_stream_of(const scn_plan *p, const Slot &s) { return s.own_stream ? s.stream : p->h2d_stream.get(); }
-
 // the first `count` records of the slot's list are in pinned host memory
 int fetch_list(scn_plan *p, Slot &s, uint32_t count) {
   if (!s.list_built)
@@ -46,8 +23,6 @@ int fetch_list(scn_plan *p, Slot &s, uint32_t count) {
   }
   return SCN_OK;
 }
-
-}  // namespace
 
 ScnCompactArgs compact_args(const scn_plan *p, const Slot &s, uint32_t first, uint32_t cap, void *out) {
   ScnCompactArgs c;
@@ -148,6 +123,7 @@ int scn_collect(scn_plan *p, int slot, float *power_db, scn_hit *hits, uint32_t 
     memset(trigger, 0, nb);
   }
   s.list_valid = have_hits;
+  s.folded_epoch = 0;  // (a new collected submit: not yet part of the hit history)
   if (total > 0x7fffffffu) return scn_fail(SCN_E_INVALID, "%llu hits in one submit: split the batch", (unsigned long long)total);
   s.total_hits = (uint32_t)total;
   if (have_hits) {  // what the automatic mode goes by at the next submit

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/scanner_hip.h"
+#include "scn_hitlist.h"
 #include "scn_kernels.h"
 
 namespace {
@@ -91,17 +92,10 @@ __global__ __launch_bounds__(kScanThreads) void scn_hit_scan_kernel(ScnCompactAr
   if (blockIdx.x == gridDim.x - 1 && t == kScanThreads - 1) a.offsets[a.n_buffers] = run;  // the total
 }
 
-// uint64_t(double) the way the reference's x86-64 build does it (process.cpp:57 casts a double that is negative for the
-// lowest bins of a sweep starting at 0 Hz: cvttsd2si gives the two's complement of the magnitude, not 0)
-__device__ __forceinline__ uint64_t to_u64_like_x86(double f) {
-  return f < 0.0 ? (uint64_t)(int64_t)f : (uint64_t)f;
-}
-
 __global__ __launch_bounds__(256) void scn_hit_compact_kernel(ScnCompactArgs a) {
   extern __shared__ uint32_t smem[];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t words = (a.n + 31u) / 32u;            // bitmap words per buffer
-  const uint32_t per_lane = (words + 63u) / 64u;       // contiguous words a lane sums
   uint32_t *const bits = smem + (size_t)wave * 2u * words;
   uint32_t *const below = bits + words;                // set bits in the words before word w
   const uint32_t bin_step = a.sample_rate / a.n;       // process.cpp:39 (truncating)
@@ -113,57 +107,15 @@ __global__ __launch_bounds__(256) void scn_hit_compact_kernel(ScnCompactArgs a) 
     const ScnDevHit *const region = a.regions + (size_t)b * a.hit_region;
     const uint32_t o0 = a.offsets[b], o1 = a.offsets[b + 1u];
     const ScnDevHit first64 = region[lane < a.hit_region ? lane : 0u];
-    const double fc = a.center_freq[a.table_count ? (uint32_t)(((uint64_t)a.table_first + b) % a.table_count) : b];
-    const uint64_t seq = a.seq_id ? a.seq_id[b] : (uint64_t)b;  // (no ids given at submit: a buffer's id is its index, messageQueue.h:86 from zero)
+    const double fc = scn_unit_centre(a, b);
+    const uint64_t seq = scn_unit_seq(a, b);
     const uint32_t c = o1 - o0;
     if (c == 0 || o0 >= last || o1 <= a.first) continue;  // no hits, or nothing of this buffer inside the window
     const uint32_t stored = c < a.hit_region ? c : a.hit_region;
-    for (uint32_t w = lane; w < words; w += 64u) bits[w] = 0u;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (uint32_t k = lane; k < stored; k += 64u) {
-      const uint32_t i = k < 64u ? first64.i : region[k].i;
-      atomicOr(&bits[i >> 5], 1u << (i & 31u));
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    // below[w]: lane l sums its words [l*per_lane, (l+1)*per_lane), exclusive scan over the lanes, then fills in
-    uint32_t mine = 0;
-    for (uint32_t k = 0; k < per_lane; k++) {
-      const uint32_t w = lane * per_lane + k;
-      if (w < words) mine += (uint32_t)__popc(bits[w]);
-    }
-    uint32_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t v = __shfl_up(incl, off, 64);
-      if (lane >= (uint32_t)off) incl += v;
-    }
-    uint32_t run = incl - mine;
-    for (uint32_t k = 0; k < per_lane; k++) {
-      const uint32_t w = lane * per_lane + k;
-      if (w < words) {
-        below[w] = run;
-        run += (uint32_t)__popc(bits[w]);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const double start_frequency = fc - (double)(a.sample_rate / 2u);  // process.cpp:38 (uint32 division)
-    for (uint32_t k = lane; k < stored; k += 64u) {
-      const ScnDevHit h = k < 64u ? first64 : region[k];
-      const uint32_t w = h.i >> 5;
-      const uint32_t pos = o0 + below[w] + (uint32_t)__popc(bits[w] & ((1u << (h.i & 31u)) - 1u));
-      if (pos >= a.first && pos < last) {
-        const double frequency = start_frequency + (double)(uint32_t)(h.i * bin_step);  // process.cpp:55
-        scn_hit r;
-        r.seq_id = seq;
-        r.i = h.i;
-        r.power_db = h.power_db;
-        r.freq_hz = to_u64_like_x86(frequency);  // process.cpp:57
-        out[pos - a.first] = r;
-      }
-    }
+    // (the three steps are scn_hitlist.h's: the bitmap, the set bits before each word, the completed records at their ranks)
+    scn_wave_hit_bitmap(region, first64, stored, words, lane, bits);
+    scn_wave_rank_prefix(bits, below, words, lane);
+    scn_wave_write_ranked<false>(region, first64, stored, bits, below, o0, a.first, last, seq, fc, a.sample_rate, bin_step, out, lane);
     __builtin_amdgcn_wave_barrier();  // the bitmap is reused by this wave's next buffer
   }
 }

@@ -89,6 +89,14 @@ int check_baseline_submit(uint32_t rows, bool indexed, uint32_t table_count);
 int check_baseline_update(uint32_t rows, uint32_t units, uint32_t op);
 int check_baseline_range(uint32_t have, uint32_t first_row, uint32_t rows);
 
+// The hit history (scanner_hip.h, "Hit history"): what a fold, a confirmation and a read-out must satisfy, from numbers alone (SCN_OK,
+// or the status with the error text set) -- shared by the plan's entry points (scn_history_plan.hip) and the host forms
+// (scn_history_fold_hits, scn_confirm_hits).  The row of a unit is scn_baseline_row, the mask and the predicate scn_history_mask and
+// scn_history_confirms (scn_mask.h: the kernels' own).  rows: the history's; indexed: the submit named a run of the plan's table
+int check_history_fold(uint32_t rows, uint32_t units, bool indexed, uint32_t table_count);
+int check_history_window(uint32_t m, uint32_t window);
+int check_history_range(uint32_t have, uint32_t first_row, uint32_t rows);
+
 // Averaged plans (k = average > 1; sweeps: SCN_AVG_SWEEPS, else SCN_AVG_DWELL).  group_headers redirects fc / seq to the groups'
 // (held in group_fc / group_seq) where the submit gave them or the compaction kernel's default would be wrong; returns the groups
 int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc);

@@ -317,6 +317,53 @@ int check_baseline_range(uint32_t have, uint32_t first_row, uint32_t rows) {
   return SCN_OK;
 }
 
+int check_history_fold(uint32_t rows, uint32_t units, bool indexed, uint32_t table_count) {
+  if (!rows) return scn_fail(SCN_E_STATE, "the plan has no hit history: scn_plan_set_history was never called, or dropped it");
+  if (units > rows) return scn_fail(SCN_E_INVALID, "the submit had %u units, the history has %u rows: a row would be visited twice", units, rows);
+  if (indexed && rows != 1u && rows != table_count)
+    return scn_fail(SCN_E_STATE, "an indexed submit needs a history of 1 row or of one per table entry (%u): it has %u", table_count, rows);
+  return SCN_OK;
+}
+
+int check_history_window(uint32_t m, uint32_t window) {
+  if (m < 1u || m > window || window > 32u) return scn_fail(SCN_E_INVALID, "confirmation needs 1 <= m <= window <= 32: m %u, window %u", m, window);
+  return SCN_OK;
+}
+
+int check_history_range(uint32_t have, uint32_t first_row, uint32_t rows) {
+  if ((uint64_t)first_row + rows > have) return scn_fail(SCN_E_INVALID, "rows [%u, %u + %u) outside the history of %u rows", first_row, first_row, rows, have);
+  return SCN_OK;
+}
+
+namespace {
+
+// An ordered host hit list, unit by unit: unit u owns the maximal run of records at the cursor whose seq_id is the unit's
+// (unit_seq_ids[u], or u); each(row of the unit, record) for every record.  A record with i >= n, and records left over behind the
+// last unit's, are SCN_E_INVALID.
+template <class F>
+int walk_history_units(uint32_t rows, uint32_t n, uint32_t first, uint32_t n_units, const uint64_t *unit_seq_ids, const scn_hit *hits, uint64_t n_hits,
+                       F each) {
+  if (!rows || !n) return scn_fail(SCN_E_INVALID, "a history of %u rows of %u bins", rows, n);
+  if (!hits && n_hits) return scn_fail(SCN_E_INVALID, "null argument");
+  const uint32_t f = first % rows;
+  if ((uint64_t)f + n_units > 0xffffffffull) return scn_fail(SCN_E_INVALID, "%u units from row %u", n_units, f);
+  uint64_t k = 0;
+  for (uint32_t u = 0; u < n_units; u++) {
+    const uint64_t id = unit_seq_ids ? unit_seq_ids[u] : (uint64_t)u;
+    const uint32_t row = scn_baseline_row(f, u, rows);
+    for (; k < n_hits && hits[k].seq_id == id; k++) {
+      if (hits[k].i >= n) return scn_fail(SCN_E_INVALID, "record %llu: i = %u outside the %u bins", (unsigned long long)k, hits[k].i, n);
+      each(row, hits[k]);
+    }
+  }
+  if (k != n_hits)
+    return scn_fail(SCN_E_INVALID, "record %llu (seq_id %llu) belongs to none of the %u units in order", (unsigned long long)k,
+                    (unsigned long long)hits[k].seq_id, n_units);
+  return SCN_OK;
+}
+
+}  // namespace
+
 // Averaged plans: a submit's arguments alone decide whether it can run -- checked before any copy or kernel is queued
 int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc) {
   if (nb % k) return scn_fail(SCN_E_INVALID, "n_buffers %u is not a multiple of average %u", nb, k);
@@ -455,6 +502,41 @@ int scn_signals_from_hits(const scn_hit *hits, uint64_t n_hits, uint32_t n, uint
   if (total && total <= cap) signals[total - 1] = cur;
   *n_signals = total;
   if (total > cap) return scn_fail(SCN_E_TRUNCATED, "%llu signals, the first %llu returned", (unsigned long long)total, (unsigned long long)cap);
+  return SCN_OK;
+}
+
+int scn_history_fold_hits(uint32_t *history, uint32_t *visits, uint32_t rows, uint32_t n, uint32_t first, uint32_t n_units,
+                          const uint64_t *unit_seq_ids, const scn_hit *hits, uint64_t n_hits) {
+  if (!history || !visits) return scn_fail(SCN_E_INVALID, "null argument");
+  // the whole list is checked before a word changes: a refused call leaves the history as it was
+  if (int st = walk_history_units(rows, n, first, n_units, unit_seq_ids, hits, n_hits, [](uint32_t, const scn_hit &) {})) return st;
+  if (int st = check_history_fold(rows, n_units, false, 0)) return st;
+  for (uint32_t u = 0; u < n_units; u++) {  // (units <= rows: every unit has a row of its own)
+    const uint32_t row = scn_baseline_row(first % rows, u, rows);
+    uint32_t *const h = history + (size_t)row * n;
+    for (uint32_t i = 0; i < n; i++) h[i] = scn_history_fold(h[i], 0u);
+    if (visits[row] != 0xffffffffu) visits[row]++;
+  }
+  return walk_history_units(rows, n, first, n_units, unit_seq_ids, hits, n_hits,
+                            [&](uint32_t row, const scn_hit &r) { history[(size_t)row * n + r.i] |= 1u; });
+}
+
+int scn_confirm_hits(const uint32_t *history, uint32_t rows, uint32_t n, uint32_t first, uint32_t n_units, const uint64_t *unit_seq_ids,
+                     const scn_hit *hits, uint64_t n_hits, uint32_t m, uint32_t window, scn_hit *out, uint64_t cap, uint64_t *n_out) {
+  if (!n_out) return scn_fail(SCN_E_INVALID, "null argument");
+  *n_out = 0;
+  if (!history || (!out && cap)) return scn_fail(SCN_E_INVALID, "null argument");
+  if (int st = check_history_window(m, window)) return st;
+  const uint32_t mask = scn_history_mask(window);
+  uint64_t total = 0;
+  const int st = walk_history_units(rows, n, first, n_units, unit_seq_ids, hits, n_hits, [&](uint32_t row, const scn_hit &r) {
+    if (!scn_history_confirms(history[(size_t)row * n + r.i], mask, m)) return;
+    if (total < cap) out[total] = r;
+    total++;
+  });
+  if (st) return st;
+  *n_out = total;
+  if (total > cap) return scn_fail(SCN_E_TRUNCATED, "%llu confirmed records, the first %llu returned", (unsigned long long)total, (unsigned long long)cap);
   return SCN_OK;
 }
 

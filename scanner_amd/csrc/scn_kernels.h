@@ -130,6 +130,42 @@ struct ScnSignalArgs {
 };
 hipError_t scn_launch_signal_count(const ScnSignalArgs &args, hipStream_t stream);
 hipError_t scn_launch_signal_build(const ScnSignalArgs &args, hipStream_t stream);
+// The hit history (scn_history.hip, scanner_hip.h "Hit history"): history[rows][n] words by fftshift index and visits[rows], device
+// memory, per plan.  The fold launch shifts a submit's hits -- the units' regions and counts where the FFT kernels and the detectors
+// left them, in any order -- into the rows of its units, every bin of each row: word = (word << 1) | hit, and adds one to each such
+// row's visits (saturating).  It needs n_units <= rows: every unit then has a row of its own, no two threads write the same word.
+struct ScnHistoryArgs {
+  const ScnDevHit *regions;    // [n_units][hit_region]
+  uint32_t hit_region;
+  const uint32_t *counts;      // [n_units] hits per unit
+  uint32_t *history;           // [rows][n]
+  uint32_t *visits;            // [rows]
+  uint32_t n, n_units;
+  uint32_t rows, first;        // unit u folds into row scn_baseline_row(first, u, rows); first < rows
+};
+hipError_t scn_launch_history_fold(const ScnHistoryArgs &args, int num_cus, hipStream_t stream);
+// The confirmed list: the records of the submit's ordered hit list whose history word has at least m of the bits of `mask` set
+// (scn_history_confirms), in the list's order.  scn_launch_confirm_count writes each unit's number of confirmed records,
+// scn_launch_hit_scan (counts = conf_counts, offsets = conf_offsets) turns them into offsets and the total, and
+// scn_launch_confirm_build writes the completed records [first, first + out_cap) of the confirmed list to `out`.
+struct ScnConfirmArgs {
+  const ScnDevHit *regions;    // as ScnSignalArgs: regions, the hits' offsets (the scan's output) and the submit's header fields
+  uint32_t hit_region;
+  const uint32_t *offsets;     // [n_buffers + 1]
+  const double *center_freq;
+  const uint64_t *seq_id;
+  uint32_t table_count, table_first;
+  uint32_t n_buffers, n, sample_rate;
+  const uint32_t *history;     // [rows][n]
+  uint32_t rows, hist_first;   // unit b reads row scn_baseline_row(hist_first, b, rows); hist_first < rows
+  uint32_t m, mask;            // scn_history_mask(window)
+  uint32_t *conf_counts;       // [n_buffers] confirmed records per unit (the count kernel's output)
+  const uint32_t *conf_offsets;  // [n_buffers + 1] their exclusive prefix sums, the total last (the build kernel's input)
+  void *out;                   // scn_hit[out_cap]
+  uint32_t first, out_cap;     // first + out_cap must not wrap
+};
+hipError_t scn_launch_confirm_count(const ScnConfirmArgs &args, hipStream_t stream);
+hipError_t scn_launch_confirm_build(const ScnConfirmArgs &args, hipStream_t stream);
 // sum of counts[0, n_buffers) -> *host_total (pinned host memory); acc: two zeroed device words the kernel leaves zeroed
 hipError_t scn_launch_hit_total(const uint32_t *counts, uint32_t n_buffers, uint32_t trigger_count, unsigned long long *acc, unsigned long long *host_total,
                                 uint32_t *trigger_bits, hipStream_t stream);

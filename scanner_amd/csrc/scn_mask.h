@@ -23,6 +23,13 @@ SCN_HOST_DEVICE uint32_t scn_baseline_row(uint32_t first, uint32_t u, uint32_t r
   return s < rows ? s : s % rows;
 }
 
+// The hit history (scanner_hip.h, "Hit history"), one 32-bit word per bin: bit 0 the row's most recent visit, bit k the visit k
+// visits before it.  A fold shifts the visit in at the bottom (the oldest falls off the top); a record is confirmed when at least m
+// of the `window` most recent visits were hits, 1 <= m <= window <= 32 (the caller's check: check_history_window, scn_host.h).
+SCN_HOST_DEVICE uint32_t scn_history_fold(uint32_t word, uint32_t hit) { return (word << 1) | (hit & 1u); }
+SCN_HOST_DEVICE uint32_t scn_history_mask(uint32_t window) { return window >= 32u ? 0xffffffffu : (1u << window) - 1u; }
+SCN_HOST_DEVICE bool scn_history_confirms(uint32_t word, uint32_t mask, uint32_t m) { return (uint32_t)__builtin_popcount(word & mask) >= m; }
+
 // The grid of a launch of persistent teams (scn_detect.h): ceil(n_units / teams) workgroups of `teams` teams each, capped at what is
 // resident at once, per_cu workgroups on each of num_cus CUs (256 CUs where the count is unknown).
 SCN_HOST_DEVICE uint32_t scn_team_grid(uint32_t n_units, uint32_t teams, int num_cus, int per_cu) {

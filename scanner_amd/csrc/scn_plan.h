@@ -89,6 +89,11 @@ struct Slot {
   // and the window of records the build kernel writes before they are copied out (grown on demand, like d_window)
   ScnDeviceMem<uint32_t> d_sig_counts, d_sig_offsets;
   ScnDeviceMem<scn_signal> d_sig_window;
+  // scn_collect_confirmed: confirmed records per unit and their exclusive scan, and the window of records the build kernel writes
+  // (the same three, allocated and grown the same way)
+  ScnDeviceMem<uint32_t> d_conf_counts, d_conf_offsets;
+  ScnDeviceMem<scn_hit> d_conf_window;
+  uint64_t folded_epoch = 0;        // scn_plan::history_epoch when the last collected submit was folded into the hit history (0: it was not)
   // floor-detector plans (scn_floor.hip): floor_db of the pending / last submit's units, kernel-written device memory and the pinned
   // copy a DMA behind the counts' brings (scn_collect_floor reads it).  ONE generation of each is enough, unlike the regions and
   // counts: the only reader of d_floor is that DMA, which is complete when `done` is -- and a slot is not submitted again before
@@ -139,6 +144,12 @@ struct scn_plan : PlanShape {
   // baseline plans: what scn_baseline.hip detects against, [baseline_rows][n] (scn_plan_set_baseline; kept allocated when dropped, as d_table)
   ScnDeviceMem<float> d_baseline;
   uint32_t baseline_rows = 0;  // 0: none, every submit is refused
+  // the hit history (scn_history.hip; scn_plan_set_history, kept allocated when dropped): [history_rows][n] words by fftshift index
+  // and [history_rows] visits.  No kernel of a submit reads or writes them -- only scn_plan_update_history and
+  // scn_collect_confirmed, which both return synchronised --, so they may change while other slots are pending.
+  ScnDeviceMem<uint32_t> d_history, d_visits;
+  uint32_t history_rows = 0;   // 0: none
+  uint64_t history_epoch = 0;  // grows with every fold and every scn_plan_set_history: a slot's confirmed list is that of the plan's LATEST fold
   uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
   ScnDeviceMem<double> d_twiddle64;  // four-step: [256][2] W_256^k; Bluestein: [fft_m][2] W_m^k; in double
   ScnDeviceMem<double> d_table;      // the plan's frequency table (scn_plan_set_table), read by the compaction kernel; grown on demand
@@ -170,6 +181,29 @@ int ensure_slot_stream(scn_plan *p, Slot &s);
 int ensure_slot_outputs(scn_plan *p, Slot &s, uint32_t gen);
 
 // scn_collect.hip
+// What the list kernels, the signal kernels and the confirm kernels read of a slot's pending / last submit, under the same names in
+// every argument struct: the regions, the hits' offsets, and the submit's header fields where they lie (the slot's pinned copy or the
+// plan's table)
+template <class A>
+void set_list_source(A &a, const scn_plan *p, const Slot &s) {
+  const SlotGen &g = s.cur();
+  a.regions = g.d_hits.get();
+  a.hit_region = p->hit_region;
+  a.offsets = s.d_offsets.get();
+  const bool table = g.table_first >= 0;
+  a.center_freq = table ? p->d_table.get() : s.centres(p->d.max_batch);
+  a.table_count = table ? p->table_count : 0u;
+  a.table_first = table ? (uint32_t)g.table_first : 0u;
+  a.seq_id = g.seq_given ? s.seq_ids(p->d.max_batch) : nullptr;
+  a.n_buffers = s.n_buffers;
+  a.n = p->d.n;
+  a.sample_rate = p->d.sample_rate;
+}
+// where work on an already complete list goes (top-up copies, scn_collect_more's windows, signals, the hit history): a stream with
+// nothing of a pending submit's kernels queued
+inline hipStream_t topup_stream_of(const scn_plan *p, const Slot &s) { return s.own_stream ? s.stream : p->h2d_stream.get(); }
+// the first `count` records of the slot's list are in pinned host memory (count 0: its scan and compaction are complete)
+int fetch_list(scn_plan *p, Slot &s, uint32_t count);
 ScnCompactArgs compact_args(const scn_plan *p, const Slot &s, uint32_t first, uint32_t cap, void *out);
 int build_list(scn_plan *p, Slot &s, bool prefetch);
 // (for scn_gather.hip) the collected slot's ordered list where the compaction kernel left it, in device memory.

@@ -62,6 +62,7 @@ class Plan:
         self._submit_device, self._collect, self._n_hits = self._L.scn_submit_device, self._L.scn_collect, C.c_uint32()
         self._submit_device_indexed = self._L.scn_submit_device_indexed
         self._baseline_rows = 0
+        self._history_rows = 0
         try:
             if floor_window is not None:
                 self.set_floor_window(*floor_window)
@@ -155,6 +156,44 @@ class Plan:
         out = np.empty((rows, self.n), np.float32)
         capi.check(self._L.scn_plan_get_baseline(self._h, int(first_row), rows, out.ctypes.data_as(C.c_void_p)), "scn_plan_get_baseline")
         return out
+
+    def set_history(self, rows):
+        """scn_plan_set_history: give the plan a hit history of `rows` rows, all zero (0 drops it) -- one uint32 per table entry and
+        fftshift index, bit k the visit k visits ago (scanner_hip.h, "Hit history").  Allowed while slots are pending."""
+        capi.check(self._L.scn_plan_set_history(self._h, int(rows)), "scn_plan_set_history")
+        self._history_rows = int(rows)
+
+    def update_history(self, slot):
+        """scn_plan_update_history: fold the hits of the slot's last collected submit into the rows of its units, on the GPU -- every
+        word of those rows shifts left by one and takes the bin's hit bit.  Once per submit; other slots may be pending."""
+        capi.check(self._L.scn_plan_update_history(self._h, slot), "scn_plan_update_history")
+
+    def history(self, first_row=0, rows=None):
+        """scn_plan_get_history: (history uint32 [rows, n] by fftshift index, visits uint32 [rows]) of rows [first_row, first_row +
+        rows) (to the history's end by default)."""
+        rows = max(0, self._history_rows - int(first_row)) if rows is None else int(rows)
+        hist, visits = np.empty((rows, self.n), np.uint32), np.empty(rows, np.uint32)
+        capi.check(self._L.scn_plan_get_history(self._h, int(first_row), rows, hist.ctypes.data_as(C.c_void_p), visits.ctypes.data_as(C.c_void_p)),
+                   "scn_plan_get_history")
+        return hist, visits
+
+    def collect_confirmed(self, slot, m, window, first=0, cap=None):
+        """scn_collect_confirmed: the records of the slot's last collected -- and folded -- submit whose bin was a hit in at least m of
+        the last `window` visits of its table entry, this one included: a subsequence of collect's list (HIT_DTYPE), bit for bit.
+        cap=None returns records [first, end) (one call for the total, one for the records); with an explicit cap the C-ABI's own
+        behaviour shows: ScannerError(E_TRUNCATED) when first + cap falls short of the total."""
+        total = C.c_uint32()
+        if cap is None:
+            st = self._L.scn_collect_confirmed(self._h, slot, int(m), int(window), int(first), None, 0, C.byref(total))
+            if st != capi.E_TRUNCATED:
+                capi.check(st, "scn_collect_confirmed")
+            cap = max(0, total.value - int(first))
+        out = np.zeros(cap, capi.HIT_DTYPE)
+        if cap:
+            capi.check(self._L.scn_collect_confirmed(self._h, slot, int(m), int(window), int(first), out.ctypes.data_as(C.c_void_p), cap,
+                                                     C.byref(total)), "scn_collect_confirmed")
+        self.last_n_confirmed = total.value
+        return out[: max(0, min(cap, total.value - int(first)))]
 
     def submit(self, slot, n_buffers, center_freqs=None, seq_ids=None, first_index=None):
         """Process the first n_buffers raw buffers of the pinned slot (async)."""
