@@ -22,6 +22,7 @@
 #include <new>
 #include <vector>
 
+#include "scn_gather_kernels.h"
 #include "scn_gather_protocol.h"
 #include "scn_plan.h"  // scn_fail, SCN_HIP, the resource holders; scn_plan_device_hits: a collected slot's list where it lies
 
@@ -350,36 +351,8 @@ int scn_gather_hits_device(scn_comm *c, scn_plan *plan, int slot, uint32_t root,
 // The steady-state form (scn_gather_protocol.h): pack -> ONE group of fixed-size sends / receives -> compaction, all on the
 // communicator's stream; the host comes back for the result whenever it likes (scn_gather_wait).
 // ---------------------------------------------------------------------------------------------------------------------------
+// The two kernels, their grids and every address into the ring, the outgoing buffer and the pinned list: scn_gather_kernels.h.
 namespace {
-// message = [header][cap records]; the first `h.sent` records of `src` follow the header
-__global__ __launch_bounds__(256) void scn_gather_pack_kernel(const scn_hit *src, ScnStreamHeader h, scn_hit *msg) {
-  typedef unsigned long long u64;
-  const u64 *s = reinterpret_cast<const u64 *>(src);
-  u64 *d = reinterpret_cast<u64 *>(msg + 1);
-  const size_t words = (size_t)h.sent * 3u;  // 24-byte records as three 8-byte words: coalesced
-  for (size_t e = (size_t)blockIdx.x * 256u + threadIdx.x; e < words; e += (size_t)gridDim.x * 256u) d[e] = s[e];
-  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<ScnStreamHeader *>(msg) = h;
-}
-
-// root: the world's messages [world][cap + 1] -> the rank-major list and the headers, both in pinned host memory.
-// grid = world x chunks; workgroup (r, c) finds rank r's place from the headers before it (world is a node's GPU count).
-__global__ __launch_bounds__(256) void scn_gather_compact_kernel(const scn_hit *ring, uint32_t world, uint32_t cap, uint64_t seq, scn_hit *list,
-                                                                  ScnStreamHeader *heads) {
-  typedef unsigned long long u64;
-  const uint32_t r = blockIdx.x % world, chunk = blockIdx.x / world, chunks = gridDim.x / world;
-  auto sent_of = [&](uint32_t q) -> uint32_t {
-    const ScnStreamHeader h = *reinterpret_cast<const ScnStreamHeader *>(ring + (size_t)q * (cap + 1u));
-    return (h.magic == SCN_STREAM_MAGIC && h.seq == seq && h.sent <= cap && h.sent <= h.count) ? h.sent : 0u;  // as scn_stream_outcome reads it
-  };
-  size_t off = 0;
-  for (uint32_t q = 0; q < r; q++) off += sent_of(q);
-  const size_t words = (size_t)sent_of(r) * 3u;
-  const u64 *s = reinterpret_cast<const u64 *>(ring + (size_t)r * (cap + 1u) + 1u);
-  u64 *d = reinterpret_cast<u64 *>(list + off);
-  for (size_t e = (size_t)chunk * 256u + threadIdx.x; e < words; e += (size_t)chunks * 256u) d[e] = s[e];
-  if (chunk == 0 && threadIdx.x == 0) heads[r] = *reinterpret_cast<const ScnStreamHeader *>(ring + (size_t)r * (cap + 1u));
-}
-
 int stream_buffers(scn_comm *c, uint32_t cap, bool root) {
   StreamGather &g = c->sg;
   if (g.cap != cap) {
@@ -391,13 +364,13 @@ int stream_buffers(scn_comm *c, uint32_t cap, bool root) {
     g.h_head.reset();
     g.cap = cap;
   }
-  const size_t msg = (size_t)cap + 1u;
-  SCN_HIP(g.d_msg.alloc(msg * SCN_GATHER_TICKETS));
+  SCN_HIP(g.d_msg.alloc(scn_gather_out_at(SCN_GATHER_TICKETS, cap)));
   for (int k = 0; k < SCN_GATHER_TICKETS; k++) SCN_HIP(g.done[k].create());
   if (root) {
-    SCN_HIP(g.d_ring.alloc(msg * (size_t)c->world * SCN_GATHER_TICKETS));
-    SCN_HIP(g.h_list.alloc(std::max<size_t>((size_t)cap * c->world, 1u) * SCN_GATHER_TICKETS));
-    SCN_HIP(g.h_head.alloc((size_t)c->world * SCN_GATHER_TICKETS));
+    const uint32_t world = (uint32_t)c->world;
+    SCN_HIP(g.d_ring.alloc(scn_gather_ring_at(SCN_GATHER_TICKETS, world, 0, cap)));
+    SCN_HIP(g.h_list.alloc(std::max<size_t>(scn_gather_list_at(SCN_GATHER_TICKETS, world, cap), SCN_GATHER_TICKETS)));
+    SCN_HIP(g.h_head.alloc(scn_gather_heads_at(SCN_GATHER_TICKETS, world)));
   }
   return SCN_OK;
 }
@@ -431,18 +404,17 @@ int scn_gather_post(scn_comm *c, scn_plan *plan, int slot, uint32_t root, uint32
   h.status = (uint32_t)(status != SCN_OK ? status : h.sent < n_local ? SCN_E_TRUNCATED : SCN_OK);
   h.magic = SCN_STREAM_MAGIC;
   h.seq = g.next_seq;
-  const size_t msg = (size_t)cap_per_rank + 1u;
-  scn_hit *out = is_root ? g.d_ring.get() + ((size_t)tk * c->world + c->rank) * msg : g.d_msg.get() + (size_t)tk * msg;
-  const uint32_t blocks = h.sent ? std::min<uint32_t>((h.sent * 3u + 255u) / 256u, 64u) : 1u;
-  hipLaunchKernelGGL(scn_gather_pack_kernel, dim3(blocks), dim3(256), 0, c->stream.get(), d_list, h, out);
-  SCN_HIP(hipGetLastError());
+  const uint32_t world = (uint32_t)c->world;
+  const size_t msg = scn_gather_msg_records(cap_per_rank);
+  scn_hit *out = is_root ? g.d_ring.get() + scn_gather_ring_at(tk, world, (uint32_t)c->rank, cap_per_rank) : g.d_msg.get() + scn_gather_out_at(tk, cap_per_rank);
+  SCN_HIP(scn_launch_gather_pack(d_list, h, out, c->stream.get()));
   if (c->world > 1) {
     ncclResult_t first_err = api.GroupStart();
     if (first_err == ncclSuccess) {
       if (is_root) {
         for (int r = 0; r < c->world; r++)
           if (r != c->rank) {
-            const ncclResult_t e = api.Recv(g.d_ring.get() + ((size_t)tk * c->world + r) * msg, sizeof(scn_hit) * msg, ncclUint8, r, c->comm, c->stream.get());
+            const ncclResult_t e = api.Recv(g.d_ring.get() + scn_gather_ring_at(tk, world, (uint32_t)r, cap_per_rank), sizeof(scn_hit) * msg, ncclUint8, r, c->comm, c->stream.get());
             if (e != ncclSuccess && first_err == ncclSuccess) first_err = e;  // keep posting: the peers' sends are coming
           }
       } else {
@@ -454,10 +426,8 @@ int scn_gather_post(scn_comm *c, scn_plan *plan, int slot, uint32_t root, uint32
     if (first_err != ncclSuccess) return scn_fail(SCN_E_COMM, "scn_gather_post: %s", api.GetErrorString(first_err));
   }
   if (is_root) {
-    const uint32_t chunks = std::max<uint32_t>(1u, std::min<uint32_t>((cap_per_rank * 3u + 2047u) / 2048u, 16u));
-    hipLaunchKernelGGL(scn_gather_compact_kernel, dim3((uint32_t)c->world * chunks), dim3(256), 0, c->stream.get(), g.d_ring.get() + (size_t)tk * c->world * msg,
-                       (uint32_t)c->world, cap_per_rank, h.seq, g.h_list.get() + (size_t)tk * cap_per_rank * c->world, g.h_head.get() + (size_t)tk * c->world);
-    SCN_HIP(hipGetLastError());
+    SCN_HIP(scn_launch_gather_compact(g.d_ring.get() + scn_gather_ring_at(tk, world, 0, cap_per_rank), world, cap_per_rank, h.seq,
+                                      g.h_list.get() + scn_gather_list_at(tk, world, cap_per_rank), g.h_head.get() + scn_gather_heads_at(tk, world), c->stream.get()));
   }
   SCN_HIP(hipEventRecord(g.done[tk].get(), c->stream.get()));
   g.posted[tk] = true;
@@ -481,10 +451,10 @@ int scn_gather_wait(scn_comm *c, uint32_t ticket, const scn_hit **list, uint64_t
   g.posted[ticket] = false;
   if (e != hipSuccess) return scn_fail(SCN_E_HIP, "scn_gather_wait: %s", hipGetErrorString(e));
   if (!g.as_root[ticket]) return SCN_OK;
-  const ScnGatherOutcome o = scn_stream_outcome(g.h_head.get() + (size_t)ticket * c->world, (uint32_t)c->world, g.cap, g.seq_of[ticket]);
+  const ScnGatherOutcome o = scn_stream_outcome(g.h_head.get() + scn_gather_heads_at(ticket, (uint32_t)c->world), (uint32_t)c->world, g.cap, g.seq_of[ticket]);
   if (per_rank) memcpy(per_rank, o.counts.data(), sizeof(uint32_t) * (size_t)c->world);
   if (n_total) *n_total = o.total;
-  if (list) *list = g.h_list.get() + (size_t)ticket * g.cap * c->world;
+  if (list) *list = g.h_list.get() + scn_gather_list_at(ticket, (uint32_t)c->world, g.cap);
   if (o.status == SCN_OK) return SCN_OK;
   if (o.status == SCN_E_TRUNCATED)
     return scn_fail(SCN_E_TRUNCATED, "rank %d holds %u hits, its message %u (cap_per_rank): the list has the first %u of them", o.bad_rank,

@@ -8,11 +8,46 @@ the other ranks.  On CPU (the gloo tests) the same gather runs over torch.distri
 computed by the C-ABI's scn_gather_layout.  Because shards are contiguous, rank-major concatenation is
 already the global (centre index, i) order.
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import capi
+
+STREAM_MAGIC = 0x53434E47
+STREAM_HEAD = np.dtype([("count", "<u4"), ("status", "<u4"), ("sent", "<u4"), ("magic", "<u4"), ("seq", "<u8")])  # ScnStreamHeader
+StreamOutcome = collections.namedtuple("StreamOutcome", "per_rank offsets status bad_rank bad_status step")
+
+
+def stream_outcome(heads, cap, seq):
+    """What the root makes of the headers of one post: scn_stream_outcome (scn_gather_protocol.h), restated for the
+    torch.distributed twin -- tests/test_gather_twin_cpu.py holds the two readings to each other on seeded header sets.
+    heads: STREAM_HEAD records, one per rank.  Returns per_rank (the ranks' true counts, 0 for a message that is not intact),
+    offsets (by what was sent: the list), status (capi.OK, E_TRUNCATED or E_COMM), the first bad rank (-1: none), what it
+    announced, and the step the failure belongs to (1: the rank could not prepare its part, 3: its message is not this post's)."""
+    heads = np.asarray(heads, dtype=STREAM_HEAD)
+    world = len(heads)
+    per_rank = np.zeros(world, np.uint32)
+    offsets = np.zeros(world + 1, np.uint64)
+    status, bad_rank, bad_status, step, trunc = capi.OK, -1, 0, 3, -1
+    for r in range(world):
+        count, st, sent, magic, hseq = (int(heads[r][f]) for f in ("count", "status", "sent", "magic", "seq"))
+        intact = magic == STREAM_MAGIC and hseq == seq % (1 << 64) and sent <= cap and sent <= count
+        per_rank[r] = count if intact else 0
+        offsets[r + 1] = int(offsets[r]) + (sent if intact else 0)
+        if not intact:
+            if bad_rank < 0:
+                status, bad_rank, bad_status = capi.E_COMM, r, capi.E_COMM
+        elif st != capi.OK and not (st == capi.E_TRUNCATED and sent < count):
+            # (E_TRUNCATED with nothing cut off is the PLAN's device list being shorter than its hits: nothing was sent)
+            if bad_rank < 0:
+                status, bad_rank, bad_status, step = capi.E_COMM, r, st, 1
+        elif sent < count and trunc < 0:
+            trunc = r   # a rank's list did not fit its message: the list holds its first cap records
+    if status == capi.OK and trunc >= 0:
+        status, bad_rank, bad_status = capi.E_TRUNCATED, trunc, capi.E_TRUNCATED
+    return StreamOutcome(per_rank, offsets, status, bad_rank, bad_status, step)
 
 
 def shard_range(count, rank, world):
@@ -142,8 +177,8 @@ class HitGather:
     def _L_wait(self):
         return capi.lib().scn_gather_wait
 
-    _STREAM_MAGIC = 0x53434E47
-    _HEAD = np.dtype([("count", "<u4"), ("status", "<u4"), ("sent", "<u4"), ("magic", "<u4"), ("seq", "<u8")])
+    _STREAM_MAGIC = STREAM_MAGIC
+    _HEAD = STREAM_HEAD
 
     def _post_torch(self, hits, cap, dst, local_status):
         import torch
@@ -187,27 +222,18 @@ class HitGather:
         per_rank = np.zeros(self.world, np.uint32)
         if self.rank != dst:
             return np.zeros(0, capi.HIT_DTYPE), per_rank
-        # the root's reading of the headers: scn_stream_outcome (scn_gather_protocol.h), restated
-        parts, bad, trunc = [], None, None
-        for r in range(self.world):
-            m = out[r].numpy().view(capi.HIT_DTYPE)
-            h = m[:1].view(self._HEAD)[0]
-            intact = h["magic"] == self._STREAM_MAGIC and h["seq"] == seq and h["sent"] <= cap and h["sent"] <= h["count"]
-            if not intact:
-                bad = bad or (r, capi.E_COMM, "does not belong to this post")
-                continue
-            per_rank[r] = h["count"]
-            parts.append(m[1:1 + int(h["sent"])])
-            if h["status"] != capi.OK and not (h["status"] == capi.E_TRUNCATED and h["sent"] < h["count"]):
-                bad = bad or (r, int(h["status"]), "could not prepare its part of the gather")
-            elif h["sent"] < h["count"]:
-                trunc = trunc if trunc is not None else r
+        # the root's reading of the headers: scn_stream_outcome (scn_gather_protocol.h), restated in stream_outcome above
+        msgs = [out[r].numpy().view(capi.HIT_DTYPE) for r in range(self.world)]
+        o = stream_outcome(np.concatenate([m[:1].view(self._HEAD) for m in msgs]), cap, seq)
+        per_rank = o.per_rank
+        parts = [msgs[r][1:1 + int(o.offsets[r + 1] - o.offsets[r])] for r in range(self.world)]
         self.last_per_rank = per_rank
         self.last_list = np.concatenate(parts) if parts else np.zeros(0, capi.HIT_DTYPE)
-        if bad:
-            raise capi.ScannerError(capi.E_COMM, "gather wait", f"rank {bad[0]} {bad[2]} (status {bad[1]})")
-        if trunc is not None:
-            raise capi.ScannerError(capi.E_TRUNCATED, "gather wait", f"rank {trunc} holds {per_rank[trunc]} hits, its message {cap}")
+        if o.status == capi.E_TRUNCATED:
+            raise capi.ScannerError(capi.E_TRUNCATED, "gather wait", f"rank {o.bad_rank} holds {per_rank[o.bad_rank]} hits, its message {cap}")
+        if o.status != capi.OK:
+            what = "could not prepare its part of the gather" if o.step == 1 else "does not belong to this post"
+            raise capi.ScannerError(capi.E_COMM, "gather wait", f"rank {o.bad_rank} {what} (status {o.bad_status})")
         return self.last_list, per_rank
 
     def _gather_torch(self, hits, dst, local_status=capi.OK):

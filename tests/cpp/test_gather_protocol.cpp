@@ -129,9 +129,43 @@ std::vector<int> run(uint32_t world, Fault fault, uint32_t bad_rank, uint32_t ro
   else delete w;
   return status;
 }
+
+// `--outcomes FILE`: scn_stream_outcome's reading of header sets drawn elsewhere (tests/test_gather_twin_cpu.py holds sweep.py's
+// restatement to it).  A line per set: cap seq world, then count status sent magic seq per rank.  Printed per set:
+// status bad_rank bad_status step total, then the counts, then the offsets.
+int print_outcomes(const char *path) {
+  FILE *f = fopen(path, "r");
+  if (!f) {
+    fprintf(stderr, "cannot open %s\n", path);
+    return 2;
+  }
+  unsigned long long cap, seq, world;
+  int sets = 0;
+  while (fscanf(f, "%llu %llu %llu", &cap, &seq, &world) == 3) {
+    std::vector<ScnStreamHeader> h((size_t)world);
+    for (auto &x : h) {
+      unsigned long long v[5];
+      if (fscanf(f, "%llu %llu %llu %llu %llu", &v[0], &v[1], &v[2], &v[3], &v[4]) != 5) {
+        fprintf(stderr, "set %d: short line\n", sets);
+        fclose(f);
+        return 2;
+      }
+      x = ScnStreamHeader{(uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2], (uint32_t)v[3], (uint64_t)v[4]};
+    }
+    const ScnGatherOutcome o = scn_stream_outcome(h.data(), (uint32_t)world, (uint32_t)cap, (uint64_t)seq);
+    printf("%d %d %u %d %llu", o.status, o.bad_rank, o.bad_status, o.step, (unsigned long long)o.total);
+    for (uint32_t c : o.counts) printf(" %u", c);
+    for (uint64_t x : o.offsets) printf(" %llu", (unsigned long long)x);
+    printf("\n");
+    sets++;
+  }
+  fclose(f);
+  return sets ? 0 : 2;
+}
 }  // namespace
 
-int main() {
+int main(int argc, char **argv) {
+  if (argc == 3 && !strcmp(argv[1], "--outcomes")) return print_outcomes(argv[2]);
   for (uint32_t world : {3u, 8u}) {
     // clean run: rank-major concatenation on the root, every rank OK
     World *w = nullptr;
