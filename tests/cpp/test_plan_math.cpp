@@ -67,6 +67,15 @@ static void test_twiddles() {
   }
 }
 
+// cosl / sinl of the chirp's exactly reduced angle -pi (i^2 mod 2n) / n: the reduction in uint64_t (i * i passes 2^31 from n = 46342 on)
+static const long double kPiL = 3.14159265358979323846264338327950288L;
+static void chirp_exact(uint32_t i, uint32_t n, long double &c, long double &s) {
+  const uint64_t r = ((uint64_t)i * (uint64_t)i) % (2ull * (uint64_t)n);
+  const long double a = -kPiL * (long double)r / (long double)n;
+  c = cosl(a);
+  s = sinl(a);
+}
+
 static void test_bluestein(uint32_t n, uint32_t m_want) {
   const ScnBluesteinTables t = bluestein_tables(n);
   CHECK(t.m == m_want && (1u << t.log2m) == t.m && t.m >= 2 * n - 1 && t.m / 2 < 2 * n - 1);
@@ -75,10 +84,11 @@ static void test_bluestein(uint32_t n, uint32_t m_want) {
   CHECK(t.twiddle == twiddles<double>(t.m));
   vec br(t.m, 0.0), bi(t.m, 0.0), want_re, want_im, got_re(t.m), got_im(t.m);
   for (uint32_t i = 0; i < n; i++) {  // w[i] = exp(-i pi i^2 / n), i^2 reduced mod 2n
-    const double a = -kPi * (double)((i * i) % (2 * n)) / (double)n;
-    CHECK(std::fabs(t.chirp[2 * i] - std::cos(a)) <= 1e-15 && std::fabs(t.chirp[2 * i + 1] - std::sin(a)) <= 1e-15);
-    br[i] = br[(t.m - i) % t.m] = std::cos(a);  // the cyclic conj(w[|k|])
-    bi[i] = bi[(t.m - i) % t.m] = -std::sin(a);
+    long double c, s;
+    chirp_exact(i, n, c, s);
+    CHECK(fabsl((long double)t.chirp[2 * i] - c) <= 1e-15L && fabsl((long double)t.chirp[2 * i + 1] - s) <= 1e-15L);
+    br[i] = br[(t.m - i) % t.m] = (double)c;  // the cyclic conj(w[|k|])
+    bi[i] = bi[(t.m - i) % t.m] = -(double)s;
   }
   naive_dft(br, bi, want_re, want_im);
   for (uint32_t k = 0; k < t.m; k++) {
@@ -88,6 +98,54 @@ static void test_bluestein(uint32_t n, uint32_t m_want) {
     got_im[k] = t.bfilter[2 * k + 1];
   }
   CHECK(rel_to_largest(got_re, got_im, want_re, want_im) <= 1e-12);
+}
+
+// The sizes at which i * i passes 2^31 (n >= 46342; 46341 is the last below) and comes within 0.006 % of 2^32 (65535): every chirp
+// entry against cosl / sinl of the EXACTLY reduced angle -pi (i^2 mod 2n) / n, the reduction in uint64_t; 64 spread bins of the
+// filter transform (0, 1, m/2 and m-1 among them) against the direct sum in long double over a long double W_m table.  The full
+// naive_dft stays at 17 and 48.
+static void test_bluestein_large(uint32_t n) {
+  const ScnBluesteinTables t = bluestein_tables(n);
+  const uint32_t m = t.m;
+  CHECK((1u << t.log2m) == m && m >= 2 * n - 1 && m / 2 < 2 * n - 1 && m == 131072u);
+  CHECK(t.chirp.size() == 2 * (size_t)n && t.bfilter.size() == 2 * (size_t)m && t.twiddle.size() == 2 * (size_t)m);
+  if (g_failed) return;
+  std::vector<long double> br(m, 0.0L), bi(m, 0.0L), wr(m), wi(m);
+  double worst = 0.0;
+  for (uint32_t i = 0; i < n; i++) {
+    long double c, s;
+    chirp_exact(i, n, c, s);
+    worst = std::fmax(worst, std::fmax((double)fabsl((long double)t.chirp[2 * i] - c), (double)fabsl((long double)t.chirp[2 * i + 1] - s)));
+    br[i] = br[(m - i) % m] = c;  // the cyclic conj(w[|k|])
+    bi[i] = bi[(m - i) % m] = -s;
+  }
+  CHECK(worst <= 1e-15);
+  for (uint32_t k = 0; k < m; k++) {
+    const long double a = -2.0L * kPiL * (long double)k / (long double)m;
+    wr[k] = cosl(a);
+    wi[k] = sinl(a);
+  }
+  std::vector<uint32_t> bins = {0u, 1u, m / 2u, m - 1u};
+  for (uint32_t s = 1; s <= 60; s++) bins.push_back((uint32_t)(((uint64_t)s * (m - 1u)) / 61u) | 1u);  // odd, so none of the four above but m - 1
+  CHECK(bins.size() == 64);
+  long double err = 0.0L, top = 0.0L;
+  for (uint32_t k : bins) {
+    CHECK(k < m);
+    long double sr = 0.0L, si = 0.0L;
+    for (uint32_t j = 0; j < m; j++) {
+      if (j >= n && j <= m - n) continue;  // the zero padding between the two halves of the filter
+      const uint32_t e = (uint32_t)(((uint64_t)j * k) & (m - 1u));
+      sr += br[j] * wr[e] - bi[j] * wi[e];
+      si += br[j] * wi[e] + bi[j] * wr[e];
+    }
+    sr /= (long double)m;
+    si /= (long double)m;
+    err = fmaxl(err, hypotl((long double)t.bfilter[2 * k] - sr, (long double)t.bfilter[2 * k + 1] - si));
+    top = fmaxl(top, hypotl(sr, si));
+  }
+  std::printf("bluestein_tables(%u): chirp within %.2e of the exactly reduced angle's, 64 filter bins within %.2Le of the largest\n", n, worst,
+              top > 0.0L ? err / top : 0.0L);
+  CHECK(top > 0.0L && err <= 1e-12L * top);
 }
 
 struct Mask {
@@ -273,6 +331,7 @@ int main() {
   test_twiddles();
   test_bluestein(17, 64);
   test_bluestein(48, 128);
+  for (uint32_t n : {46341u, 46342u, 65534u, 65535u}) test_bluestein_large(n);
   test_evaluated_bins(16, 0, 0.75, false);
   test_evaluated_bins(64, 4, 0.75, false);
   test_evaluated_bins(64, 4, 0.01, true);

@@ -550,9 +550,10 @@ def test_strong_tone_accuracy_16384(torch_cuda, oracle_mod):
     (65535, capi.KIND_SHORT_COMPLEX, 12, False),   # the ends of the range (65535: a 131072-point transform)
 ])
 def test_non_power_of_two_sizes_vs_oracle(torch_cuda, oracle_mod, n, kind, enob, dc):
-    """--count is any integer in the reference (FFTW plans it, fft.cpp:4-11).  Sizes that are not powers of two run
-    Bluestein's algorithm over the staged path; the oracle evaluates the DFT sum itself in double for them.  Odd sizes
-    exercise the general form of the mask: j = (i + N/2) % N with an integer N/2 (process.cpp:45-47)."""
+    """--count is any integer in the reference (FFTW plans it, fft.cpp:4-11).  Of the sizes that are not powers of two, 1000 / 3000 /
+    6000 run the fused mixed-radix kernels (tests/test_dispatch_gpu.py MIXED_SIZES) and the others Bluestein's algorithm over the
+    staged path (tests/test_bluestein_gpu.py holds that path to its own bar); the oracle evaluates the DFT sum itself in double for
+    all of them.  Odd sizes exercise the general form of the mask: j = (i + N/2) % N with an integer N/2 (process.cpp:45-47)."""
     nb = 24 if n < 8000 else 3 if n < 40000 else 2      # (the oracle's direct DFT is O(N^2) per buffer)
     x = synth.cfloat_batch(n, nb, seed=80 + n % 1000, sigma=0.1)
     raw = synth.quantize(x, kind) if kind != capi.KIND_FLOAT_COMPLEX else x
@@ -671,15 +672,16 @@ def _negative_sum_buffers(n, nb, kind, seed):
 
 # one size per kernel family, each with its own DC reduction: tiny (a segmented shuffle over R lanes), small (over T lanes),
 # narrow (wave sums through LDS), 8192 (two samples per lane and load), 16384 (half a buffer prefetched), the four-step pair
-# (scn_big_dc_kernel: a pass of its own over the raw samples), Bluestein (scn_gen_load_kernel)
+# (scn_big_dc_kernel: a pass of its own over the raw samples), mixed radix (1000: the fused mixed-radix kernel's reduction), Bluestein
+# (1001: scn_gen_load_kernel's sums over 256 threads and its (uint32) / n)
 @pytest.mark.parametrize("kind,enob", [(capi.KIND_SHORT_COMPLEX, 12), (capi.KIND_SHORT, 12), (capi.KIND_BYTE_COMPLEX, 8)],
                          ids=["int16", "int16planar", "int8"])
-@pytest.mark.parametrize("n", [64, 256, 1024, 4096, 8192, 16384, 32768, 1000])
+@pytest.mark.parametrize("n", [64, 256, 1024, 4096, 8192, 16384, 32768, 1000, 1001])
 def test_dc_quirk_negative_mean(torch_cuda, oracle_mod, n, kind, enob):
     """utility.cpp:77-78: int32 /= uint32 turns a negative sum into a huge positive 'mean'.  Every kernel family must reproduce the
     same (nonsensical) samples, hence the same spectrum and the same detections -- bit for bit wherever the spectrum tolerance
     itself cannot move a bin across the threshold (tolerances.flip_unsafe)."""
-    nb = {64: 331, 256: 83, 1024: 41, 4096: 13, 8192: 11, 16384: 7, 32768: 5, 1000: 12}[n]
+    nb = {64: 331, 256: 83, 1024: 41, 4096: 13, 8192: 11, 16384: 7, 32768: 5, 1000: 12, 1001: 13}[n]
     raw = _negative_sum_buffers(n, nb, kind, seed=4 + n)
     o = oracle_mod.Oracle(n, FS, 1e9, kind=kind, enob=enob, correct_dc=True)
     c = o.convert(raw[0].reshape(-1))
