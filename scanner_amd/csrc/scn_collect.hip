@@ -7,7 +7,7 @@
 
 // the first `count` records of the slot's list are in pinned host memory
 int fetch_list(scn_plan *p, Slot &s, uint32_t count) {
-  if (!s.list_built)
+  if (!s.life.list_built)
     if (int st = build_list(p, s, false)) return st;
   SCN_HIP(hipEventSynchronize(s.cur().list_done.get()));
   count = std::min(count, p->d.max_hits);
@@ -62,7 +62,7 @@ int build_list(scn_plan *p, Slot &s, bool prefetch) {
   }
   SCN_HIP(hipEventRecord(s.cur().list_done.get(), last));
   s.cur().list_used = true;
-  s.list_built = true;
+  on_list_built(s.life);
   return SCN_OK;
 }
 
@@ -71,7 +71,7 @@ extern "C" {
 int scn_wait(scn_plan *p, int slot) {
   if (int st = check_slot(p, slot)) return st;
   Slot &s = p->slot[slot];
-  if (!s.pending) return scn_fail(SCN_E_STATE, "slot %d has nothing submitted", slot);
+  if (int st = require_pending(s.life, slot)) return st;
   SCN_HIP(hipSetDevice(p->d.device_id));
   SCN_HIP(hipEventSynchronize(s.done.get()));
   return SCN_OK;
@@ -84,9 +84,9 @@ int scn_collect_time_domain(scn_plan *p, int slot, float *max_db, float *min_db,
   st = scn_wait(p, slot);
   if (st) return st;
   Slot &s = p->slot[slot];
-  s.pending = false;
+  on_collect_time_domain(s.life);
   const float *mx = s.h_td.get(), *mn = s.h_td.get() + p->d.max_batch;
-  for (uint32_t b = 0; b < s.n_buffers; b++) {
+  for (uint32_t b = 0; b < s.life.n_buffers; b++) {
     if (max_db) max_db[b] = mx[b];
     if (min_db) min_db[b] = mn[b];
     if (above) above[b] = mx[b] >= p->d.threshold;  // process.cpp:226
@@ -102,8 +102,8 @@ int scn_collect(scn_plan *p, int slot, float *power_db, scn_hit *hits, uint32_t 
   st = scn_wait(p, slot);  // the kernel and the per-buffer counts; the ordered list has an event of its own
   if (st) return st;
   Slot &s = p->slot[slot];
-  s.pending = false;
-  const uint32_t n = p->d.n, nb = s.n_buffers;
+  on_take(s.life);  // (before the argument checks below: a collect they refuse has consumed the submit)
+  const uint32_t n = p->d.n, nb = s.life.n_buffers;
   const bool have_hits = (p->d.flags & SCN_OUT_HITS) != 0;
   if ((hits || trigger) && !have_hits) return scn_fail(SCN_E_INVALID, "plan was created without SCN_OUT_HITS");
   if (power_db && !s.cur_power) return scn_fail(SCN_E_INVALID, "plan was created without SCN_OUT_SPECTRUM");
@@ -122,10 +122,7 @@ int scn_collect(scn_plan *p, int slot, float *power_db, scn_hit *hits, uint32_t 
   } else if (trigger) {
     memset(trigger, 0, nb);
   }
-  s.list_valid = have_hits;
-  s.folded_epoch = 0;  // (a new collected submit: not yet part of the hit history)
-  if (total > 0x7fffffffu) return scn_fail(SCN_E_INVALID, "%llu hits in one submit: split the batch", (unsigned long long)total);
-  s.total_hits = (uint32_t)total;
+  if ((st = on_collect(s.life, have_hits, total))) return st;
   if (have_hits) {  // what the automatic mode goes by at the next submit
     if (total && p->view_age < 0xffffffffu) p->view_age++;
     p->records_wanted = hits != nullptr || p->view_age <= 4u;
@@ -162,10 +159,10 @@ int scn_collect_more(scn_plan *p, int slot, uint32_t first, scn_hit *hits, uint3
   if (!hits || !n_written) return scn_fail(SCN_E_INVALID, "null argument");
   *n_written = 0;
   Slot &s = p->slot[slot];
-  if (s.pending || !s.list_valid) return scn_fail(SCN_E_STATE, "slot %d: no collected submit whose hit list is still on the device", slot);
-  if (first >= s.total_hits || hit_cap == 0) return SCN_OK;
+  if ((st = require_list(s.life, slot, "hit list is still on the device"))) return st;
+  if (first >= s.life.total_hits || hit_cap == 0) return SCN_OK;
   SCN_HIP(hipSetDevice(p->d.device_id));
-  const uint32_t want = std::min(hit_cap, s.total_hits - first);
+  const uint32_t want = std::min(hit_cap, s.life.total_hits - first);
   if (first + want <= p->d.max_hits) {  // still inside the part the plan keeps
     if ((st = fetch_list(p, s, first + want))) return st;
     memcpy(hits, s.h_list.get() + first, sizeof(scn_hit) * want);
@@ -193,8 +190,8 @@ int scn_collect_signals(scn_plan *p, int slot, uint32_t max_gap, uint32_t first,
   if (p->d.mode != SCN_MODE_FREQUENCY_DOMAIN) return scn_fail(SCN_E_INVALID, "time-domain plan: it has no hits to merge");
   if (!(p->d.flags & SCN_OUT_HITS)) return scn_fail(SCN_E_INVALID, "plan was created without SCN_OUT_HITS");
   Slot &s = p->slot[slot];
-  if (s.pending || !s.list_valid) return scn_fail(SCN_E_STATE, "slot %d: no collected submit whose hit list is still on the device", slot);
-  if (s.total_hits == 0) return SCN_OK;
+  if ((st = require_list(s.life, slot, "hit list is still on the device"))) return st;
+  if (s.life.total_hits == 0) return SCN_OK;
   SCN_HIP(hipSetDevice(p->d.device_id));
   if ((st = fetch_list(p, s, 0))) return st;  // (the hits' offsets come from the scan: wait for it)
   SCN_HIP(s.d_sig_counts.alloc(p->d.max_batch));
@@ -211,7 +208,7 @@ int scn_collect_signals(scn_plan *p, int slot, uint32_t max_gap, uint32_t first,
   SCN_HIP(scn_launch_signal_count(a, side));
   SCN_HIP(scn_launch_hit_scan(scan, side));
   uint32_t total = 0;
-  SCN_HIP(hipMemcpyAsync(&total, s.d_sig_offsets.get() + s.n_buffers, sizeof(uint32_t), hipMemcpyDeviceToHost, side));
+  SCN_HIP(hipMemcpyAsync(&total, s.d_sig_offsets.get() + s.life.n_buffers, sizeof(uint32_t), hipMemcpyDeviceToHost, side));
   SCN_HIP(hipStreamSynchronize(side));
   *n_signals = total;
   const uint32_t want = first < total ? std::min(cap, total - first) : 0u;
@@ -234,10 +231,9 @@ int scn_collect_floor(scn_plan *p, int slot, float *floor_db) {
   if (!floor_db) return scn_fail(SCN_E_INVALID, "null argument");
   if (!p->floor) return scn_fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_FLOOR");
   Slot &s = p->slot[slot];
-  if (s.pending || !s.list_valid) return scn_fail(SCN_E_STATE, "slot %d: no collected submit whose floor is still available", slot);
-  if (s.floor_windowed)
-    return scn_fail(SCN_E_INVALID, "slot %d was submitted under a floor window: every bin has a floor of its own (scn_local_floor_from_spectrum), no unit has one", slot);
-  if (s.n_buffers) memcpy(floor_db, s.h_floor.get(), sizeof(float) * s.n_buffers);  // (in pinned memory since `done`: scn_collect waited for it)
+  if (int st = require_list(s.life, slot, "floor is still available")) return st;
+  if (int st = require_unit_floor(s.life, slot)) return st;
+  if (s.life.n_buffers) memcpy(floor_db, s.h_floor.get(), sizeof(float) * s.life.n_buffers);  // (in pinned memory since `done`: scn_collect waited for it)
   return SCN_OK;
 }
 
@@ -246,9 +242,9 @@ int scn_hits_view(scn_plan *p, int slot, const scn_hit **hits, uint32_t *n) {
   if (st) return st;
   if (!hits || !n) return scn_fail(SCN_E_INVALID, "null argument");
   Slot &s = p->slot[slot];
-  if (s.pending || !s.list_valid) return scn_fail(SCN_E_STATE, "slot %d: no collected submit whose hit list is still available", slot);
+  if ((st = require_list(s.life, slot, "hit list is still available"))) return st;
   SCN_HIP(hipSetDevice(p->d.device_id));
-  *n = std::min(s.total_hits, p->d.max_hits);
+  *n = std::min(s.life.total_hits, p->d.max_hits);
   p->view_age = 0;  // (a caller that reads the list through the view wants it built eagerly too)
   p->records_wanted = true;
   if (*n && (st = fetch_list(p, s, *n))) return st;
@@ -264,21 +260,21 @@ int scn_plan_device_hits(scn_plan *p, int slot, const scn_hit **d_list, uint32_t
   if (!d_list || !n) return scn_fail(SCN_E_INVALID, "null argument");
   if (list_ready) *list_ready = nullptr;
   Slot &s = p->slot[slot];
-  if (s.pending || !s.list_valid) return scn_fail(SCN_E_STATE, "slot %d: no collected submit whose hit list is still on the device", slot);
-  if (s.total_hits > p->d.max_hits)
+  if ((st = require_list(s.life, slot, "hit list is still on the device"))) return st;
+  if (s.life.total_hits > p->d.max_hits)
     return scn_fail(SCN_E_TRUNCATED, "slot %d holds %u hits, the plan's device list %u (max_hits): gather from a host list read with scn_collect_more",
-                    slot, s.total_hits, p->d.max_hits);
+                    slot, s.life.total_hits, p->d.max_hits);
   SCN_HIP(hipSetDevice(p->d.device_id));
   p->device_list_age = 0;  // (a caller that sends the list from the device wants it built eagerly too: behind the launch, on the list
   p->device_list_wanted = true;  // stream, instead of here with the host waiting for it -- 56 us per scn_gather_post against 3, r06_experiments.md)
-  if (s.total_hits) {
-    if (!s.list_built)
+  if (s.life.total_hits) {
+    if (!s.life.list_built)
       if ((st = build_list(p, s, false))) return st;
     if (list_ready) *list_ready = (void *)s.cur().list_done.get();
     else SCN_HIP(hipEventSynchronize(s.cur().list_done.get()));
   }
   *d_list = s.d_list.get();
-  *n = s.total_hits;
+  *n = s.life.total_hits;
   if (device_id) *device_id = p->d.device_id;
   return SCN_OK;
 }

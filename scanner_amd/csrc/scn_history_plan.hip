@@ -50,11 +50,11 @@ int scn_plan_update_history(scn_plan *p, int slot) {
   if (int st = check_slot(p, slot)) return st;
   if (int st = check_history_plan(p)) return st;
   Slot &s = p->slot[slot];
-  if (s.pending || !s.list_valid) return scn_fail(SCN_E_STATE, "slot %d: no collected submit whose hit list is still on the device", slot);
-  const bool units = s.n_buffers != 0;  // (a submit without units left the slot's header fields as they were: it named no table entry)
-  if (int st = check_history_fold(p->history_rows, s.n_buffers, units && s.cur().table_first >= 0, p->table_count)) return st;
-  if (s.folded_epoch) return scn_fail(SCN_E_STATE, "slot %d: its submit is already part of the history", slot);
-  s.folded_epoch = ++p->history_epoch;
+  if (int st = require_list(s.life, slot, "hit list is still on the device")) return st;
+  const bool units = s.life.n_buffers != 0;  // (a submit without units left the slot's header fields as they were: it named no table entry)
+  if (int st = check_history_fold(p->history_rows, s.life.n_buffers, units && s.cur().table_first >= 0, p->table_count)) return st;
+  if (int st = require_unfolded(s.life, slot)) return st;
+  on_fold(s.life, ++p->history_epoch);
   if (!units) return SCN_OK;  // (no unit, no visit)
   SCN_HIP(hipSetDevice(p->d.device_id));
   // The regions and the counts are complete -- the slot's collect waited for the kernel that wrote them -- and the fold reads the
@@ -66,7 +66,7 @@ int scn_plan_update_history(scn_plan *p, int slot) {
   a.history = p->d_history.get();
   a.visits = p->d_visits.get();
   a.n = p->d.n;
-  a.n_units = s.n_buffers;
+  a.n_units = s.life.n_buffers;
   a.rows = p->history_rows;
   a.first = history_first(p, s);
   hipStream_t side = topup_stream_of(p, s);
@@ -96,12 +96,9 @@ int scn_collect_confirmed(scn_plan *p, int slot, uint32_t m, uint32_t window, ui
   if (int st = check_history_plan(p)) return st;
   if (int st = check_history_window(m, window)) return st;
   Slot &s = p->slot[slot];
-  if (s.pending || !s.list_valid) return scn_fail(SCN_E_STATE, "slot %d: no collected submit whose hit list is still on the device", slot);
-  // (stricter than rows that do not overlap would need -- and never wrong: the words a record is held against are those its own
-  // submit was folded into, with nothing folded since)
-  if (!s.folded_epoch || s.folded_epoch != p->history_epoch || !p->history_rows)
-    return scn_fail(SCN_E_STATE, "slot %d: its submit is not the history's latest fold (scn_plan_update_history)", slot);
-  if (s.total_hits == 0) return SCN_OK;
+  if (int st = require_list(s.life, slot, "hit list is still on the device")) return st;
+  if (int st = require_latest_fold(s.life, slot, p->history_epoch, p->history_rows)) return st;
+  if (s.life.total_hits == 0) return SCN_OK;
   SCN_HIP(hipSetDevice(p->d.device_id));
   int st = fetch_list(p, s, 0);  // (the hits' offsets come from the scan: wait for it)
   if (st) return st;
@@ -123,7 +120,7 @@ int scn_collect_confirmed(scn_plan *p, int slot, uint32_t m, uint32_t window, ui
   SCN_HIP(scn_launch_confirm_count(a, side));
   SCN_HIP(scn_launch_hit_scan(scan, side));
   uint32_t total = 0;
-  SCN_HIP(hipMemcpyAsync(&total, s.d_conf_offsets.get() + s.n_buffers, sizeof(uint32_t), hipMemcpyDeviceToHost, side));
+  SCN_HIP(hipMemcpyAsync(&total, s.d_conf_offsets.get() + s.life.n_buffers, sizeof(uint32_t), hipMemcpyDeviceToHost, side));
   SCN_HIP(hipStreamSynchronize(side));
   *n_confirmed = total;
   const uint32_t want = first < total ? std::min(cap, total - first) : 0u;

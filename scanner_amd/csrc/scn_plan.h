@@ -2,7 +2,8 @@
 // scn_sizes.h: which sizes each kernel family takes, the path of a size (no HIP header).  scn_host.hip: arithmetic and entry points that
 // never touch HIP -- a descriptor's defaults, checks and everything derived from it (resolve_plan, resolve_welch) and the contents of
 // the tables; scn_plan.hip: the device side of create (streams, uploads), first-use allocation, destroy, getters;
-// scn_submit.hip / scn_collect.hip: the two sides of a slot; scn_welch_plan.hip: the Welch plan.
+// scn_slot_life.h: what a slot may do next -- every precondition and every transition of its life cycle (no HIP header);
+// scn_submit.hip / scn_collect.hip: the two sides of a slot; scn_history_plan.hip: the hit history; scn_welch_plan.hip: the Welch plan.
 //
 // A plan owns: one HIP stream, the window and twiddle tables, and SCN_NUM_SLOTS independent result slots (double buffering:
 // the host fills / drains one slot while the GPU works on the other -- the replacement for the reference's MemoryPool + bounded
@@ -17,6 +18,7 @@
 #include "scn_host.h"
 #include "scn_kernels.h"
 #include "scn_resource.h"
+#include "scn_slot_life.h"
 
 #define SCN_HIP(call)                                                                              \
   do {                                                                                             \
@@ -81,9 +83,6 @@ struct Slot {
   ScnDeviceMem<scn_hit> d_list;     // device [max_hits]
   ScnPinnedMem<scn_hit> h_list;     // pinned [max_hits]
   uint32_t prefetched = 0;          // leading records of the current list that are (being) copied to h_list
-  bool list_valid = false;          // regions, counts and offsets of the last collected submit are still on the device
-  bool list_built = false;          // the scan + compaction of the pending / last submit have been enqueued
-  uint32_t total_hits = 0;          // of the last collected submit
   ScnDeviceMem<scn_hit> d_window;   // scratch of scn_collect_more, grown on demand
   // scn_collect_signals: signals per unit and their exclusive scan ([max_batch], [max_batch + 1]; allocated at the first call),
   // and the window of records the build kernel writes before they are copied out (grown on demand, like d_window)
@@ -93,23 +92,19 @@ struct Slot {
   // (the same three, allocated and grown the same way)
   ScnDeviceMem<uint32_t> d_conf_counts, d_conf_offsets;
   ScnDeviceMem<scn_hit> d_conf_window;
-  uint64_t folded_epoch = 0;        // scn_plan::history_epoch when the last collected submit was folded into the hit history (0: it was not)
   // floor-detector plans (scn_floor.hip): floor_db of the pending / last submit's units, kernel-written device memory and the pinned
   // copy a DMA behind the counts' brings (scn_collect_floor reads it).  ONE generation of each is enough, unlike the regions and
   // counts: the only reader of d_floor is that DMA, which is complete when `done` is -- and a slot is not submitted again before
   // its collect has waited for `done` --, and h_floor is promised only until the slot's next submit.
   ScnDeviceMem<float> d_floor;      // [max_batch]
   ScnPinnedMem<float> h_floor;      // [max_batch]
-  bool floor_windowed = false;      // the pending / last submit ran under a floor window: it has no per-unit floor (scn_collect_floor)
   ScnDeviceMem<float> d_detect_power;  // [max_batch][N] the spectrum the detect kernel reads when the caller keeps none (hits-only floor / baseline plans)
   // baseline plans (scn_baseline.hip): what scn_plan_update_baseline needs of the slot's last submit -- the spectrum its detect
   // kernel read (cur_power, d_detect_power: still intact, the slot's next submit is what overwrites it), its units and its first_index
   const float *base_power = nullptr;
   uint32_t base_units = 0, base_first = 0;
-  bool base_submitted = false;      // ... and that there has been one
   ScnEvent done;
-  bool pending = false;
-  uint32_t n_buffers = 0;
+  SlotLife life;                    // what the slot may do next (scn_slot_life.h): written by its on_* functions only
 };
 
 // Where the ordered hit list of a submit is built: behind the kernel on the list stream, overlapping the next launch (plus a
@@ -175,6 +170,16 @@ hipError_t upload(ScnDeviceMem<D> &dst, const std::vector<T> &v) {
   return e != hipSuccess ? e : hipMemcpy(dst.get(), v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
 }
 
+// the plan's slots as the plan-wide functions of scn_slot_life.h take them
+struct SlotLives {
+  SlotLife *life[SCN_NUM_SLOTS];
+};
+inline SlotLives lives_of(scn_plan *p) {
+  SlotLives l;
+  for (int i = 0; i < SCN_NUM_SLOTS; i++) l.life[i] = &p->slot[i].life;
+  return l;
+}
+
 // scn_plan.hip
 int check_slot(scn_plan *p, int slot);
 int ensure_slot_stream(scn_plan *p, Slot &s);
@@ -195,7 +200,7 @@ void set_list_source(A &a, const scn_plan *p, const Slot &s) {
   a.table_count = table ? p->table_count : 0u;
   a.table_first = table ? (uint32_t)g.table_first : 0u;
   a.seq_id = g.seq_given ? s.seq_ids(p->d.max_batch) : nullptr;
-  a.n_buffers = s.n_buffers;
+  a.n_buffers = s.life.n_buffers;
   a.n = p->d.n;
   a.sample_rate = p->d.sample_rate;
 }

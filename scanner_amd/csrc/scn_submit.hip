@@ -32,6 +32,39 @@ hipEvent_t end_event_of(const Slot &s) {
 }
 hipStream_t counts_stream_of(const scn_plan *p, const Slot &s) { return s.route.counts_stream == RouteStream::D2H ? p->d2h_stream.get() : s.stream; }
 
+// Averaged plans: the transform of nb buffers = nb / K groups, one spectrum per group (scn_average.hip)
+int launch_average(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float *d_power, bool hits) {
+  const uint32_t n = p->d.n, ng = nb / p->avg;
+  const int kind = (int)p->d.sample_kind;
+  if (ng) SCN_HIP(s.d_avg_partial.alloc(scn_avg_partial_floats(n, p->d.max_batch / p->avg, p->num_cus)));
+  ScnAvgArgs a;
+  memset(&a, 0, sizeof(a));
+  a.raw = d_raw;
+  a.window = p->d_window.get();
+  a.twiddle = p->d_twiddle.get();
+  a.tw1_table = p->d_tw1_table.get();
+  a.tw1_half = p->d_avg_tw1.get();
+  a.tw_half = reinterpret_cast<const double2_scn *>(p->d_avg_tw.get());
+  a.partial = s.d_avg_partial.get();
+  a.power_db = d_power;
+  a.n = n;
+  a.n_groups = ng;
+  a.k = p->avg;
+  a.parts = scn_avg_parts(n, ng, p->avg, p->num_cus);
+  a.layout = p->avg_layout == SCN_AVG_SWEEPS ? SCN_AVG_L_SWEEPS : SCN_AVG_L_DWELL;
+  a.scale = p->scale;
+  a.threshold = p->d.threshold;
+  a.p_lo = scn_hit_prefilter(p->d.threshold);
+  a.dc_ignore = p->d.dc_ignore_bins;
+  a.i_lo = p->i_lo;
+  a.i_hi = p->i_hi;
+  a.hits = s.cur().d_hits.get();
+  a.hit_region = p->hit_region;
+  a.per_group_hits = s.cur().d_buf_hits.get();
+  SCN_HIP(scn_launch_average(kind, p->d.correct_dc != 0 && kind != SCN_KIND_FLOAT_COMPLEX, hits, d_power != nullptr, a, p->num_cus, s.stream));
+  return SCN_OK;
+}
+
 // The transform of a submit on the slot's stream: the only code that knows which launcher and which argument struct a path
 // uses.  From the slot's route: where a fused kernel stores the counts as well (host_hits, or nullptr), and the event a fused
 // kernel's own dispatch packet completes (stop, or nullptr)
@@ -46,36 +79,7 @@ int launch_transform(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, float
   const int kind = (int)p->d.sample_kind;
   // (a floor or baseline plan's transform reports the spectrum only: its hits come from the detect kernel behind it, launch_floor / launch_baseline)
   const bool hits = (p->d.flags & SCN_OUT_HITS) != 0 && !detects_behind(p), dc = p->d.correct_dc != 0;
-  if (p->avg > 1u) {  // nb buffers = nb / K groups (scn_average.hip)
-    const uint32_t ng = nb / p->avg;
-    if (ng) SCN_HIP(s.d_avg_partial.alloc(scn_avg_partial_floats(n, p->d.max_batch / p->avg, p->num_cus)));
-    ScnAvgArgs a;
-    memset(&a, 0, sizeof(a));
-    a.raw = d_raw;
-    a.window = p->d_window.get();
-    a.twiddle = p->d_twiddle.get();
-    a.tw1_table = p->d_tw1_table.get();
-    a.tw1_half = p->d_avg_tw1.get();
-    a.tw_half = reinterpret_cast<const double2_scn *>(p->d_avg_tw.get());
-    a.partial = s.d_avg_partial.get();
-    a.power_db = d_power;
-    a.n = n;
-    a.n_groups = ng;
-    a.k = p->avg;
-    a.parts = scn_avg_parts(n, ng, p->avg, p->num_cus);
-    a.layout = p->avg_layout == SCN_AVG_SWEEPS ? SCN_AVG_L_SWEEPS : SCN_AVG_L_DWELL;
-    a.scale = p->scale;
-    a.threshold = p->d.threshold;
-    a.p_lo = scn_hit_prefilter(p->d.threshold);
-    a.dc_ignore = p->d.dc_ignore_bins;
-    a.i_lo = p->i_lo;
-    a.i_hi = p->i_hi;
-    a.hits = s.cur().d_hits.get();
-    a.hit_region = p->hit_region;
-    a.per_group_hits = s.cur().d_buf_hits.get();
-    SCN_HIP(scn_launch_average(kind, dc && kind != SCN_KIND_FLOAT_COMPLEX, hits, d_power != nullptr, a, p->num_cus, s.stream));
-    return SCN_OK;
-  }
+  if (p->avg > 1u) return launch_average(p, s, d_raw, nb, d_power, hits);
   switch (p->path) {
     case Path::FusedPow2:
     case Path::FusedMixed: {
@@ -179,6 +183,92 @@ int launch_baseline(scn_plan *p, Slot &s, const float *d_power, uint32_t nu, uin
   return SCN_OK;
 }
 
+// Time-domain plans: one kernel, `done` behind it
+int submit_time_domain(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb) {
+  s.cur_power = nullptr;
+  ScnTdArgs a;
+  a.raw = d_raw;
+  a.n = p->d.n;
+  a.n_buffers = nb;
+  a.scale = p->scale;
+  a.max_db = s.h_td.get();
+  a.min_db = s.h_td.get() + p->d.max_batch;
+  SCN_HIP(scn_launch_time_domain((int)p->d.sample_kind, p->d.correct_dc != 0, a, p->num_cus, s.stream));
+  SCN_HIP(hipEventRecord(s.done.get(), s.stream));
+  on_submitted(s.life);
+  return SCN_OK;
+}
+
+// Where the transform stores the spectrum: the caller's buffer, the plan's for a caller that collects it, a buffer the caller never
+// sees for a hits-only floor or baseline plan (the same spectrum-only transform), or nowhere
+int spectrum_destination(scn_plan *p, Slot &s, uint32_t nb, float **d_power) {
+  const size_t count = (size_t)p->d.n * p->d.max_batch;
+  if (!*d_power && (p->d.flags & SCN_OUT_SPECTRUM)) {
+    SCN_HIP(s.d_power.alloc(count));
+    *d_power = s.d_power.get();
+  }
+  s.cur_power = *d_power;  // (what the caller may collect)
+  if (detects_behind(p) && !*d_power && nb) {
+    SCN_HIP(s.d_detect_power.alloc(count));
+    *d_power = s.d_detect_power.get();
+  }
+  return SCN_OK;
+}
+
+// Baseline plans: what scn_plan_update_baseline folds in once this submit is collected
+void note_baseline_source(const scn_plan *p, Slot &s, const float *d_power, uint32_t nb, uint32_t table_first) {
+  if (!p->baseline) return;
+  s.base_power = d_power;
+  s.base_units = nb;
+  s.base_first = table_first;
+}
+
+// A submit with hits takes the slot's other generation and leaves its header fields where the compaction kernel reads them
+int stage_headers(scn_plan *p, Slot &s, uint32_t nb, const double *fc, const uint64_t *seq, uint32_t table_first) {
+  // this submit's generation; the only thing that can still be using it is the list (compaction + copy) of the submit TWO
+  // submits back ON THIS SLOT -- 2 x (slots in use) launches back on the plan -- wait for it on the host, where it never
+  // blocks in practice
+  // -- and the list of the submit before this one on this slot, whose compaction output (d_list) and pinned copy (h_list)
+  // exist once per slot: its prefetch DMA rides the D2H stream, which nothing on the list stream is ordered behind, so the
+  // next compaction must not start while it may still be reading d_list (a caller that collected counts only has not
+  // waited for it).  Both waits are host-side queries of events that completed long ago in any steady loop.
+  s.gen ^= 1u;
+  for (const SlotGen &g : s.gen_state)
+    if (g.list_used && hipEventQuery(g.list_done.get()) != hipSuccess) SCN_HIP(hipEventSynchronize(g.list_done.get()));
+  // the header fields: read by the compaction kernel in place, over PCIe (two 8-byte reads per buffer that has hits;
+  // staging copies cost ~7 us each plus ~10 us of cross-engine hand-off, on the list's critical path)
+  // the centres: copied when given; a submit that names a range of the plan's device-resident table writes none (the other
+  // 8 header bytes per buffer: 2 MB per launch of 262144 128-point buffers, written and then read back over PCIe)
+  s.cur().table_first = fc ? -1 : (int64_t)table_first;
+  if (fc) memcpy(s.centres(p->d.max_batch), fc, sizeof(double) * nb);
+  // sequence ids: copied when given; otherwise a buffer's id is its index and the compaction kernel computes it -- 8 of the
+  // 16 header bytes per buffer that made the 16 .. 128-point steps host-bound (524288 buffers per launch: 4 MB less to write)
+  s.cur().seq_given = seq != nullptr;
+  if (seq) memcpy(s.seq_ids(p->d.max_batch), seq, sizeof(uint64_t) * nb);
+  return SCN_OK;
+}
+
+// What follows the submit's last compute kernel: the slot's route (submit_route, scn_host.hip), executed
+int queue_behind_transform(scn_plan *p, Slot &s, uint32_t nb) {
+  const SubmitRoute &r = s.route;
+  const hipEvent_t end = end_event_of(s);
+  const hipStream_t cnt = counts_stream_of(p, s);
+  if (end && !r.end_in_packet) SCN_HIP(hipEventRecord(end, s.stream));
+  if (cnt != s.stream) SCN_HIP(hipStreamWaitEvent(cnt, end, 0));
+  if (r.list_forks) SCN_HIP(hipStreamWaitEvent(p->list_stream.get(), end, 0));
+  if (r.counts == Counts::Reduced)
+    SCN_HIP(scn_launch_hit_total(s.cur().d_buf_hits.get(), nb, p->d.trigger_count, s.d_total_acc.get(), s.h_total, s.h_buf_hits.get(), cnt));
+  if (r.counts == Counts::Dma)
+    SCN_HIP(hipMemcpyAsync(s.h_buf_hits.get(), s.cur().d_buf_hits.get(), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, cnt));
+  // (the way the counts go; a windowed submit has no per-unit floor)
+  if (p->floor && r.counts != Counts::None && !s.life.floor_windowed)
+    SCN_HIP(hipMemcpyAsync(s.h_floor.get(), s.d_floor.get(), sizeof(float) * nb, hipMemcpyDeviceToHost, cnt));
+  if (r.done_behind_counts) SCN_HIP(hipEventRecord(s.done.get(), cnt));
+  if (r.list_behind)  // (the prefetch to pinned memory only for a caller that reads the records on the host)
+    return build_list(p, s, p->records_wanted);
+  return SCN_OK;
+}
+
 // fc == nullptr: the buffers carry entries table_first, table_first + 1, ... (wrapping) of the plan's frequency table
 int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const double *fc, const uint64_t *seq,
                   float *d_power, uint32_t table_first = 0) {
@@ -188,91 +278,25 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
   std::vector<double> group_fc;
   std::vector<uint64_t> group_seq;
   if (p->avg > 1u) nb = group_headers(p->avg, p->avg_layout == SCN_AVG_SWEEPS, nb, fc, seq, group_fc, group_seq);
-  const bool will_flip = p->d.mode != SCN_MODE_TIME_DOMAIN && (p->d.flags & SCN_OUT_HITS) != 0 && nb != 0;
-  int st = ensure_slot_outputs(p, s, will_flip ? s.gen ^ 1u : s.gen);
-  if (st) return st;
-  const uint32_t n = p->d.n;
-  if (p->d.mode == SCN_MODE_TIME_DOMAIN) {
-    s.cur_power = nullptr;
-    s.n_buffers = nb;
-    ScnTdArgs a;
-    a.raw = d_raw;
-    a.n = n;
-    a.n_buffers = nb;
-    a.scale = p->scale;
-    a.max_db = s.h_td.get();
-    a.min_db = s.h_td.get() + p->d.max_batch;
-    SCN_HIP(scn_launch_time_domain((int)p->d.sample_kind, p->d.correct_dc != 0, a, p->num_cus, s.stream));
-    SCN_HIP(hipEventRecord(s.done.get(), s.stream));
-    s.pending = true;
-    return SCN_OK;
-  }
-  if (!d_power && (p->d.flags & SCN_OUT_SPECTRUM)) {
-    SCN_HIP(s.d_power.alloc((size_t)n * p->d.max_batch));
-    d_power = s.d_power.get();
-  }
-  s.cur_power = d_power;  // (what the caller may collect)
-  if (detects_behind(p) && !d_power && nb) {  // a hits-only floor or baseline plan: the same spectrum-only transform, into a buffer the caller never sees
-    SCN_HIP(s.d_detect_power.alloc((size_t)n * p->d.max_batch));
-    d_power = s.d_detect_power.get();
-  }
-  if (p->baseline) {  // (what scn_plan_update_baseline folds in once this submit is collected)
-    s.base_power = d_power;
-    s.base_units = nb;
-    s.base_first = table_first;
-    s.base_submitted = true;
-  }
-  s.n_buffers = nb;
-  s.floor_windowed = p->floor && p->floor_train != 0u;
-  s.list_valid = false;
   const bool hits = (p->d.flags & SCN_OUT_HITS) != 0;
-  s.list_built = false;
-  if (hits && nb) {
-    // this submit's generation; the only thing that can still be using it is the list (compaction + copy) of the submit TWO
-    // submits back ON THIS SLOT -- 2 x (slots in use) launches back on the plan -- wait for it on the host, where it never
-    // blocks in practice
-    // -- and the list of the submit before this one on this slot, whose compaction output (d_list) and pinned copy (h_list)
-    // exist once per slot: its prefetch DMA rides the D2H stream, which nothing on the list stream is ordered behind, so the
-    // next compaction must not start while it may still be reading d_list (a caller that collected counts only has not
-    // waited for it).  Both waits are host-side queries of events that completed long ago in any steady loop.
-    s.gen ^= 1u;
-    for (const SlotGen &g : s.gen_state)
-      if (g.list_used && hipEventQuery(g.list_done.get()) != hipSuccess) SCN_HIP(hipEventSynchronize(g.list_done.get()));
-    // the header fields: read by the compaction kernel in place, over PCIe (two 8-byte reads per buffer that has hits;
-    // staging copies cost ~7 us each plus ~10 us of cross-engine hand-off, on the list's critical path)
-    // the centres: copied when given; a submit that names a range of the plan's device-resident table writes none (the other
-    // 8 header bytes per buffer: 2 MB per launch of 262144 128-point buffers, written and then read back over PCIe)
-    s.cur().table_first = fc ? -1 : (int64_t)table_first;
-    if (fc) memcpy(s.centres(p->d.max_batch), fc, sizeof(double) * nb);
-    // sequence ids: copied when given; otherwise a buffer's id is its index and the compaction kernel computes it -- 8 of the
-    // 16 header bytes per buffer that made the 16 .. 128-point steps host-bound (524288 buffers per launch: 4 MB less to write)
-    s.cur().seq_given = seq != nullptr;
-    if (seq) memcpy(s.seq_ids(p->d.max_batch), seq, sizeof(uint64_t) * nb);
+  const SubmitFacts facts = {nb, hits, p->floor && p->floor_train != 0u, p->baseline, p->d.mode == SCN_MODE_TIME_DOMAIN};
+  int st = ensure_slot_outputs(p, s, submit_flips(facts) ? s.gen ^ 1u : s.gen);
+  if (st) return st;
+  if (facts.time_domain) {
+    on_submit(s.life, facts);
+    return submit_time_domain(p, s, d_raw, nb);
   }
-
+  if ((st = spectrum_destination(p, s, nb, &d_power))) return st;
+  note_baseline_source(p, s, d_power, nb, table_first);
+  if (on_submit(s.life, facts) && (st = stage_headers(p, s, nb, fc, seq, table_first))) return st;
   // what follows the transform, decided once (submit_route, scn_host.hip: the table and the measurements behind it)
   const bool fused = (p->path == Path::FusedPow2 || p->path == Path::FusedMixed) && p->avg == 1u && !detects_behind(p);
-  const SubmitRoute r = s.route = submit_route({hits, fused, p->direct_counts, s.own_stream, p->records_wanted || p->device_list_wanted, n, nb});
-  const hipEvent_t end = end_event_of(s);
-  const hipStream_t cnt = counts_stream_of(p, s);
-  st = launch_transform(p, s, d_raw, n_raw, d_power);
-  if (st) return st;
+  s.route = submit_route({hits, fused, p->direct_counts, s.own_stream, p->records_wanted || p->device_list_wanted, p->d.n, nb});
+  if ((st = launch_transform(p, s, d_raw, n_raw, d_power))) return st;
   if (p->floor && nb && (st = launch_floor(p, s, d_power, nb))) return st;
   if (p->baseline && nb && (st = launch_baseline(p, s, d_power, nb, table_first))) return st;
-  if (end && !r.end_in_packet) SCN_HIP(hipEventRecord(end, s.stream));
-  if (cnt != s.stream) SCN_HIP(hipStreamWaitEvent(cnt, end, 0));
-  if (r.list_forks) SCN_HIP(hipStreamWaitEvent(p->list_stream.get(), end, 0));
-  if (r.counts == Counts::Reduced)
-    SCN_HIP(scn_launch_hit_total(s.cur().d_buf_hits.get(), nb, p->d.trigger_count, s.d_total_acc.get(), s.h_total, s.h_buf_hits.get(), cnt));
-  if (r.counts == Counts::Dma)
-    SCN_HIP(hipMemcpyAsync(s.h_buf_hits.get(), s.cur().d_buf_hits.get(), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, cnt));
-  // (the way the counts go; a windowed submit has no per-unit floor)
-  if (p->floor && r.counts != Counts::None && !s.floor_windowed)
-    SCN_HIP(hipMemcpyAsync(s.h_floor.get(), s.d_floor.get(), sizeof(float) * nb, hipMemcpyDeviceToHost, cnt));
-  if (r.done_behind_counts) SCN_HIP(hipEventRecord(s.done.get(), cnt));
-  if (r.list_behind)  // (the prefetch to pinned memory only for a caller that reads the records on the host)
-    if ((st = build_list(p, s, p->records_wanted))) return st;
-  s.pending = true;
+  if ((st = queue_behind_transform(p, s, nb))) return st;
+  on_submitted(s.life);
   return SCN_OK;
 }
 
@@ -287,7 +311,7 @@ int begin_submit(scn_plan *p, int slot, uint32_t nb, const double *fc, bool null
     if (int st = check_average(p->avg, p->avg_layout == SCN_AVG_SWEEPS, nb, fc)) return st;
   if (p->baseline)
     if (int st = check_baseline_submit(p->baseline_rows, indexed, p->table_count)) return st;
-  if (s.pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit", slot);
+  if (int st = require_free(s.life, slot)) return st;
   if (host && !s.h_raw) return scn_fail(SCN_E_STATE, "slot %d: scn_host_buffer was never called", slot);
   SCN_HIP(hipSetDevice(p->d.device_id));
   return ensure_slot_stream(p, s);
@@ -353,8 +377,8 @@ int scn_submit_device_indexed(scn_plan *p, int slot, const void *d_raw, uint32_t
 int scn_plan_set_table(scn_plan *p, const double *fc, uint32_t count) {
   if (!p) return scn_fail(SCN_E_INVALID, "null plan");
   if (count && !fc) return scn_fail(SCN_E_INVALID, "center_freqs is null");
-  for (int i = 0; i < SCN_NUM_SLOTS; i++)
-    if (p->slot[i].pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit: its records still read the table", i);
+  const SlotLives lives = lives_of(p);
+  if (int st = require_none_pending(lives.life, SCN_NUM_SLOTS, ": its records still read the table")) return st;
   SCN_HIP(hipSetDevice(p->d.device_id));
   // (a list of an already collected submit may still be being completed -- the prefetch of scn_collect, scn_collect_more --
   // from the OLD table: wait for what THIS plan has queued on the streams that read the table, then forget those lists.  Not a
@@ -364,7 +388,7 @@ int scn_plan_set_table(scn_plan *p, const double *fc, uint32_t count) {
   SCN_HIP(hipStreamSynchronize(p->h2d_stream.get()));
   for (int i = 0; i < SCN_NUM_SLOTS; i++)  // (a slot with a stream of its own builds its list there)
     if (p->slot[i].own_stream && p->slot[i].stream) SCN_HIP(hipStreamSynchronize(p->slot[i].stream));
-  for (int i = 0; i < SCN_NUM_SLOTS; i++) p->slot[i].list_valid = false;
+  on_table_change(lives.life, SCN_NUM_SLOTS);
   p->table_count = 0;
   if (!count) return SCN_OK;
   if (count > p->d_table.capacity()) SCN_HIP(p->d_table.grow(count));  // (a caller that re-tables between sweeps keeps its allocation)
@@ -377,8 +401,7 @@ int scn_plan_set_table(scn_plan *p, const double *fc, uint32_t count) {
 int scn_plan_set_floor_window(scn_plan *p, uint32_t train, uint32_t guard) {
   if (!p) return scn_fail(SCN_E_INVALID, "null plan");
   if (!p->floor) return scn_fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_FLOOR");
-  for (int i = 0; i < SCN_NUM_SLOTS; i++)
-    if (p->slot[i].pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit", i);
+  if (int st = require_none_pending(lives_of(p).life, SCN_NUM_SLOTS, "")) return st;
   if (!train && !guard) {  // back to the unit-wide floor (collected slots keep their lists: nothing of theirs reads the table)
     p->floor_train = p->floor_guard = 0;
     return SCN_OK;
@@ -398,8 +421,7 @@ int scn_plan_set_floor_window(scn_plan *p, uint32_t train, uint32_t guard) {
 int scn_plan_set_baseline(scn_plan *p, uint32_t rows, const float *baseline_db) {
   if (!p) return scn_fail(SCN_E_INVALID, "null plan");
   if (!p->baseline) return scn_fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_BASELINE");
-  for (int i = 0; i < SCN_NUM_SLOTS; i++)
-    if (p->slot[i].pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit: its detect kernel may still read the baseline", i);
+  if (int st = require_none_pending(lives_of(p).life, SCN_NUM_SLOTS, ": its detect kernel may still read the baseline")) return st;
   // (no slot is pending, and a slot's detect kernel is complete when its `done` is: nothing reads the old rows any more)
   p->baseline_rows = 0;
   if (!rows) return SCN_OK;  // (the allocation stays for the next one, as the table's)
@@ -416,10 +438,9 @@ int scn_plan_set_baseline(scn_plan *p, uint32_t rows, const float *baseline_db) 
 int scn_plan_update_baseline(scn_plan *p, int slot, uint32_t op) {
   if (int st = check_slot(p, slot)) return st;
   if (!p->baseline) return scn_fail(SCN_E_INVALID, "plan was created without detect = SCN_DETECT_BASELINE");
-  for (int i = 0; i < SCN_NUM_SLOTS; i++)
-    if (p->slot[i].pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit: its detect kernel may still read the baseline", i);
+  if (int st = require_none_pending(lives_of(p).life, SCN_NUM_SLOTS, ": its detect kernel may still read the baseline")) return st;
   const Slot &s = p->slot[slot];
-  if (!s.base_submitted) return scn_fail(SCN_E_STATE, "slot %d has no collected submit to learn from", slot);
+  if (int st = require_learnable(s.life, slot)) return st;
   if (!p->baseline_rows) return scn_fail(SCN_E_STATE, "the plan has no baseline: scn_plan_set_baseline was never called, or dropped it");
   if (int st = check_baseline_update(p->baseline_rows, s.base_units, op)) return st;
   if (!s.base_units) return SCN_OK;

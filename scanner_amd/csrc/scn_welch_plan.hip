@@ -29,7 +29,7 @@ struct WelchSlot {
   WelchWork work;                  // ... which needs a work set of its own
   uint32_t graph_npsd = 0;
   ScnEvent done;
-  bool pending = false;
+  SlotLife life;                   // (of which a Welch slot has `pending` alone)
   uint32_t n_psd = 0;
 };
 }  // namespace
@@ -166,7 +166,7 @@ int scn_welch_submit(scn_welch *w, int slot, uint32_t n_psd) {
   if (int st = welch_check(w, slot)) return st;
   WelchSlot &s = w->slot[slot];
   if (n_psd < 1 || n_psd > w->d.max_psd) return scn_fail(SCN_E_INVALID, "n_psd %u out of range (1..%u)", n_psd, w->d.max_psd);
-  if (s.pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit", slot);
+  if (int st = require_free(s.life, slot)) return st;
   if (!s.h_in) return scn_fail(SCN_E_STATE, "slot %d: scn_welch_host_buffer was never called", slot);
   SCN_HIP(hipSetDevice(w->d.device_id));
   const size_t in_bytes = welch_samples(w, w->d.max_psd) * w->bytes_per_sample, psd_floats = (size_t)w->d.n * w->d.max_psd;
@@ -203,7 +203,7 @@ int scn_welch_submit(scn_welch *w, int slot, uint32_t n_psd) {
   }
   SCN_HIP(hipGraphLaunch(s.graph, stream));
   SCN_HIP(hipEventRecord(s.done.get(), stream));
-  s.pending = true;
+  on_submitted(s.life);
   s.via_graph = true;
   s.n_psd = n_psd;
   s.cur_psd = s.d_psd.get();
@@ -216,7 +216,7 @@ int scn_welch_submit_device(scn_welch *w, int slot, const void *d_samples, uint3
   WelchSlot &s = w->slot[slot];
   if (n_psd < 1 || n_psd > w->d.max_psd) return scn_fail(SCN_E_INVALID, "n_psd %u out of range (1..%u)", n_psd, w->d.max_psd);
   if (!d_samples) return scn_fail(SCN_E_INVALID, "null argument");
-  if (s.pending) return scn_fail(SCN_E_STATE, "slot %d has an uncollected submit", slot);
+  if (int st = require_free(s.life, slot)) return st;
   SCN_HIP(hipSetDevice(w->d.device_id));
   if (!d_psd_db) {
     SCN_HIP(s.d_psd.alloc((size_t)w->d.n * w->d.max_psd));
@@ -226,7 +226,7 @@ int scn_welch_submit_device(scn_welch *w, int slot, const void *d_samples, uint3
   st = welch_enqueue(w, d_samples, n_psd, d_psd_db, w->stream.get(), w->work);
   if (st) return st;
   SCN_HIP(hipEventRecord(s.done.get(), w->stream.get()));
-  s.pending = true;
+  on_submitted(s.life);
   s.via_graph = false;
   s.n_psd = n_psd;
   s.cur_psd = d_psd_db;
@@ -236,10 +236,10 @@ int scn_welch_submit_device(scn_welch *w, int slot, const void *d_samples, uint3
 int scn_welch_collect(scn_welch *w, int slot, float *psd_db) {
   if (int st = welch_check(w, slot)) return st;
   WelchSlot &s = w->slot[slot];
-  if (!s.pending) return scn_fail(SCN_E_STATE, "slot %d has nothing submitted", slot);
+  if (int st = require_pending(s.life, slot)) return st;
   SCN_HIP(hipSetDevice(w->d.device_id));
   SCN_HIP(hipEventSynchronize(s.done.get()));
-  s.pending = false;
+  on_take(s.life);
   if (psd_db) {
     const size_t bytes = sizeof(float) * (size_t)w->d.n * s.n_psd;
     if (s.via_graph) {
