@@ -48,7 +48,9 @@ extern "C" {
                              still 6 (additions only): the baseline detector -- SCN_DETECT_BASELINE, SCN_BASELINE_*,
                              scn_plan_set_baseline, scn_plan_update_baseline, scn_plan_get_baseline;
                              still 6 (additions only): the hit history -- scn_plan_set_history, scn_plan_update_history,
-                             scn_plan_get_history, scn_collect_confirmed, scn_history_fold_hits, scn_confirm_hits */
+                             scn_plan_get_history, scn_collect_confirmed, scn_history_fold_hits, scn_confirm_hits;
+                             still 6 (additions only): the sweep trace -- SCN_TRACE_CELLS_MAX, scn_plan_set_trace,
+                             scn_plan_update_trace, scn_plan_get_trace, scn_trace_fold_spectrum, scn_trace_init, scn_trace_merge */
 
 /* status codes */
 enum {
@@ -259,6 +261,32 @@ enum {
  * kernel of a submit reads or writes the history: it changes only through scn_plan_set_history and scn_plan_update_history, both
  * allowed while other slots are pending.  A plan on which scn_plan_set_history is never called allocates nothing for it. */
 
+/* Sweep trace (scn_plan_set_trace): the picture of the sweep -- one power-versus-frequency line across the whole table, in absolute
+ * hertz, at a resolution the caller chooses: a panorama, a peak-hold line, a waterfall row.  A plan may own a trace; it has none at
+ * first.  Its geometry is (f0_hz: uint64, cell_hz: uint32 >= 1, cells: 1 ... SCN_TRACE_CELLS_MAX): cell c covers the frequencies
+ * [f0_hz + c * cell_hz, f0_hz + (c + 1) * cell_hz).  Per cell it holds max_db, min_db (float32) and count (uint64), device memory; an
+ * empty cell reads max_db = -inf, min_db = +inf, count = 0.
+ *   Which plans: frequency-domain plans with SCN_OUT_HITS whose submits store a spectrum -- SCN_OUT_SPECTRUM is set, or detect is
+ *     SCN_DETECT_FLOOR or SCN_DETECT_BASELINE (those keep the spectrum their detect kernel reads) --; every size scn_size_path supports,
+ *     and averaged plans (the unit is the group).  Anything else is SCN_E_INVALID from scn_plan_set_trace: a time-domain plan, a plan
+ *     without SCN_OUT_HITS, a fixed-threshold hits-only plan (no spectrum exists anywhere).  SCN_OUT_HITS is required because only such
+ *     submits stage their centre frequencies where a later kernel can read them.
+ *   Fold (scn_plan_update_trace): for every unit u of the slot's last collected submit and every bin the mask of process.cpp:46-52
+ *     lets through (fftshift index i, natural bin j = (i + n / 2) % n):
+ *       f = the freq_hz a hit record of (u, i) would carry, bit for bit: uint64(fc - double(sample_rate / 2) + double(uint32(i *
+ *         bin_step))), bin_step = sample_rate / n truncated, the cast the reference's x86-64 build makes (a negative double becomes
+ *         the two's complement of its magnitude), fc the unit's centre exactly as its records get it: its own center_freqs entry, or
+ *         table entry (first_index + u) % count;
+ *       f < f0_hz: the bin is skipped; otherwise c = (f - f0_hz) / cell_hz in uint64 integer arithmetic, and c >= cells is skipped
+ *         too.  (A negative start frequency wraps to a huge f and is therefore skipped.)
+ *       v = power_db[u][j], read from the spectrum that submit stored.  A NaN is skipped and nothing changes.  Every other value,
+ *         +-inf included, is folded: count[c] += 1, max_db[c] becomes the larger of itself and v, min_db[c] the smaller -- larger and
+ *         smaller in the floor detector's key order, where -0.0 is below +0.0; the stored bits are the winning value's bits.
+ * Maximum, minimum and an integer sum commute, so the trace is exact: the same bits on every run, route, partition and fold order.
+ * No kernel of a submit reads or writes the trace: it changes only through scn_plan_set_trace and scn_plan_update_trace, both
+ * allowed while other slots are pending.  A plan on which scn_plan_set_trace is never called allocates nothing for it. */
+#define SCN_TRACE_CELLS_MAX (1u << 22)
+
 /* Signals (scn_collect_signals, scn_signals_from_hits): runs of nearby hits merged into one record each.  A plan's buffer is
  * its unit of output (for an averaged plan: the group).  The hits of one unit, in increasing i, are split into signals: a hit
  * starts a new signal when it is the unit's first hit or when its i exceeds the previous hit's i by more than max_gap + 1.
@@ -468,6 +496,40 @@ SCN_API int scn_history_fold_hits(uint32_t *history, uint32_t *visits, uint32_t 
 SCN_API int scn_confirm_hits(const uint32_t *history, uint32_t rows, uint32_t n, uint32_t first, uint32_t n_units,
                              const uint64_t *unit_seq_ids, const scn_hit *hits, uint64_t n_hits, uint32_t m, uint32_t window,
                              scn_hit *out, uint64_t cap, uint64_t *n_out);
+
+/* Gives the plan a sweep trace of `cells` cells of cell_hz hertz from f0_hz up ("Sweep trace" above), every cell empty; every call
+ * resets every cell.  cells == 0 drops the trace (the allocation is kept for the next one).  Allowed at any time, pending slots or
+ * not: nothing asynchronous ever touches the trace.  A plan that cannot have one (above), cell_hz == 0 with cells != 0, or cells >
+ * SCN_TRACE_CELLS_MAX: SCN_E_INVALID, nothing changed. */
+SCN_API int scn_plan_set_trace(scn_plan *plan, uint64_t f0_hz, uint32_t cell_hz, uint32_t cells);
+
+/* Folds the spectrum of the slot's last COLLECTED submit into the trace, on the GPU, and returns when that is complete.  Refused
+ * before anything is queued: a pending slot, or one without a collected submit whose list is still on the device -- after the slot's
+ * next submit or a scn_plan_set_table the centres are gone -- (SCN_E_STATE); a plan without a trace (SCN_E_STATE).  OTHER slots may
+ * be pending.  A submit that wrote its spectrum into the caller's d_power_db is read from there: the caller keeps that memory intact
+ * until this call has returned (the baseline's rule).  A submit of zero units is SCN_OK and folds nothing.  Folding the same slot
+ * twice is allowed: it counts twice and leaves max_db and min_db as they are. */
+SCN_API int scn_plan_update_trace(scn_plan *plan, int slot);
+
+/* Copies cells [first_cell, first_cell + cells) of the trace to host memory; any of the three pointers may be NULL.  A range outside
+ * the trace is SCN_E_INVALID. */
+SCN_API int scn_plan_get_trace(scn_plan *plan, uint32_t first_cell, uint32_t cells, float *max_db, float *min_db, uint64_t *count);
+
+/* The same fold on host memory: the definition the GPU form is held to (the same bits), and what a caller without the plan at hand
+ * folds a collected spectrum with.  Needs no device.  max_db, min_db and count (`cells` entries each) are read and written:
+ * scn_trace_init makes the empty trace, and calls accumulate.  power_db: n_units spectra of n floats, natural bin order;
+ * center_freqs: one per unit; dc_ignore_bins and use_bandwidth with the descriptor's zero defaults.  A null array (power_db and
+ * center_freqs: with n_units != 0), cell_hz == 0, cells outside 1 ... SCN_TRACE_CELLS_MAX, n == 0 or above 2^24, sample_rate == 0:
+ * SCN_E_INVALID, nothing changed. */
+SCN_API int scn_trace_fold_spectrum(float *max_db, float *min_db, uint64_t *count, uint64_t f0_hz, uint32_t cell_hz, uint32_t cells,
+                                    const float *power_db, uint32_t n_units, uint32_t n, uint32_t sample_rate, uint32_t dc_ignore_bins,
+                                    double use_bandwidth, const double *center_freqs);
+/* The empty trace: max_db = -inf, min_db = +inf, count = 0 in every cell (same limits on cells, no null array). */
+SCN_API int scn_trace_init(float *max_db, float *min_db, uint64_t *count, uint32_t cells);
+/* Cell by cell: count += src_count, max_db = the larger of the two, min_db = the smaller, in the same key order -- how the root of a
+ * sharded sweep joins the ranks' traces of one geometry; merge(A, B) is the trace of everything folded into A or B. */
+SCN_API int scn_trace_merge(float *max_db, float *min_db, uint64_t *count, const float *src_max, const float *src_min,
+                            const uint64_t *src_count, uint32_t cells);
 
 /* Time-domain plans (mode = SCN_MODE_TIME_DOMAIN; ProcessSamples::DoTimeDomainThresholding,
  * process.cpp:203-237): wait for the slot's submit and fetch, per buffer, the maximum and

@@ -27,6 +27,7 @@ DETECT_FIXED, DETECT_FLOOR, DETECT_BASELINE = 0, 1, 2  # scn_plan_desc.detect
 BASELINE_SET, BASELINE_MAX = 0, 1  # scn_plan_update_baseline's op
 FLOOR_MIN = 0xFFFFFFFF  # scn_plan_desc.floor_permille: rank 0 (0 itself asks for the default, the median)
 FLOOR_TRAIN_MAX, FLOOR_GUARD_MAX = 128, 64  # the floor window's limits (scn_plan_set_floor_window)
+TRACE_CELLS_MAX = 1 << 22  # the most cells a sweep trace has (scn_plan_set_trace)
 PATH_UNSUPPORTED, PATH_FUSED, PATH_FOUR_STEP, PATH_STAGED, PATH_BLUESTEIN = range(5)
 COMM_ID_BYTES = 128
 GATHER_TICKETS = 4
@@ -122,6 +123,13 @@ SYMBOLS = {
     "scn_history_fold_hits": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64]),
     "scn_confirm_hits": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32,
                                    _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "scn_plan_set_trace": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "scn_plan_update_trace": (C.c_int, [_vp, C.c_int]),
+    "scn_plan_get_trace": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "scn_trace_fold_spectrum": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.c_double, _vp]),
+    "scn_trace_init": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
+    "scn_trace_merge": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
     "scn_collect_time_domain": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "scn_convert_raw": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "scn_wait": (C.c_int, [_vp, C.c_int]),
@@ -270,6 +278,45 @@ def confirm_hits(history, hits, n_units, m, window, first=0, unit_seq_ids=None):
                                  hits.ctypes.data_as(_vp), hits.size, int(m), int(window), out.ctypes.data_as(_vp), out.size, C.byref(total)),
           "scn_confirm_hits")
     return out[: total.value]
+
+
+def _trace_arrays(max_db, min_db, count):
+    for a, dt in ((max_db, np.float32), (min_db, np.float32), (count, np.uint64)):
+        assert a.dtype == dt and a.ndim == 1 and a.flags.c_contiguous and a.flags.writeable and a.size == max_db.size
+    return max_db.ctypes.data_as(_vp), min_db.ctypes.data_as(_vp), count.ctypes.data_as(_vp)
+
+
+def trace_init(cells):
+    """scn_trace_init: the empty trace of `cells` cells -- (max_db float32 all -inf, min_db float32 all +inf, count uint64 all 0).
+    Needs no device."""
+    max_db, min_db, count = np.empty(cells, np.float32), np.empty(cells, np.float32), np.empty(cells, np.uint64)
+    check(lib().scn_trace_init(*_trace_arrays(max_db, min_db, count), int(cells)), "scn_trace_init")
+    return max_db, min_db, count
+
+
+def trace_fold_spectrum(trace, f0_hz, cell_hz, power_db, sample_rate, center_freqs, dc_ignore_bins=4, use_bandwidth=0.75):
+    """scn_trace_fold_spectrum: the spectra power_db (float32 [units, n], natural bin order) of units centred at center_freqs folded
+    IN PLACE into trace = (max_db, min_db, count) on the grid (f0_hz, cell_hz, len(max_db)) -- what Plan.update_trace does on the
+    GPU, to the bit (scanner_hip.h, "Sweep trace").  Needs no device."""
+    max_db, min_db, count = trace
+    power_db = np.ascontiguousarray(power_db, np.float32)
+    assert power_db.ndim == 2
+    fc = np.ascontiguousarray(center_freqs, np.float64).reshape(-1)
+    assert fc.size == power_db.shape[0], f"{fc.size} centres for {power_db.shape[0]} units"
+    check(lib().scn_trace_fold_spectrum(*_trace_arrays(max_db, min_db, count), int(f0_hz), int(cell_hz), max_db.size, power_db.ctypes.data_as(_vp),
+                                        power_db.shape[0], power_db.shape[1], int(sample_rate),
+                                        DC_IGNORE_NONE if dc_ignore_bins == 0 else int(dc_ignore_bins), float(use_bandwidth), fc.ctypes.data_as(_vp)),
+          "scn_trace_fold_spectrum")
+
+
+def trace_merge(trace, src):
+    """scn_trace_merge: the trace src = (max_db, min_db, count) joined IN PLACE into trace, cell by cell -- the counts added, the
+    larger maximum and the smaller minimum kept: how the root of a sharded sweep joins the ranks' traces.  Needs no device."""
+    max_db, min_db, count = trace
+    src_max, src_min, src_count = (np.ascontiguousarray(a, dt) for a, dt in zip(src, (np.float32, np.float32, np.uint64)))
+    assert src_max.size == src_min.size == src_count.size == max_db.size
+    check(lib().scn_trace_merge(*_trace_arrays(max_db, min_db, count), src_max.ctypes.data_as(_vp), src_min.ctypes.data_as(_vp),
+                                src_count.ctypes.data_as(_vp), max_db.size), "scn_trace_merge")
 
 
 def floor_from_spectrum(power_db, dc_ignore_bins=4, use_bandwidth=0.75, floor_permille=0):

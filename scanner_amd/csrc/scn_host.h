@@ -97,6 +97,12 @@ int check_history_fold(uint32_t rows, uint32_t units, bool indexed, uint32_t tab
 int check_history_window(uint32_t m, uint32_t window);
 int check_history_range(uint32_t have, uint32_t first_row, uint32_t rows);
 
+// The sweep trace (scanner_hip.h, "Sweep trace"): a geometry's limits and a read-out's range, from numbers alone -- shared by the
+// plan's entry points (scn_trace_plan.hip) and the host forms (scn_trace_fold_spectrum, scn_trace_init, scn_trace_merge).  The
+// arithmetic of a fold is scn_trace.h's, the kernel's own.
+int check_trace_geometry(uint32_t cell_hz, uint32_t cells);
+int check_trace_range(uint32_t have, uint32_t first_cell, uint32_t cells);
+
 // Averaged plans (k = average > 1; sweeps: SCN_AVG_SWEEPS, else SCN_AVG_DWELL).  group_headers redirects fc / seq to the groups'
 // (held in group_fc / group_seq) where the submit gave them or the compaction kernel's default would be wrong; returns the groups
 int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc);

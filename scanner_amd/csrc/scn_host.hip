@@ -3,6 +3,7 @@
 // test_plan_resolve.cpp build the unit with g++ under the sanitizers); the .hip suffix only puts it through the library's compiler.
 #include "scn_host.h"
 
+#include "scn_trace.h"
 #include "scn_wire.h"
 
 #include <algorithm>
@@ -344,7 +345,30 @@ int check_history_range(uint32_t have, uint32_t first_row, uint32_t rows) {
   return SCN_OK;
 }
 
+int check_trace_geometry(uint32_t cell_hz, uint32_t cells) {
+  if (cell_hz == 0) return scn_fail(SCN_E_INVALID, "a trace cell is at least 1 Hz wide");
+  if (cells == 0 || cells > SCN_TRACE_CELLS_MAX) return scn_fail(SCN_E_INVALID, "a trace has 1 ... %u cells: %u", SCN_TRACE_CELLS_MAX, cells);
+  return SCN_OK;
+}
+
+int check_trace_range(uint32_t have, uint32_t first_cell, uint32_t cells) {
+  if ((uint64_t)first_cell + cells > have) return scn_fail(SCN_E_INVALID, "cells [%u, %u + %u) outside the trace of %u cells", first_cell, first_cell, cells, have);
+  return SCN_OK;
+}
+
 namespace {
+
+// One cell's hold: *max_db becomes the larger of itself and hi, *min_db the smaller of itself and lo, in the key order of
+// scn_trace.h; the winning value's bits are stored as they are
+void trace_hold(float *max_db, float *min_db, float hi, float lo) {
+  uint32_t cur_max, cur_min, bits_hi, bits_lo;
+  memcpy(&cur_max, max_db, sizeof(cur_max));
+  memcpy(&cur_min, min_db, sizeof(cur_min));
+  memcpy(&bits_hi, &hi, sizeof(bits_hi));
+  memcpy(&bits_lo, &lo, sizeof(bits_lo));
+  if (scn_trace_key(bits_hi) > scn_trace_key(cur_max)) memcpy(max_db, &bits_hi, sizeof(bits_hi));
+  if (scn_trace_key(bits_lo) < scn_trace_key(cur_min)) memcpy(min_db, &bits_lo, sizeof(bits_lo));
+}
 
 // An ordered host hit list, unit by unit: unit u owns the maximal run of records at the cursor whose seq_id is the unit's
 // (unit_seq_ids[u], or u); each(row of the unit, record) for every record.  A record with i >= n, and records left over behind the
@@ -546,6 +570,58 @@ int scn_confirm_hits(const uint32_t *history, uint32_t rows, uint32_t n, uint32_
   if (st) return st;
   *n_out = total;
   if (total > cap) return scn_fail(SCN_E_TRUNCATED, "%llu confirmed records, the first %llu returned", (unsigned long long)total, (unsigned long long)cap);
+  return SCN_OK;
+}
+
+int scn_trace_init(float *max_db, float *min_db, uint64_t *count, uint32_t cells) {
+  if (!max_db || !min_db || !count) return scn_fail(SCN_E_INVALID, "null argument");
+  if (int st = check_trace_geometry(1u, cells)) return st;
+  const uint32_t below = scn_trace_unkey(kTraceEmptyMaxKey), above = scn_trace_unkey(kTraceEmptyMinKey);  // -inf, +inf
+  for (uint32_t c = 0; c < cells; c++) {
+    memcpy(max_db + c, &below, sizeof(below));
+    memcpy(min_db + c, &above, sizeof(above));
+    count[c] = 0;
+  }
+  return SCN_OK;
+}
+
+int scn_trace_merge(float *max_db, float *min_db, uint64_t *count, const float *src_max, const float *src_min, const uint64_t *src_count,
+                    uint32_t cells) {
+  if (!max_db || !min_db || !count || !src_max || !src_min || !src_count) return scn_fail(SCN_E_INVALID, "null argument");
+  if (int st = check_trace_geometry(1u, cells)) return st;
+  for (uint32_t c = 0; c < cells; c++) {
+    trace_hold(max_db + c, min_db + c, src_max[c], src_min[c]);
+    count[c] += src_count[c];
+  }
+  return SCN_OK;
+}
+
+int scn_trace_fold_spectrum(float *max_db, float *min_db, uint64_t *count, uint64_t f0_hz, uint32_t cell_hz, uint32_t cells, const float *power_db,
+                            uint32_t n_units, uint32_t n, uint32_t sample_rate, uint32_t dc_ignore_bins, double use_bandwidth,
+                            const double *center_freqs) {
+  if (!max_db || !min_db || !count || (n_units && (!power_db || !center_freqs))) return scn_fail(SCN_E_INVALID, "null argument");
+  if (int st = check_trace_geometry(cell_hz, cells)) return st;
+  if (n == 0 || n > (1u << 24)) return scn_fail(SCN_E_INVALID, "bad bin count %u", n);
+  if (sample_rate == 0) return scn_fail(SCN_E_INVALID, "sample_rate must be > 0");
+  struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {dc_ignore_bins ? dc_ignore_bins : 4u, 0, 0};  // the descriptor's defaults (scn_plan_create)
+  if (mask.dc_ignore == SCN_DC_IGNORE_NONE) mask.dc_ignore = 0;
+  evaluated_bins(n, mask.dc_ignore, use_bandwidth == 0.0 ? 0.75 : use_bandwidth, &mask.i_lo, &mask.i_hi);
+  const uint32_t bin_step = sample_rate / n;  // process.cpp:39 (truncating)
+  for (uint32_t u = 0; u < n_units; u++) {
+    const double start_frequency = scn_trace_start(center_freqs[u], sample_rate);
+    const float *const row = power_db + (size_t)u * n;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t j = (i + n / 2) % n;
+      if (!scn_bin_evaluated(j, i, n, mask)) continue;
+      uint32_t bits;
+      memcpy(&bits, row + j, sizeof(bits));
+      if (scn_trace_is_nan(bits)) continue;
+      const uint32_t c = scn_trace_cell(scn_trace_freq(start_frequency, i, bin_step), f0_hz, cell_hz, cells);
+      if (c == kTraceNoCell) continue;
+      trace_hold(max_db + c, min_db + c, row[j], row[j]);
+      count[c]++;
+    }
+  }
   return SCN_OK;
 }
 

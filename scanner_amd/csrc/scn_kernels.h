@@ -166,6 +166,22 @@ struct ScnConfirmArgs {
 };
 hipError_t scn_launch_confirm_count(const ScnConfirmArgs &args, hipStream_t stream);
 hipError_t scn_launch_confirm_build(const ScnConfirmArgs &args, hipStream_t stream);
+// The sweep trace (scn_trace.hip, scanner_hip.h "Sweep trace"): per cell of the plan's frequency grid the largest and the smallest
+// dB value folded into it, as ordered keys (scn_trace.h), and their number.  The fold launch reads the spectrum a collected submit
+// stored and its centres where the submit left them, and changes the three arrays with atomics only: any number of units may name
+// the same cell.
+struct ScnTraceArgs {
+  const float *power_db;       // [n_units][n], natural bin order
+  const double *center_freq;   // as ScnCompactArgs: the submit's own [n_units], or the plan's table
+  uint32_t table_count, table_first;
+  uint32_t n, n_units, sample_rate;
+  uint32_t dc_ignore, i_lo, i_hi;
+  uint64_t f0_hz;              // the grid: cell c covers [f0_hz + c cell_hz, f0_hz + (c + 1) cell_hz)
+  uint32_t cell_hz, cells;     // cell_hz >= 1, 1 <= cells <= SCN_TRACE_CELLS_MAX
+  uint32_t *max_key, *min_key; // [cells] scn_trace_key of max_db / min_db (empty: kTraceEmptyMaxKey / kTraceEmptyMinKey)
+  unsigned long long *count;   // [cells]
+};
+hipError_t scn_launch_trace_fold(const ScnTraceArgs &args, int num_cus, hipStream_t stream);
 // sum of counts[0, n_buffers) -> *host_total (pinned host memory); acc: two zeroed device words the kernel leaves zeroed
 hipError_t scn_launch_hit_total(const uint32_t *counts, uint32_t n_buffers, uint32_t trigger_count, unsigned long long *acc, unsigned long long *host_total,
                                 uint32_t *trigger_bits, hipStream_t stream);

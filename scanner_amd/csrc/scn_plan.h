@@ -3,7 +3,8 @@
 // never touch HIP -- a descriptor's defaults, checks and everything derived from it (resolve_plan, resolve_welch) and the contents of
 // the tables; scn_plan.hip: the device side of create (streams, uploads), first-use allocation, destroy, getters;
 // scn_slot_life.h: what a slot may do next -- every precondition and every transition of its life cycle (no HIP header);
-// scn_submit.hip / scn_collect.hip: the two sides of a slot; scn_history_plan.hip: the hit history; scn_welch_plan.hip: the Welch plan.
+// scn_submit.hip / scn_collect.hip: the two sides of a slot; scn_history_plan.hip: the hit history; scn_trace_plan.hip: the sweep trace;
+// scn_welch_plan.hip: the Welch plan.
 //
 // A plan owns: one HIP stream, the window and twiddle tables, and SCN_NUM_SLOTS independent result slots (double buffering:
 // the host fills / drains one slot while the GPU works on the other -- the replacement for the reference's MemoryPool + bounded
@@ -99,10 +100,11 @@ struct Slot {
   ScnDeviceMem<float> d_floor;      // [max_batch]
   ScnPinnedMem<float> h_floor;      // [max_batch]
   ScnDeviceMem<float> d_detect_power;  // [max_batch][N] the spectrum the detect kernel reads when the caller keeps none (hits-only floor / baseline plans)
-  // baseline plans (scn_baseline.hip): what scn_plan_update_baseline needs of the slot's last submit -- the spectrum its detect
-  // kernel read (cur_power, d_detect_power: still intact, the slot's next submit is what overwrites it), its units and its first_index
-  const float *base_power = nullptr;
-  uint32_t base_units = 0, base_first = 0;
+  // what scn_plan_update_baseline and scn_plan_update_trace need of the slot's last submit: the spectrum its transform stored (the
+  // caller's buffer, d_power or d_detect_power: still intact, the slot's next submit is what overwrites it; nullptr: it stored
+  // none), its units and its first_index
+  const float *spec_power = nullptr;
+  uint32_t spec_units = 0, spec_first = 0;
   ScnEvent done;
   SlotLife life;                    // what the slot may do next (scn_slot_life.h): written by its on_* functions only
 };
@@ -145,6 +147,13 @@ struct scn_plan : PlanShape {
   ScnDeviceMem<uint32_t> d_history, d_visits;
   uint32_t history_rows = 0;   // 0: none
   uint64_t history_epoch = 0;  // grows with every fold and every scn_plan_set_history: a slot's confirmed list is that of the plan's LATEST fold
+  // the sweep trace (scn_trace.hip; scn_plan_set_trace, kept allocated when dropped): per cell the keys of max_db and min_db
+  // (scn_trace.h; unkeyed at read-out) and the count.  As the history: only scn_plan_update_trace writes them, and it returns
+  // synchronised, so they may change while other slots are pending.
+  ScnDeviceMem<uint32_t> d_trace_max, d_trace_min;
+  ScnDeviceMem<unsigned long long> d_trace_count;
+  uint64_t trace_f0 = 0;
+  uint32_t trace_cell_hz = 0, trace_cells = 0;  // cells 0: none
   uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
   ScnDeviceMem<double> d_twiddle64;  // four-step: [256][2] W_256^k; Bluestein: [fft_m][2] W_m^k; in double
   ScnDeviceMem<double> d_table;      // the plan's frequency table (scn_plan_set_table), read by the compaction kernel; grown on demand
@@ -189,16 +198,22 @@ int ensure_slot_outputs(scn_plan *p, Slot &s, uint32_t gen);
 // What the list kernels, the signal kernels and the confirm kernels read of a slot's pending / last submit, under the same names in
 // every argument struct: the regions, the hits' offsets, and the submit's header fields where they lie (the slot's pinned copy or the
 // plan's table)
+// ... of which the centres alone (the trace's fold reads the spectrum, not the regions)
+template <class A>
+void set_centre_source(A &a, const scn_plan *p, const Slot &s) {
+  const SlotGen &g = s.cur();
+  const bool table = g.table_first >= 0;
+  a.center_freq = table ? p->d_table.get() : s.centres(p->d.max_batch);
+  a.table_count = table ? p->table_count : 0u;
+  a.table_first = table ? (uint32_t)g.table_first : 0u;
+}
 template <class A>
 void set_list_source(A &a, const scn_plan *p, const Slot &s) {
   const SlotGen &g = s.cur();
   a.regions = g.d_hits.get();
   a.hit_region = p->hit_region;
   a.offsets = s.d_offsets.get();
-  const bool table = g.table_first >= 0;
-  a.center_freq = table ? p->d_table.get() : s.centres(p->d.max_batch);
-  a.table_count = table ? p->table_count : 0u;
-  a.table_first = table ? (uint32_t)g.table_first : 0u;
+  set_centre_source(a, p, s);
   a.seq_id = g.seq_given ? s.seq_ids(p->d.max_batch) : nullptr;
   a.n_buffers = s.life.n_buffers;
   a.n = p->d.n;

@@ -215,12 +215,12 @@ int spectrum_destination(scn_plan *p, Slot &s, uint32_t nb, float **d_power) {
   return SCN_OK;
 }
 
-// Baseline plans: what scn_plan_update_baseline folds in once this submit is collected
-void note_baseline_source(const scn_plan *p, Slot &s, const float *d_power, uint32_t nb, uint32_t table_first) {
-  if (!p->baseline) return;
-  s.base_power = d_power;
-  s.base_units = nb;
-  s.base_first = table_first;
+// What scn_plan_update_baseline and scn_plan_update_trace fold in once this submit is collected: behind spectrum_destination d_power
+// is the buffer the transform writes, for every plan kind (nullptr: a hits-only submit that stores no spectrum)
+void note_spectrum_source(Slot &s, const float *d_power, uint32_t nb, uint32_t table_first) {
+  s.spec_power = d_power;
+  s.spec_units = nb;
+  s.spec_first = table_first;
 }
 
 // A submit with hits takes the slot's other generation and leaves its header fields where the compaction kernel reads them
@@ -287,7 +287,7 @@ int submit_common(scn_plan *p, Slot &s, const void *d_raw, uint32_t nb, const do
     return submit_time_domain(p, s, d_raw, nb);
   }
   if ((st = spectrum_destination(p, s, nb, &d_power))) return st;
-  note_baseline_source(p, s, d_power, nb, table_first);
+  note_spectrum_source(s, d_power, nb, table_first);
   if (on_submit(s.life, facts) && (st = stage_headers(p, s, nb, fc, seq, table_first))) return st;
   // what follows the transform, decided once (submit_route, scn_host.hip: the table and the measurements behind it)
   const bool fused = (p->path == Path::FusedPow2 || p->path == Path::FusedMixed) && p->avg == 1u && !detects_behind(p);
@@ -442,17 +442,17 @@ int scn_plan_update_baseline(scn_plan *p, int slot, uint32_t op) {
   const Slot &s = p->slot[slot];
   if (int st = require_learnable(s.life, slot)) return st;
   if (!p->baseline_rows) return scn_fail(SCN_E_STATE, "the plan has no baseline: scn_plan_set_baseline was never called, or dropped it");
-  if (int st = check_baseline_update(p->baseline_rows, s.base_units, op)) return st;
-  if (!s.base_units) return SCN_OK;
+  if (int st = check_baseline_update(p->baseline_rows, s.spec_units, op)) return st;
+  if (!s.spec_units) return SCN_OK;
   SCN_HIP(hipSetDevice(p->d.device_id));
   ScnBaselineArgs a;
   memset(&a, 0, sizeof(a));
-  a.power_db = s.base_power;  // (complete: the slot's collect waited for the detect kernel behind the transform that wrote it)
+  a.power_db = s.spec_power;  // (complete: the slot's collect waited for the detect kernel behind the transform that wrote it)
   a.baseline_db = p->d_baseline.get();
   a.n = p->d.n;
-  a.n_units = s.base_units;
+  a.n_units = s.spec_units;
   a.rows = p->baseline_rows;
-  a.first = s.base_first % p->baseline_rows;
+  a.first = s.spec_first % p->baseline_rows;
   a.op = op;
   SCN_HIP(scn_launch_baseline_update(a, p->stream.get()));
   SCN_HIP(hipStreamSynchronize(p->stream.get()));

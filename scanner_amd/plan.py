@@ -63,6 +63,7 @@ class Plan:
         self._submit_device_indexed = self._L.scn_submit_device_indexed
         self._baseline_rows = 0
         self._history_rows = 0
+        self._trace_cells = 0
         try:
             if floor_window is not None:
                 self.set_floor_window(*floor_window)
@@ -194,6 +195,27 @@ class Plan:
                                                      C.byref(total)), "scn_collect_confirmed")
         self.last_n_confirmed = total.value
         return out[: max(0, min(cap, total.value - int(first)))]
+
+    def set_trace(self, f0_hz, cell_hz, cells):
+        """scn_plan_set_trace: give the plan a sweep trace of `cells` empty cells of cell_hz hertz from f0_hz up (0 cells drops it) --
+        per cell the largest and smallest dB value folded into it and their number (scanner_hip.h, "Sweep trace").  Plans with
+        OUT_HITS whose submits store a spectrum; allowed while slots are pending."""
+        capi.check(self._L.scn_plan_set_trace(self._h, int(f0_hz), int(cell_hz), int(cells)), "scn_plan_set_trace")
+        self._trace_cells = int(cells)
+
+    def update_trace(self, slot):
+        """scn_plan_update_trace: fold the spectrum of the slot's last collected submit into the trace, on the GPU -- every evaluated
+        bin into the cell of the frequency its hit record would carry.  Other slots may be pending; folding a slot twice counts twice."""
+        capi.check(self._L.scn_plan_update_trace(self._h, slot), "scn_plan_update_trace")
+
+    def trace(self, first=0, cells=None):
+        """scn_plan_get_trace: (max_db float32, min_db float32, count uint64) of cells [first, first + cells) (to the trace's end by
+        default); an empty cell reads (-inf, +inf, 0)."""
+        cells = max(0, self._trace_cells - int(first)) if cells is None else int(cells)
+        max_db, min_db, count = np.empty(cells, np.float32), np.empty(cells, np.float32), np.empty(cells, np.uint64)
+        capi.check(self._L.scn_plan_get_trace(self._h, int(first), cells, max_db.ctypes.data_as(C.c_void_p), min_db.ctypes.data_as(C.c_void_p),
+                                              count.ctypes.data_as(C.c_void_p)), "scn_plan_get_trace")
+        return max_db, min_db, count
 
     def submit(self, slot, n_buffers, center_freqs=None, seq_ids=None, first_index=None):
         """Process the first n_buffers raw buffers of the pinned slot (async)."""
