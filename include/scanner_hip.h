@@ -50,7 +50,10 @@ extern "C" {
                              still 6 (additions only): the hit history -- scn_plan_set_history, scn_plan_update_history,
                              scn_plan_get_history, scn_collect_confirmed, scn_history_fold_hits, scn_confirm_hits;
                              still 6 (additions only): the sweep trace -- SCN_TRACE_CELLS_MAX, scn_plan_set_trace,
-                             scn_plan_update_trace, scn_plan_get_trace, scn_trace_fold_spectrum, scn_trace_init, scn_trace_merge */
+                             scn_plan_update_trace, scn_plan_get_trace, scn_trace_fold_spectrum, scn_trace_init, scn_trace_merge;
+                             still 6 (additions only): the level histogram -- SCN_LEVELS_EDGES_MAX, SCN_LEVELS_WORDS_MAX,
+                             scn_plan_set_levels, scn_plan_update_levels, scn_plan_get_levels, scn_plan_levels_summary,
+                             scn_levels_fold_spectrum, scn_levels_merge, scn_levels_summary */
 
 /* status codes */
 enum {
@@ -286,6 +289,35 @@ enum {
  * No kernel of a submit reads or writes the trace: it changes only through scn_plan_set_trace and scn_plan_update_trace, both
  * allowed while other slots are pending.  A plan on which scn_plan_set_trace is never called allocates nothing for it. */
 #define SCN_TRACE_CELLS_MAX (1u << 22)
+
+/* Level histogram (scn_plan_set_levels): how often each cell of a frequency grid was how loud -- what a channel's occupancy, a band's
+ * amplitude distribution and a median (or any percentile) line across the whole table are read from, where the trace keeps only a
+ * cell's two extremes.  A plan may own a level histogram; it has none at first.  It is independent of the plan's trace: a plan may
+ * have both, on different grids.
+ *   Geometry: the trace's cells (f0_hz: uint64, cell_hz: uint32 >= 1, cells: 1 ... SCN_TRACE_CELLS_MAX) and a level table
+ *     edges_db[n_edges] of float32, 1 <= n_edges <= SCN_LEVELS_EDGES_MAX, with cells * (n_edges + 1) <= SCN_LEVELS_WORDS_MAX.
+ *   Edges: no edge is a NaN, and the edges are strictly increasing in the floor detector's key order (the order max_db and min_db of
+ *     the trace are held in): -inf and +inf are legal edges, and -0.0, +0.0 are two distinct edges in that order.  Anything else is
+ *     SCN_E_INVALID, nothing changed.
+ *   State: hist[cells][n_edges + 1] of uint64, device memory, the level index fastest; every counter starts at 0.
+ *   Level of a value v that is not a NaN: level(v) = the number of edges e with key(e) <= key(v), 0 ... n_edges.  Level l holds
+ *     edges_db[l - 1] <= v < edges_db[l] (level 0: everything below the first edge, level n_edges: everything from the last edge
+ *     up); a value equal to an edge belongs to the level above it.
+ *   Which plans: exactly those that can have a trace ("Sweep trace").
+ *   Fold (scn_plan_update_levels): for every unit of the slot's last collected submit and every bin the mask lets through, the cell
+ *     c is the trace's, step for step -- the same freq_hz, the same skips below f0_hz and at or beyond `cells`, the same centre --
+ *     and v = power_db[u][j].  A NaN is skipped; every other value, +-inf included, does hist[c][level(v)] += 1.
+ *   Summary (scn_plan_levels_summary, scn_levels_summary), per cell: total = the sum of hist[c][l] over all l; above = the sum over
+ *     l >= level, for the caller's level in 0 ... n_edges; rank_level = the smallest l whose cumulative count hist[c][0] + ... +
+ *     hist[c][l] exceeds r = floor(permille * (total - 1) / 1000), the caller's permille in 0 ... 1000 taken as it is (0 is the
+ *     lowest occupied level, not a default; 500 the median's; 1000 the highest occupied level).  r is formed without an overflow:
+ *     total - 1 = 1000 a + b, 0 <= b < 1000, r = permille * a + (permille * b) / 1000.  An empty cell reads rank_level =
+ *     0xffffffff, above = 0, total = 0.
+ * An integer sum commutes, so the histogram is exact: the same bits on every run, route, partition and fold order.  No kernel of a
+ * submit reads or writes it: it changes only through scn_plan_set_levels and scn_plan_update_levels, both allowed while other slots
+ * are pending.  A plan on which scn_plan_set_levels is never called allocates nothing for it. */
+#define SCN_LEVELS_EDGES_MAX 255u
+#define SCN_LEVELS_WORDS_MAX (1u << 24)
 
 /* Signals (scn_collect_signals, scn_signals_from_hits): runs of nearby hits merged into one record each.  A plan's buffer is
  * its unit of output (for an averaged plan: the group).  The hits of one unit, in increasing i, are split into signals: a hit
@@ -530,6 +562,42 @@ SCN_API int scn_trace_init(float *max_db, float *min_db, uint64_t *count, uint32
  * sharded sweep joins the ranks' traces of one geometry; merge(A, B) is the trace of everything folded into A or B. */
 SCN_API int scn_trace_merge(float *max_db, float *min_db, uint64_t *count, const float *src_max, const float *src_min,
                             const uint64_t *src_count, uint32_t cells);
+
+/* Gives the plan a level histogram of `cells` cells of cell_hz hertz from f0_hz up and the n_edges + 1 levels of edges_db ("Level
+ * histogram" above), every counter 0; every call zeroes the histogram.  cells == 0 drops it (the allocation is kept for the next
+ * one; the other arguments are not looked at).  Allowed at any time, pending slots or not.  A plan that cannot have a trace, a
+ * geometry outside the limits, a null, unordered or NaN-holding table: SCN_E_INVALID, nothing changed.  A failure of the device
+ * (an allocation, a copy) leaves the plan without a histogram. */
+SCN_API int scn_plan_set_levels(scn_plan *plan, uint64_t f0_hz, uint32_t cell_hz, uint32_t cells, const float *edges_db, uint32_t n_edges);
+
+/* Folds the spectrum of the slot's last COLLECTED submit into the histogram, on the GPU, and returns when that is complete.  The
+ * call rules, the refusals and their order are scn_plan_update_trace's, with "no level histogram" (SCN_E_STATE) in the place of "no
+ * trace".  Folding the same slot twice counts twice. */
+SCN_API int scn_plan_update_levels(scn_plan *plan, int slot);
+
+/* Copies cells [first_cell, first_cell + cells) of the histogram, (n_edges + 1) counters each, to host memory.  A range outside the
+ * histogram is SCN_E_INVALID; hist may be NULL where cells is 0. */
+SCN_API int scn_plan_get_levels(scn_plan *plan, uint32_t first_cell, uint32_t cells, uint64_t *hist);
+
+/* The summary of cells [first_cell, first_cell + cells), reduced on the GPU: what a caller reads instead of the whole table.  Any
+ * of the three outputs (`cells` entries each) may be NULL.  A range outside the histogram, permille > 1000 or level > n_edges:
+ * SCN_E_INVALID. */
+SCN_API int scn_plan_levels_summary(scn_plan *plan, uint32_t first_cell, uint32_t cells, uint32_t permille, uint32_t level,
+                                    uint32_t *rank_level, uint64_t *above, uint64_t *total);
+
+/* The same fold on host memory: the definition the GPU form is held to (the same bits).  Needs no device.  hist (cells * (n_edges +
+ * 1) counters) is read and written: calls accumulate on what the caller zeroed.  The other arguments and their rules are
+ * scn_trace_fold_spectrum's; a geometry or a table scn_plan_set_levels would refuse: SCN_E_INVALID, nothing changed. */
+SCN_API int scn_levels_fold_spectrum(uint64_t *hist, uint64_t f0_hz, uint32_t cell_hz, uint32_t cells, const float *edges_db, uint32_t n_edges,
+                                     const float *power_db, uint32_t n_units, uint32_t n, uint32_t sample_rate, uint32_t dc_ignore_bins,
+                                     double use_bandwidth, const double *center_freqs);
+/* Counter by counter hist += src (cells * n_levels each, n_levels = n_edges + 1) -- how the root of a sharded sweep joins the ranks'
+ * histograms of one geometry; merge(A, B) is the histogram of everything folded into A or B. */
+SCN_API int scn_levels_merge(uint64_t *hist, const uint64_t *src, uint32_t cells, uint32_t n_levels);
+/* The summary ("Level histogram" above) of every cell of a histogram on host memory; any of the three outputs may be NULL.
+ * permille > 1000, level >= n_levels, a null hist or a size outside the limits: SCN_E_INVALID, nothing written. */
+SCN_API int scn_levels_summary(const uint64_t *hist, uint32_t cells, uint32_t n_levels, uint32_t permille, uint32_t level,
+                               uint32_t *rank_level, uint64_t *above, uint64_t *total);
 
 /* Time-domain plans (mode = SCN_MODE_TIME_DOMAIN; ProcessSamples::DoTimeDomainThresholding,
  * process.cpp:203-237): wait for the slot's submit and fetch, per buffer, the maximum and

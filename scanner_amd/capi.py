@@ -28,6 +28,8 @@ BASELINE_SET, BASELINE_MAX = 0, 1  # scn_plan_update_baseline's op
 FLOOR_MIN = 0xFFFFFFFF  # scn_plan_desc.floor_permille: rank 0 (0 itself asks for the default, the median)
 FLOOR_TRAIN_MAX, FLOOR_GUARD_MAX = 128, 64  # the floor window's limits (scn_plan_set_floor_window)
 TRACE_CELLS_MAX = 1 << 22  # the most cells a sweep trace has (scn_plan_set_trace)
+LEVELS_EDGES_MAX, LEVELS_WORDS_MAX = 255, 1 << 24  # a level histogram's most edges, and most counters (scn_plan_set_levels)
+LEVELS_NO_RANK = 0xFFFFFFFF  # rank_level of an empty cell
 PATH_UNSUPPORTED, PATH_FUSED, PATH_FOUR_STEP, PATH_STAGED, PATH_BLUESTEIN = range(5)
 COMM_ID_BYTES = 128
 GATHER_TICKETS = 4
@@ -130,6 +132,14 @@ SYMBOLS = {
                                           C.c_double, _vp]),
     "scn_trace_init": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
     "scn_trace_merge": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
+    "scn_plan_set_levels": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32]),
+    "scn_plan_update_levels": (C.c_int, [_vp, C.c_int]),
+    "scn_plan_get_levels": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    "scn_plan_levels_summary": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "scn_levels_fold_spectrum": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_double, _vp]),
+    "scn_levels_merge": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32]),
+    "scn_levels_summary": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "scn_collect_time_domain": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "scn_convert_raw": (C.c_int, [_vp, _vp, C.c_uint32, _vp]),
     "scn_wait": (C.c_int, [_vp, C.c_int]),
@@ -317,6 +327,48 @@ def trace_merge(trace, src):
     assert src_max.size == src_min.size == src_count.size == max_db.size
     check(lib().scn_trace_merge(*_trace_arrays(max_db, min_db, count), src_max.ctypes.data_as(_vp), src_min.ctypes.data_as(_vp),
                                 src_count.ctypes.data_as(_vp), max_db.size), "scn_trace_merge")
+
+
+def _levels_hist(hist):
+    assert hist.dtype == np.uint64 and hist.ndim == 2 and hist.flags.c_contiguous and hist.flags.writeable
+    return hist.ctypes.data_as(_vp)
+
+
+def levels_fold_spectrum(hist, f0_hz, cell_hz, edges_db, power_db, sample_rate, center_freqs, dc_ignore_bins=4, use_bandwidth=0.75):
+    """scn_levels_fold_spectrum: the spectra power_db (float32 [units, n], natural bin order) of units centred at center_freqs folded
+    IN PLACE into hist (uint64 [cells, len(edges_db) + 1]) on the grid (f0_hz, cell_hz, cells) and the level table edges_db -- what
+    Plan.update_levels does on the GPU, to the bit (scanner_hip.h, "Level histogram").  Needs no device."""
+    edges = np.ascontiguousarray(edges_db, np.float32).reshape(-1)
+    assert hist.shape[1] == edges.size + 1, f"{hist.shape[1]} levels for {edges.size} edges"
+    power_db = np.ascontiguousarray(power_db, np.float32)
+    assert power_db.ndim == 2
+    fc = np.ascontiguousarray(center_freqs, np.float64).reshape(-1)
+    assert fc.size == power_db.shape[0], f"{fc.size} centres for {power_db.shape[0]} units"
+    check(lib().scn_levels_fold_spectrum(_levels_hist(hist), int(f0_hz), int(cell_hz), hist.shape[0], edges.ctypes.data_as(_vp), edges.size,
+                                         power_db.ctypes.data_as(_vp), power_db.shape[0], power_db.shape[1], int(sample_rate),
+                                         DC_IGNORE_NONE if dc_ignore_bins == 0 else int(dc_ignore_bins), float(use_bandwidth), fc.ctypes.data_as(_vp)),
+          "scn_levels_fold_spectrum")
+
+
+def levels_merge(hist, src):
+    """scn_levels_merge: hist += src IN PLACE, counter by counter (uint64 [cells, n_levels] both) -- how the root of a sharded sweep
+    joins the ranks' histograms.  Needs no device."""
+    src = np.ascontiguousarray(src, np.uint64)
+    assert src.shape == hist.shape
+    check(lib().scn_levels_merge(_levels_hist(hist), src.ctypes.data_as(_vp), hist.shape[0], hist.shape[1]), "scn_levels_merge")
+
+
+def levels_summary(hist, permille=500, level=0):
+    """scn_levels_summary: per cell of hist (uint64 [cells, n_levels]) -> (rank_level uint32, above uint64, total uint64): the
+    smallest level whose cumulative count exceeds floor(permille * (total - 1) / 1000) (0xFFFFFFFF in an empty cell), the counts of
+    the levels >= level, and all counts.  Needs no device."""
+    hist = np.ascontiguousarray(hist, np.uint64)
+    assert hist.ndim == 2
+    cells = hist.shape[0]
+    rank, above, total = np.empty(cells, np.uint32), np.empty(cells, np.uint64), np.empty(cells, np.uint64)
+    check(lib().scn_levels_summary(hist.ctypes.data_as(_vp), cells, hist.shape[1], int(permille), int(level), rank.ctypes.data_as(_vp),
+                                   above.ctypes.data_as(_vp), total.ctypes.data_as(_vp)), "scn_levels_summary")
+    return rank, above, total
 
 
 def floor_from_spectrum(power_db, dc_ignore_bins=4, use_bandwidth=0.75, floor_permille=0):

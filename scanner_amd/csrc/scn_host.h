@@ -103,6 +103,14 @@ int check_history_range(uint32_t have, uint32_t first_row, uint32_t rows);
 int check_trace_geometry(uint32_t cell_hz, uint32_t cells);
 int check_trace_range(uint32_t have, uint32_t first_cell, uint32_t cells);
 
+// The level histogram (scanner_hip.h, "Level histogram"): a geometry's limits (the trace's, the number of edges, the words of the
+// whole table), a table of edges -- no NaN, strictly increasing keys; keys: the kLevelsKeys padded keys of scn_levels.h, written
+// only when the table is good -- and a summary's two numbers; shared by the plan's entry points (scn_levels_plan.hip) and the host
+// forms.  The arithmetic is scn_levels.h's, the kernels' own.
+int check_levels_geometry(uint32_t cell_hz, uint32_t cells, uint32_t n_edges);
+int check_levels_edges(const float *edges_db, uint32_t n_edges, uint32_t *keys);
+int check_levels_summary(uint32_t n_levels, uint32_t permille, uint32_t level);
+
 // Averaged plans (k = average > 1; sweeps: SCN_AVG_SWEEPS, else SCN_AVG_DWELL).  group_headers redirects fc / seq to the groups'
 // (held in group_fc / group_seq) where the submit gave them or the compaction kernel's default would be wrong; returns the groups
 int check_average(uint32_t k, bool sweeps, uint32_t nb, const double *fc);

@@ -3,6 +3,7 @@
 // test_plan_resolve.cpp build the unit with g++ under the sanitizers); the .hip suffix only puts it through the library's compiler.
 #include "scn_host.h"
 
+#include "scn_levels.h"
 #include "scn_trace.h"
 #include "scn_wire.h"
 
@@ -356,6 +357,40 @@ int check_trace_range(uint32_t have, uint32_t first_cell, uint32_t cells) {
   return SCN_OK;
 }
 
+int check_levels_geometry(uint32_t cell_hz, uint32_t cells, uint32_t n_edges) {
+  if (int st = check_trace_geometry(cell_hz, cells)) return st;
+  if (n_edges == 0 || n_edges > SCN_LEVELS_EDGES_MAX) return scn_fail(SCN_E_INVALID, "a level table has 1 ... %u edges: %u", SCN_LEVELS_EDGES_MAX, n_edges);
+  if ((uint64_t)cells * (n_edges + 1u) > SCN_LEVELS_WORDS_MAX)
+    return scn_fail(SCN_E_INVALID, "%u cells of %u levels: more than %u counters", cells, n_edges + 1u, SCN_LEVELS_WORDS_MAX);
+  return SCN_OK;
+}
+
+int check_levels_edges(const float *edges_db, uint32_t n_edges, uint32_t *keys) {
+  if (!edges_db) return scn_fail(SCN_E_INVALID, "null argument");
+  if (n_edges == 0 || n_edges > SCN_LEVELS_EDGES_MAX) return scn_fail(SCN_E_INVALID, "a level table has 1 ... %u edges: %u", SCN_LEVELS_EDGES_MAX, n_edges);
+  uint32_t below = 0;
+  for (uint32_t e = 0; e < n_edges; e++) {
+    uint32_t bits;
+    memcpy(&bits, edges_db + e, sizeof(bits));
+    if (scn_trace_is_nan(bits)) return scn_fail(SCN_E_INVALID, "edge %u is a NaN", e);
+    const uint32_t key = scn_trace_key(bits);
+    if (e != 0 && key <= below) return scn_fail(SCN_E_INVALID, "edge %u is not above edge %u", e, e - 1u);
+    below = key;
+  }
+  for (uint32_t e = 0; e < kLevelsKeys; e++) {
+    uint32_t bits = 0;
+    if (e < n_edges) memcpy(&bits, edges_db + e, sizeof(bits));
+    keys[e] = e < n_edges ? scn_trace_key(bits) : kLevelsPadKey;
+  }
+  return SCN_OK;
+}
+
+int check_levels_summary(uint32_t n_levels, uint32_t permille, uint32_t level) {
+  if (permille > 1000u) return scn_fail(SCN_E_INVALID, "permille %u above 1000", permille);
+  if (level >= n_levels) return scn_fail(SCN_E_INVALID, "level %u of a table of %u levels", level, n_levels);
+  return SCN_OK;
+}
+
 namespace {
 
 // One cell's hold: *max_db becomes the larger of itself and hi, *min_db the smaller of itself and lo, in the key order of
@@ -621,6 +656,71 @@ int scn_trace_fold_spectrum(float *max_db, float *min_db, uint64_t *count, uint6
       trace_hold(max_db + c, min_db + c, row[j], row[j]);
       count[c]++;
     }
+  }
+  return SCN_OK;
+}
+
+int scn_levels_fold_spectrum(uint64_t *hist, uint64_t f0_hz, uint32_t cell_hz, uint32_t cells, const float *edges_db, uint32_t n_edges,
+                             const float *power_db, uint32_t n_units, uint32_t n, uint32_t sample_rate, uint32_t dc_ignore_bins, double use_bandwidth,
+                             const double *center_freqs) {
+  if (!hist || !edges_db || (n_units && (!power_db || !center_freqs))) return scn_fail(SCN_E_INVALID, "null argument");
+  if (int st = check_levels_geometry(cell_hz, cells, n_edges)) return st;
+  uint32_t keys[kLevelsKeys];
+  if (int st = check_levels_edges(edges_db, n_edges, keys)) return st;
+  if (n == 0 || n > (1u << 24)) return scn_fail(SCN_E_INVALID, "bad bin count %u", n);
+  if (sample_rate == 0) return scn_fail(SCN_E_INVALID, "sample_rate must be > 0");
+  struct { uint32_t dc_ignore, i_lo, i_hi; } mask = {dc_ignore_bins ? dc_ignore_bins : 4u, 0, 0};  // the descriptor's defaults (scn_plan_create)
+  if (mask.dc_ignore == SCN_DC_IGNORE_NONE) mask.dc_ignore = 0;
+  evaluated_bins(n, mask.dc_ignore, use_bandwidth == 0.0 ? 0.75 : use_bandwidth, &mask.i_lo, &mask.i_hi);
+  const uint32_t bin_step = sample_rate / n;  // process.cpp:39 (truncating)
+  const uint32_t top = scn_levels_top(n_edges), n_levels = n_edges + 1u;
+  for (uint32_t u = 0; u < n_units; u++) {
+    const double start_frequency = scn_trace_start(center_freqs[u], sample_rate);
+    const float *const row = power_db + (size_t)u * n;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t j = (i + n / 2) % n;
+      if (!scn_bin_evaluated(j, i, n, mask)) continue;
+      uint32_t bits;
+      memcpy(&bits, row + j, sizeof(bits));
+      if (scn_trace_is_nan(bits)) continue;
+      const uint32_t c = scn_trace_cell(scn_trace_freq(start_frequency, i, bin_step), f0_hz, cell_hz, cells);
+      if (c == kTraceNoCell) continue;
+      hist[(size_t)c * n_levels + scn_levels_level(keys, top, scn_trace_key(bits))]++;
+    }
+  }
+  return SCN_OK;
+}
+
+int scn_levels_merge(uint64_t *hist, const uint64_t *src, uint32_t cells, uint32_t n_levels) {
+  if (!hist || !src) return scn_fail(SCN_E_INVALID, "null argument");
+  if (n_levels < 2u) return scn_fail(SCN_E_INVALID, "a level table has 1 ... %u edges: %u", SCN_LEVELS_EDGES_MAX, n_levels - 1u);
+  if (int st = check_levels_geometry(1u, cells, n_levels - 1u)) return st;
+  for (size_t w = 0; w < (size_t)cells * n_levels; w++) hist[w] += src[w];
+  return SCN_OK;
+}
+
+int scn_levels_summary(const uint64_t *hist, uint32_t cells, uint32_t n_levels, uint32_t permille, uint32_t level, uint32_t *rank_level,
+                       uint64_t *above, uint64_t *total) {
+  if (!hist) return scn_fail(SCN_E_INVALID, "null argument");
+  if (n_levels < 2u) return scn_fail(SCN_E_INVALID, "a level table has 1 ... %u edges: %u", SCN_LEVELS_EDGES_MAX, n_levels - 1u);
+  if (int st = check_levels_geometry(1u, cells, n_levels - 1u)) return st;
+  if (int st = check_levels_summary(n_levels, permille, level)) return st;
+  for (uint32_t c = 0; c < cells; c++) {
+    const uint64_t *const row = hist + (size_t)c * n_levels;
+    uint64_t sum = 0, from_level = 0;
+    for (uint32_t l = 0; l < n_levels; l++) {
+      sum += row[l];
+      if (l >= level) from_level += row[l];
+    }
+    uint32_t rank = kLevelsNoRank;
+    if (sum != 0) {
+      const uint64_t r = scn_levels_rank(sum, permille);
+      uint64_t cum = 0;
+      for (rank = 0; (cum += row[rank]) <= r; rank++) {}  // (r < sum: it ends inside the row)
+    }
+    if (rank_level) rank_level[c] = rank;
+    if (above) above[c] = from_level;
+    if (total) total[c] = sum;
   }
   return SCN_OK;
 }

@@ -182,6 +182,31 @@ struct ScnTraceArgs {
   unsigned long long *count;   // [cells]
 };
 hipError_t scn_launch_trace_fold(const ScnTraceArgs &args, int num_cus, hipStream_t stream);
+// The level histogram (scn_levels.hip, scanner_hip.h "Level histogram"): per cell of the plan's frequency grid and per level of its
+// table of edges, how many dB values were folded into it.  The fold launch reads what the trace's reads (the same fields under the
+// same names) and changes the counters with atomics only; the summary launch reduces cells [first_cell, first_cell + cells) to
+// three numbers each.
+struct ScnLevelsArgs {
+  const float *power_db;       // [n_units][n], natural bin order
+  const double *center_freq;   // as ScnTraceArgs
+  uint32_t table_count, table_first;
+  uint32_t n, n_units, sample_rate;
+  uint32_t dc_ignore, i_lo, i_hi;
+  uint64_t f0_hz;              // the grid, as the trace's
+  uint32_t cell_hz, cells;
+  const uint32_t *edge_keys;   // [kLevelsKeys] the edges' keys, padded (scn_levels.h)
+  uint32_t n_edges;            // 1 ... SCN_LEVELS_EDGES_MAX; cells * (n_edges + 1) <= SCN_LEVELS_WORDS_MAX
+  unsigned long long *hist;    // [cells][n_edges + 1]
+};
+hipError_t scn_launch_levels_fold(const ScnLevelsArgs &args, int num_cus, hipStream_t stream);
+struct ScnLevelsSummaryArgs {
+  const unsigned long long *hist;  // [..][n_levels]
+  uint32_t first_cell, cells, n_levels;
+  uint32_t permille, level;        // permille <= 1000, level < n_levels
+  uint32_t *rank_level;            // [cells] each
+  unsigned long long *above, *total;
+};
+hipError_t scn_launch_levels_summary(const ScnLevelsSummaryArgs &args, hipStream_t stream);
 // sum of counts[0, n_buffers) -> *host_total (pinned host memory); acc: two zeroed device words the kernel leaves zeroed
 hipError_t scn_launch_hit_total(const uint32_t *counts, uint32_t n_buffers, uint32_t trigger_count, unsigned long long *acc, unsigned long long *host_total,
                                 uint32_t *trigger_bits, hipStream_t stream);

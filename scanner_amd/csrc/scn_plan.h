@@ -154,6 +154,13 @@ struct scn_plan : PlanShape {
   ScnDeviceMem<unsigned long long> d_trace_count;
   uint64_t trace_f0 = 0;
   uint32_t trace_cell_hz = 0, trace_cells = 0;  // cells 0: none
+  // the level histogram (scn_levels.hip; scn_plan_set_levels, kept allocated when dropped): the counters [cells][n_edges + 1], the
+  // table's padded keys as the fold kernel stages them (scn_levels.h), and the summary kernel's outputs, grown to the largest
+  // window asked for.  Written as the trace is: by calls that return synchronised only.
+  ScnDeviceMem<unsigned long long> d_levels_hist, d_levels_sums;  // sums: [2][window] above, total
+  ScnDeviceMem<uint32_t> d_levels_keys, d_levels_rank;
+  uint64_t levels_f0 = 0;
+  uint32_t levels_cell_hz = 0, levels_cells = 0, levels_edges = 0;  // cells 0: none
   uint32_t fft_m = 0, log2m = 0;     // Bluestein: the transform length, the power of two >= 2n - 1
   ScnDeviceMem<double> d_twiddle64;  // four-step: [256][2] W_256^k; Bluestein: [fft_m][2] W_m^k; in double
   ScnDeviceMem<double> d_table;      // the plan's frequency table (scn_plan_set_table), read by the compaction kernel; grown on demand
@@ -238,3 +245,21 @@ inline bool detects_behind(const scn_plan *p) { return p->floor || p->baseline; 
 
 // the stream the slot's ordered list is built and fetched on
 inline hipStream_t list_stream_of(const scn_plan *p, const Slot &s) { return s.own_stream ? s.stream : p->list_stream.get(); }
+
+// scn_trace_plan.hip: what the sweep trace and the level histogram (scn_levels_plan.hip) share, stated there once -- the plans that
+// can have either; the refusals of a fold of `slot`, in scn_plan_update_trace's order (`owns`: the plan has what the fold writes,
+// `none`: the message where it has not; *folds: the submit has a unit to fold); and what a fold kernel reads of the slot's last
+// submit (the spectrum it stored, its centres where it left them, the mask), under the names ScnTraceArgs gives them
+int check_trace_plan(const scn_plan *p);
+int check_trace_fold(scn_plan *p, int slot, bool owns, const char *none, bool *folds);
+template <class A>
+void set_fold_source(A &a, const scn_plan *p, const Slot &s) {
+  a.power_db = s.spec_power;
+  set_centre_source(a, p, s);
+  a.n = p->d.n;
+  a.n_units = s.life.n_buffers;
+  a.sample_rate = p->d.sample_rate;
+  a.dc_ignore = p->d.dc_ignore_bins;
+  a.i_lo = p->i_lo;
+  a.i_hi = p->i_hi;
+}

@@ -11,8 +11,6 @@
 #include "scn_plan.h"
 #include "scn_trace.h"
 
-namespace {
-
 // a plan that can have a trace: frequency-domain, with SCN_OUT_HITS (its submits stage their centres), and its submits store a spectrum
 int check_trace_plan(const scn_plan *p) {
   if (!p) return scn_fail(SCN_E_INVALID, "null plan");
@@ -23,7 +21,21 @@ int check_trace_plan(const scn_plan *p) {
   return SCN_OK;
 }
 
-}  // namespace
+// The refusals of a fold, before anything is queued.  Where it returns SCN_OK with *folds set, the spectrum is complete -- the
+// slot's collect waited for the kernel that wrote it -- and stays until the slot's next submit; the centres lie where that submit
+// left them (the slot's pinned copy or the plan's table).  Other slots may be pending: their kernels never touch what a fold writes.
+int check_trace_fold(scn_plan *p, int slot, bool owns, const char *none, bool *folds) {
+  *folds = false;
+  if (int st = check_slot(p, slot)) return st;
+  if (int st = check_trace_plan(p)) return st;
+  const Slot &s = p->slot[slot];
+  if (int st = require_list(s.life, slot, "hit list is still on the device")) return st;
+  if (!owns) return scn_fail(SCN_E_STATE, "%s", none);
+  if (!s.life.n_buffers) return SCN_OK;  // (no unit, nothing to fold)
+  if (!s.spec_power || s.spec_units != s.life.n_buffers) return scn_fail(SCN_E_STATE, "slot %d: its submit stored no spectrum", slot);
+  *folds = true;
+  return SCN_OK;
+}
 
 extern "C" {
 
@@ -52,26 +64,13 @@ int scn_plan_set_trace(scn_plan *p, uint64_t f0_hz, uint32_t cell_hz, uint32_t c
 }
 
 int scn_plan_update_trace(scn_plan *p, int slot) {
-  if (int st = check_slot(p, slot)) return st;
-  if (int st = check_trace_plan(p)) return st;
+  bool folds;
+  if (int st = check_trace_fold(p, slot, p && p->trace_cells, "the plan has no trace: scn_plan_set_trace was never called, or dropped it", &folds)) return st;
+  if (!folds) return SCN_OK;
   Slot &s = p->slot[slot];
-  if (int st = require_list(s.life, slot, "hit list is still on the device")) return st;
-  if (!p->trace_cells) return scn_fail(SCN_E_STATE, "the plan has no trace: scn_plan_set_trace was never called, or dropped it");
-  if (!s.life.n_buffers) return SCN_OK;  // (no unit, nothing to fold)
-  if (!s.spec_power || s.spec_units != s.life.n_buffers) return scn_fail(SCN_E_STATE, "slot %d: its submit stored no spectrum", slot);
   SCN_HIP(hipSetDevice(p->d.device_id));
-  // The spectrum is complete -- the slot's collect waited for the kernel that wrote it -- and stays until the slot's next submit; the
-  // centres lie where that submit left them (the slot's pinned copy or the plan's table).  Other slots may be pending: their kernels
-  // never touch the trace.
   ScnTraceArgs a = {};
-  a.power_db = s.spec_power;
-  set_centre_source(a, p, s);
-  a.n = p->d.n;
-  a.n_units = s.life.n_buffers;
-  a.sample_rate = p->d.sample_rate;
-  a.dc_ignore = p->d.dc_ignore_bins;
-  a.i_lo = p->i_lo;
-  a.i_hi = p->i_hi;
+  set_fold_source(a, p, s);
   a.f0_hz = p->trace_f0;
   a.cell_hz = p->trace_cell_hz;
   a.cells = p->trace_cells;

@@ -64,6 +64,7 @@ class Plan:
         self._baseline_rows = 0
         self._history_rows = 0
         self._trace_cells = 0
+        self._levels_shape = (0, 0)
         try:
             if floor_window is not None:
                 self.set_floor_window(*floor_window)
@@ -216,6 +217,40 @@ class Plan:
         capi.check(self._L.scn_plan_get_trace(self._h, int(first), cells, max_db.ctypes.data_as(C.c_void_p), min_db.ctypes.data_as(C.c_void_p),
                                               count.ctypes.data_as(C.c_void_p)), "scn_plan_get_trace")
         return max_db, min_db, count
+
+    def set_levels(self, f0_hz, cell_hz, cells, edges_db):
+        """scn_plan_set_levels: give the plan a level histogram of `cells` cells of cell_hz hertz from f0_hz up and the
+        len(edges_db) + 1 levels the edges (float32, strictly increasing, no NaN) cut the dB axis into, every counter 0 (0 cells
+        drops it) -- scanner_hip.h, "Level histogram".  The plans that can have a trace; allowed while slots are pending."""
+        edges = np.ascontiguousarray(edges_db, np.float32).reshape(-1)
+        capi.check(self._L.scn_plan_set_levels(self._h, int(f0_hz), int(cell_hz), int(cells), edges.ctypes.data_as(C.c_void_p), edges.size),
+                   "scn_plan_set_levels")
+        self._levels_shape = (int(cells), edges.size + 1 if cells else 0)
+
+    def update_levels(self, slot):
+        """scn_plan_update_levels: fold the spectrum of the slot's last collected submit into the level histogram, on the GPU --
+        every evaluated bin that is not a NaN counts once, in the trace's cell and the level of its dB value.  Other slots may be
+        pending; folding a slot twice counts twice."""
+        capi.check(self._L.scn_plan_update_levels(self._h, slot), "scn_plan_update_levels")
+
+    def levels(self, first=0, cells=None):
+        """scn_plan_get_levels: the counters uint64 [cells, n_levels] of cells [first, first + cells) (to the end by default)."""
+        have, n_levels = self._levels_shape
+        cells = max(0, have - int(first)) if cells is None else int(cells)
+        hist = np.empty((cells, n_levels), np.uint64)
+        capi.check(self._L.scn_plan_get_levels(self._h, int(first), cells, hist.ctypes.data_as(C.c_void_p)), "scn_plan_get_levels")
+        return hist
+
+    def levels_summary(self, permille=500, level=0, first=0, cells=None):
+        """scn_plan_levels_summary, reduced on the GPU: (rank_level uint32, above uint64, total uint64) per cell of [first, first +
+        cells) -- the smallest level whose cumulative count exceeds floor(permille * (total - 1) / 1000) (500: the median's level;
+        0xFFFFFFFF in an empty cell), the counts of the levels >= level (over total: the occupancy above edges_db[level - 1]), and
+        all counts."""
+        cells = max(0, self._levels_shape[0] - int(first)) if cells is None else int(cells)
+        rank, above, total = np.empty(cells, np.uint32), np.empty(cells, np.uint64), np.empty(cells, np.uint64)
+        capi.check(self._L.scn_plan_levels_summary(self._h, int(first), cells, int(permille), int(level), rank.ctypes.data_as(C.c_void_p),
+                                                   above.ctypes.data_as(C.c_void_p), total.ctypes.data_as(C.c_void_p)), "scn_plan_levels_summary")
+        return rank, above, total
 
     def submit(self, slot, n_buffers, center_freqs=None, seq_ids=None, first_index=None):
         """Process the first n_buffers raw buffers of the pinned slot (async)."""
