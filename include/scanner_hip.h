@@ -53,7 +53,9 @@ extern "C" {
                              scn_plan_update_trace, scn_plan_get_trace, scn_trace_fold_spectrum, scn_trace_init, scn_trace_merge;
                              still 6 (additions only): the level histogram -- SCN_LEVELS_EDGES_MAX, SCN_LEVELS_WORDS_MAX,
                              scn_plan_set_levels, scn_plan_update_levels, scn_plan_get_levels, scn_plan_levels_summary,
-                             scn_levels_fold_spectrum, scn_levels_merge, scn_levels_summary */
+                             scn_levels_fold_spectrum, scn_levels_merge, scn_levels_summary;
+                             still 6 (additions only): the trace emitters -- SCN_TRACE_LINE_*, scn_emitter, scn_trace_emitters,
+                             scn_plan_trace_emitters, scn_plan_merge_trace */
 
 /* status codes */
 enum {
@@ -289,6 +291,33 @@ enum {
  * No kernel of a submit reads or writes the trace: it changes only through scn_plan_set_trace and scn_plan_update_trace, both
  * allowed while other slots are pending.  A plan on which scn_plan_set_trace is never called allocates nothing for it. */
 #define SCN_TRACE_CELLS_MAX (1u << 22)
+
+/* Trace emitters (scn_plan_trace_emitters, scn_trace_emitters): the scanner's end product -- the emitters in the band, in absolute
+ * hertz, one record per run of loud cells of a line of the trace.  Where a signal (below) never spans two units, an emitter is cut by
+ * nothing but the trace's own cells: one that straddles the seam between two table entries, is seen by overlapping centres or was
+ * on in every sweep is ONE record.  For a cell c of a window [first_cell, first_cell + cells) of a trace:
+ *   Value: line SCN_TRACE_LINE_MAX: v = max_db[c]; SCN_TRACE_LINE_MIN: v = min_db[c]; SCN_TRACE_LINE_SPREAD: v = max_db[c] -
+ *     min_db[c], one IEEE float32 subtraction, round to nearest, a denormal result kept; inf - inf is a NaN.
+ *   On: cell c is on exactly when count[c] != 0, v is not a NaN, and v > threshold_db as float32 compares them (strict, as every
+ *     detector here; -0.0 and +0.0 are equal).  threshold_db = -inf turns every non-empty cell on whose v is neither -inf nor a
+ *     NaN; +inf turns nothing on.  Cells outside the window are off.
+ *   Runs: the signals' rule, on cells.  In increasing c, an on cell starts a new emitter when it is the window's first on cell or
+ *     when its c exceeds the previous on cell's by more than max_gap + 1.  Any uint32 max_gap is legal; an empty cell bridges as
+ *     any other off cell does.
+ *   The list is ordered by first_cell.  As scn_signal, the record has no mean and no float sum: every field is a pure function of
+ *   the window, built from integers and compares (and the spread's one subtraction), the same bits on every run. */
+enum { SCN_TRACE_LINE_MAX = 0, SCN_TRACE_LINE_MIN = 1, SCN_TRACE_LINE_SPREAD = 2 };
+typedef struct scn_emitter { /* 56 bytes */
+  uint64_t start_hz;    /* f0_hz + first_cell * cell_hz, uint64 arithmetic: the lower edge of the first on cell */
+  uint64_t stop_hz;     /* f0_hz + (last_cell + 1) * cell_hz: the exclusive upper edge of the last on cell */
+  uint64_t peak_hz;     /* f0_hz + peak_cell * cell_hz */
+  uint64_t count;       /* sum of count[c] over the emitter's ON cells */
+  uint32_t first_cell, last_cell; /* absolute cell indices of the trace (not window-relative) */
+  uint32_t peak_cell;   /* the on cell with the largest v in the trace's key order (-0.0 below +0.0); equal keys: the lowest cell */
+  uint32_t n_cells;     /* on cells (<= last_cell - first_cell + 1; equal when max_gap = 0) */
+  float peak_db;        /* v at peak_cell, bit for bit */
+  float peak_other_db;  /* MAX: min_db[peak_cell]; MIN and SPREAD: max_db[peak_cell]; bit for bit */
+} scn_emitter;
 
 /* Level histogram (scn_plan_set_levels): how often each cell of a frequency grid was how loud -- what a channel's occupancy, a band's
  * amplitude distribution and a median (or any percentile) line across the whole table are read from, where the trace keeps only a
@@ -562,6 +591,37 @@ SCN_API int scn_trace_init(float *max_db, float *min_db, uint64_t *count, uint32
  * sharded sweep joins the ranks' traces of one geometry; merge(A, B) is the trace of everything folded into A or B. */
 SCN_API int scn_trace_merge(float *max_db, float *min_db, uint64_t *count, const float *src_max, const float *src_min,
                             const uint64_t *src_count, uint32_t cells);
+
+/* scn_trace_merge of a host window into cells [first_cell, first_cell + cells) of the plan's trace, on the GPU: count adds, max_db
+ * and min_db hold in key order -- what the root of a sharded sweep takes each rank's trace in with before it asks for the band's
+ * emitters, and how exact cell values are put into a plan's trace.  A plan that cannot have a trace: SCN_E_INVALID; one that has
+ * none: SCN_E_STATE; a range outside the trace, a null array with cells != 0, or a NaN anywhere in src_max or src_min (the host
+ * arrays are scanned before anything is uploaded: a plan's trace never holds a NaN): SCN_E_INVALID, nothing changed.  Afterwards the
+ * trace is bit for bit what scn_trace_merge makes of the two.  Runs on the plan's side stream and returns synchronised: allowed
+ * while slots are pending.  cells == 0 is SCN_OK. */
+SCN_API int scn_plan_merge_trace(scn_plan *plan, uint32_t first_cell, uint32_t cells, const float *src_max, const float *src_min,
+                                 const uint64_t *src_count);
+
+/* The emitters ("Trace emitters" above) of cells [first_cell, first_cell + cells) of the plan's trace, built on the GPU: only the
+ * records cross to the host.  *n_emitters = the total; records [first, first + cap) of the list are stored, SCN_E_TRUNCATED when
+ * first + cap < total (the records stored are valid), out may be NULL with cap 0 to learn the total -- scn_collect_signals' paging.
+ * Every call recomputes: pages agree as long as the trace does not change between the calls.  A plan that cannot have a trace, a
+ * line above SCN_TRACE_LINE_SPREAD or a NaN threshold_db: SCN_E_INVALID; a plan without a trace: SCN_E_STATE; a range outside the
+ * trace: SCN_E_INVALID.  cells == 0 is SCN_OK with no emitter.  Runs on the plan's side stream and returns synchronised, as
+ * scn_plan_get_trace: allowed while slots are pending.  The record storage is the plan's, allocated at the first call and grown on
+ * demand; a plan on which this is never called allocates nothing for it. */
+SCN_API int scn_plan_trace_emitters(scn_plan *plan, uint32_t first_cell, uint32_t cells, uint32_t line, float threshold_db,
+                                    uint32_t max_gap, uint32_t first, scn_emitter *out, uint32_t cap, uint32_t *n_emitters);
+
+/* The same list from a window on host memory: the definition the GPU form is held to (the same bits), and what a caller with a
+ * trace but no plan at hand uses.  Needs no device.  max_db, min_db and count are the window, `cells` entries each;
+ * first_cell_index is the absolute index of their first cell (first_cell, last_cell, peak_cell and the hertz fields count from the
+ * trace's cell 0).  Stores the first min(total, cap) records, *n_emitters = the total; SCN_E_TRUNCATED when cap < total; out may
+ * be NULL with cap 0.  A null array, cell_hz == 0, cells outside 1 ... SCN_TRACE_CELLS_MAX, first_cell_index + cells above
+ * SCN_TRACE_CELLS_MAX, a line above SCN_TRACE_LINE_SPREAD or a NaN threshold_db: SCN_E_INVALID. */
+SCN_API int scn_trace_emitters(const float *max_db, const float *min_db, const uint64_t *count, uint64_t f0_hz, uint32_t cell_hz,
+                               uint32_t cells, uint32_t first_cell_index, uint32_t line, float threshold_db, uint32_t max_gap,
+                               scn_emitter *out, uint64_t cap, uint64_t *n_emitters);
 
 /* Gives the plan a level histogram of `cells` cells of cell_hz hertz from f0_hz up and the n_edges + 1 levels of edges_db ("Level
  * histogram" above), every counter 0; every call zeroes the histogram.  cells == 0 drops it (the allocation is kept for the next

@@ -11,9 +11,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libscanner_hip.so")
-SOURCES = ["scn_kernels.hip", "scn_mixed.hip", "scn_generic.hip", "scn_big.hip", "scn_hits.hip", "scn_floor.hip", "scn_floor_local.hip", "scn_baseline.hip", "scn_history.hip", "scn_trace.hip", "scn_levels.hip", "scn_welch.hip", "scn_average.hip", "scn_gather.hip", "scn_host.hip", "scn_plan.hip", "scn_submit.hip",
-           "scn_collect.hip", "scn_history_plan.hip", "scn_trace_plan.hip", "scn_levels_plan.hip", "scn_welch_plan.hip"]
-HEADERS = ["scn_kernels.h", "scn_mask.h", "scn_wire.h", "scn_dispatch.h", "scn_host.h", "scn_slot_life.h", "scn_plan.h", "scn_resource.h", "scn_device.h", "scn_detect.h", "scn_hitlist.h", "scn_trace.h", "scn_levels.h", "scn_mixed_dft.h", "scn_mixed_plans.h", "scn_sizes.h", "scn_gather_protocol.h", "scn_gather_kernels.h", os.path.join("..", "..", "include", "scanner_hip.h")]
+SOURCES = ["scn_kernels.hip", "scn_mixed.hip", "scn_generic.hip", "scn_big.hip", "scn_hits.hip", "scn_floor.hip", "scn_floor_local.hip", "scn_baseline.hip", "scn_history.hip", "scn_trace.hip", "scn_levels.hip", "scn_emitters.hip", "scn_welch.hip", "scn_average.hip", "scn_gather.hip", "scn_host.hip", "scn_plan.hip", "scn_submit.hip",
+           "scn_collect.hip", "scn_history_plan.hip", "scn_trace_plan.hip", "scn_levels_plan.hip", "scn_emitters_plan.hip", "scn_welch_plan.hip"]
+HEADERS = ["scn_kernels.h", "scn_mask.h", "scn_wire.h", "scn_dispatch.h", "scn_host.h", "scn_slot_life.h", "scn_plan.h", "scn_resource.h", "scn_device.h", "scn_detect.h", "scn_hitlist.h", "scn_trace.h", "scn_levels.h", "scn_emitters.h", "scn_mixed_dft.h", "scn_mixed_plans.h", "scn_sizes.h", "scn_gather_protocol.h", "scn_gather_kernels.h", os.path.join("..", "..", "include", "scanner_hip.h")]
 ARCH = "gfx950"
 # The library's dynamic symbol table is the C-ABI and nothing else: everything is compiled with hidden visibility, the entry
 # points of include/scanner_hip.h carry SCN_API (default visibility while SCN_BUILDING_LIBRARY is defined), and the link takes

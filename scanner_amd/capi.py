@@ -28,6 +28,7 @@ BASELINE_SET, BASELINE_MAX = 0, 1  # scn_plan_update_baseline's op
 FLOOR_MIN = 0xFFFFFFFF  # scn_plan_desc.floor_permille: rank 0 (0 itself asks for the default, the median)
 FLOOR_TRAIN_MAX, FLOOR_GUARD_MAX = 128, 64  # the floor window's limits (scn_plan_set_floor_window)
 TRACE_CELLS_MAX = 1 << 22  # the most cells a sweep trace has (scn_plan_set_trace)
+TRACE_LINE_MAX, TRACE_LINE_MIN, TRACE_LINE_SPREAD = 0, 1, 2  # the line of a trace whose emitters are asked for (SCN_TRACE_LINE_*)
 LEVELS_EDGES_MAX, LEVELS_WORDS_MAX = 255, 1 << 24  # a level histogram's most edges, and most counters (scn_plan_set_levels)
 LEVELS_NO_RANK = 0xFFFFFFFF  # rank_level of an empty cell
 PATH_UNSUPPORTED, PATH_FUSED, PATH_FOUR_STEP, PATH_STAGED, PATH_BLUESTEIN = range(5)
@@ -43,6 +44,17 @@ assert HIT_DTYPE.itemsize == 24
 SIGNAL_DTYPE = np.dtype([("seq_id", "<u8"), ("peak_freq_hz", "<u8"), ("first_i", "<u4"), ("last_i", "<u4"), ("peak_i", "<u4"),
                          ("n_hits", "<u4"), ("peak_power_db", "<f4"), ("bandwidth_hz", "<u4")], align=True)
 assert SIGNAL_DTYPE.itemsize == 40
+
+
+class Emitter(C.Structure):
+    """struct scn_emitter"""
+    _fields_ = [("start_hz", C.c_uint64), ("stop_hz", C.c_uint64), ("peak_hz", C.c_uint64), ("count", C.c_uint64), ("first_cell", C.c_uint32),
+                ("last_cell", C.c_uint32), ("peak_cell", C.c_uint32), ("n_cells", C.c_uint32), ("peak_db", C.c_float), ("peak_other_db", C.c_float)]
+
+
+EMITTER_DTYPE = np.dtype([("start_hz", "<u8"), ("stop_hz", "<u8"), ("peak_hz", "<u8"), ("count", "<u8"), ("first_cell", "<u4"), ("last_cell", "<u4"),
+                          ("peak_cell", "<u4"), ("n_cells", "<u4"), ("peak_db", "<f4"), ("peak_other_db", "<f4")], align=True)
+assert EMITTER_DTYPE.itemsize == 56 == C.sizeof(Emitter)
 
 
 class PlanDesc(C.Structure):
@@ -132,6 +144,11 @@ SYMBOLS = {
                                           C.c_double, _vp]),
     "scn_trace_init": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
     "scn_trace_merge": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
+    "scn_plan_merge_trace": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "scn_plan_trace_emitters": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _vp, C.c_uint32,
+                                          C.POINTER(C.c_uint32)]),
+    "scn_trace_emitters": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _vp, C.c_uint64,
+                                     C.POINTER(C.c_uint64)]),
     "scn_plan_set_levels": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32]),
     "scn_plan_update_levels": (C.c_int, [_vp, C.c_int]),
     "scn_plan_get_levels": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
@@ -327,6 +344,25 @@ def trace_merge(trace, src):
     assert src_max.size == src_min.size == src_count.size == max_db.size
     check(lib().scn_trace_merge(*_trace_arrays(max_db, min_db, count), src_max.ctypes.data_as(_vp), src_min.ctypes.data_as(_vp),
                                 src_count.ctypes.data_as(_vp), max_db.size), "scn_trace_merge")
+
+
+def trace_emitters(trace, f0_hz, cell_hz, line, threshold_db, max_gap=0, first_cell=0):
+    """scn_trace_emitters: the emitters (EMITTER_DTYPE, ordered by first_cell) of the window trace = (max_db, min_db, count) of a trace
+    on the grid (f0_hz, cell_hz), whose first cell is cell first_cell of that trace -- one record per run of cells whose `line`
+    (TRACE_LINE_*) is above threshold_db, runs joined across up to max_gap off cells: what Plan.trace_emitters builds on the GPU, to
+    the bit (scanner_hip.h, "Trace emitters").  Needs no device."""
+    max_db, min_db, count = (np.ascontiguousarray(a, dt) for a, dt in zip(trace, (np.float32, np.float32, np.uint64)))
+    assert max_db.ndim == 1 and max_db.size == min_db.size == count.size
+    L, total = lib(), C.c_uint64()
+    args = (max_db.ctypes.data_as(_vp), min_db.ctypes.data_as(_vp), count.ctypes.data_as(_vp), int(f0_hz), int(cell_hz), max_db.size, int(first_cell),
+            int(line), float(threshold_db), int(max_gap))
+    st = L.scn_trace_emitters(*args, None, 0, C.byref(total))
+    if st != E_TRUNCATED:
+        check(st, "scn_trace_emitters")
+    out = np.zeros(total.value, EMITTER_DTYPE)
+    if total.value:
+        check(L.scn_trace_emitters(*args, out.ctypes.data_as(_vp), out.size, C.byref(total)), "scn_trace_emitters")
+    return out
 
 
 def _levels_hist(hist):

@@ -102,6 +102,9 @@ int check_history_range(uint32_t have, uint32_t first_row, uint32_t rows);
 // arithmetic of a fold is scn_trace.h's, the kernel's own.
 int check_trace_geometry(uint32_t cell_hz, uint32_t cells);
 int check_trace_range(uint32_t have, uint32_t first_cell, uint32_t cells);
+// The trace emitters (scanner_hip.h, "Trace emitters"): a line that exists and a threshold that is no NaN -- shared by the plan's entry
+// point (scn_emitters_plan.hip) and the host form (scn_trace_emitters).  The arithmetic is scn_emitters.h's, the kernels' own.
+int check_emitters_line(uint32_t line, float threshold_db);
 
 // The level histogram (scanner_hip.h, "Level histogram"): a geometry's limits (the trace's, the number of edges, the words of the
 // whole table), a table of edges -- no NaN, strictly increasing keys; keys: the kLevelsKeys padded keys of scn_levels.h, written

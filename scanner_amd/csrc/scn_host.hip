@@ -3,6 +3,7 @@
 // test_plan_resolve.cpp build the unit with g++ under the sanitizers); the .hip suffix only puts it through the library's compiler.
 #include "scn_host.h"
 
+#include "scn_emitters.h"
 #include "scn_levels.h"
 #include "scn_trace.h"
 #include "scn_wire.h"
@@ -357,6 +358,12 @@ int check_trace_range(uint32_t have, uint32_t first_cell, uint32_t cells) {
   return SCN_OK;
 }
 
+int check_emitters_line(uint32_t line, float threshold_db) {
+  if (line > kEmitLineSpread) return scn_fail(SCN_E_INVALID, "line %u: SCN_TRACE_LINE_MAX, _MIN or _SPREAD", line);
+  if (scn_trace_is_nan(scn_emit_bits(threshold_db))) return scn_fail(SCN_E_INVALID, "threshold_db is a NaN");
+  return SCN_OK;
+}
+
 int check_levels_geometry(uint32_t cell_hz, uint32_t cells, uint32_t n_edges) {
   if (int st = check_trace_geometry(cell_hz, cells)) return st;
   if (n_edges == 0 || n_edges > SCN_LEVELS_EDGES_MAX) return scn_fail(SCN_E_INVALID, "a level table has 1 ... %u edges: %u", SCN_LEVELS_EDGES_MAX, n_edges);
@@ -628,6 +635,58 @@ int scn_trace_merge(float *max_db, float *min_db, uint64_t *count, const float *
     trace_hold(max_db + c, min_db + c, src_max[c], src_min[c]);
     count[c] += src_count[c];
   }
+  return SCN_OK;
+}
+
+int scn_trace_emitters(const float *max_db, const float *min_db, const uint64_t *count, uint64_t f0_hz, uint32_t cell_hz, uint32_t cells,
+                       uint32_t first_cell_index, uint32_t line, float threshold_db, uint32_t max_gap, scn_emitter *out, uint64_t cap, uint64_t *n_emitters) {
+  if (!n_emitters) return scn_fail(SCN_E_INVALID, "null argument");
+  *n_emitters = 0;
+  if (!max_db || !min_db || !count || (!out && cap)) return scn_fail(SCN_E_INVALID, "null argument");
+  if (int st = check_trace_geometry(cell_hz, cells)) return st;
+  if (int st = check_trace_range(SCN_TRACE_CELLS_MAX, first_cell_index, cells)) return st;
+  if (int st = check_emitters_line(line, threshold_db)) return st;
+  const uint32_t threshold_bits = scn_emit_bits(threshold_db);
+  uint64_t total = 0, peak_key = 0;
+  scn_emitter r = {};
+  bool open = false;
+  // the open emitter's record, closed when the next one starts and behind the last cell
+  const auto close = [&]() {
+    if (!open) return;
+    const uint32_t pc = scn_emit_peak_cell(peak_key), w = pc - first_cell_index;
+    uint32_t mx, mn;
+    memcpy(&mx, max_db + w, sizeof(mx));
+    memcpy(&mn, min_db + w, sizeof(mn));
+    r.start_hz = scn_emit_hz(f0_hz, cell_hz, r.first_cell);
+    r.stop_hz = scn_emit_hz(f0_hz, cell_hz, (uint64_t)r.last_cell + 1u);
+    r.peak_hz = scn_emit_hz(f0_hz, cell_hz, pc);
+    r.peak_cell = pc;
+    r.peak_db = scn_emit_float(scn_emit_peak_bits(peak_key));
+    r.peak_other_db = scn_emit_float(scn_emit_other(line, mx, mn));
+    if (total < cap) out[total] = r;
+    total++;
+  };
+  for (uint32_t w = 0; w < cells; w++) {
+    uint32_t mx, mn;
+    memcpy(&mx, max_db + w, sizeof(mx));
+    memcpy(&mn, min_db + w, sizeof(mn));
+    const uint32_t v = scn_emit_value(line, mx, mn), c = first_cell_index + w;
+    if (!scn_emit_on(count[w], v, threshold_bits)) continue;
+    if (scn_emit_starts(open, r.last_cell, c, max_gap)) {
+      close();
+      r = scn_emitter{};
+      r.first_cell = c;
+      peak_key = 0;
+      open = true;
+    }
+    r.last_cell = c;
+    r.n_cells++;
+    r.count += count[w];
+    peak_key = std::max(peak_key, scn_emit_peak_key(v, c));
+  }
+  close();
+  *n_emitters = total;
+  if (total > cap) return scn_fail(SCN_E_TRUNCATED, "%llu emitters, the first %llu returned", (unsigned long long)total, (unsigned long long)cap);
   return SCN_OK;
 }
 

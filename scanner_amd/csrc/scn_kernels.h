@@ -207,6 +207,48 @@ struct ScnLevelsSummaryArgs {
   unsigned long long *above, *total;
 };
 hipError_t scn_launch_levels_summary(const ScnLevelsSummaryArgs &args, hipStream_t stream);
+// The trace emitters (scn_emitters.hip, scanner_hip.h "Trace emitters"): a window of the plan's trace segmented into runs of on cells,
+// one record per run.  Three launches on one stream: scn_launch_emitters_count leaves *total and the tiles' carries; the caller reads
+// *total, zeroes acc[0, total) and then has scn_launch_emitters_build gather every emitter into acc (integer atomics only) and
+// scn_launch_emitters_finish turn acc[first, first + out_cap) into records.  kEmitTile: the cells of a tile, one wave's.
+constexpr uint32_t kEmitTile = 1024;
+constexpr uint32_t kEmitTilesMax = (1u << 22) / kEmitTile;  // SCN_TRACE_CELLS_MAX's (static_assert: scn_emitters.hip)
+struct ScnEmitterAcc {         // what the build pass gathers of one emitter; all zero before it
+  unsigned long long key;      // scn_emit_peak_key of the peak (atomicMax)
+  unsigned long long count;    // sum over the on cells (atomicAdd)
+  uint32_t first_cell;         // stored by the emitter's first cell alone
+  uint32_t last_cell;          // atomicMax
+  uint32_t n_cells;            // atomicAdd
+  uint32_t reserved;
+};
+struct ScnEmittersArgs {
+  const uint32_t *max_key, *min_key;  // the plan's trace, cell 0 first (keys: scn_trace.h)
+  const unsigned long long *count;
+  uint64_t f0_hz;
+  uint32_t cell_hz;
+  uint32_t first_cell, cells;  // the window; cells >= 1, first_cell + cells <= the trace's cells
+  uint32_t line, threshold_bits, max_gap;
+  // per tile t of the window, [kEmitTilesMax] each.  The count pass: the tile's last on cell + 1 (0: none), its first on cell, its
+  // starts with its first on cell counted as one.  Its scan: the last on cell + 1 before the tile, the starts before the tile.
+  uint32_t *tile_last, *tile_first, *tile_starts, *carry_last, *carry_starts;
+  uint32_t *total;             // [1] emitters of the window
+  ScnEmitterAcc *acc;          // [acc_cap], acc_cap >= *total
+  uint32_t acc_cap;
+  void *out;                   // scn_emitter[out_cap]: records [first, first + out_cap), first + out_cap <= *total
+  uint32_t first, out_cap;
+};
+hipError_t scn_launch_emitters_count(const ScnEmittersArgs &args, hipStream_t stream);
+hipError_t scn_launch_emitters_build(const ScnEmittersArgs &args, hipStream_t stream);
+hipError_t scn_launch_emitters_finish(const ScnEmittersArgs &args, hipStream_t stream);
+// scn_trace_merge on the device: cells [first_cell, first_cell + cells) of the trace take in src (float bits and counts, no NaN)
+struct ScnTraceMergeArgs {
+  uint32_t *max_key, *min_key;  // the plan's trace, cell 0 first
+  unsigned long long *count;
+  uint32_t first_cell, cells;
+  const uint32_t *src_max, *src_min;  // [cells] float bits
+  const unsigned long long *src_count;
+};
+hipError_t scn_launch_trace_merge(const ScnTraceMergeArgs &args, hipStream_t stream);
 // sum of counts[0, n_buffers) -> *host_total (pinned host memory); acc: two zeroed device words the kernel leaves zeroed
 hipError_t scn_launch_hit_total(const uint32_t *counts, uint32_t n_buffers, uint32_t trigger_count, unsigned long long *acc, unsigned long long *host_total,
                                 uint32_t *trigger_bits, hipStream_t stream);

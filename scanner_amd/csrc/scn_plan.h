@@ -154,6 +154,13 @@ struct scn_plan : PlanShape {
   ScnDeviceMem<unsigned long long> d_trace_count;
   uint64_t trace_f0 = 0;
   uint32_t trace_cell_hz = 0, trace_cells = 0;  // cells 0: none
+  // the trace emitters (scn_emitters.hip; scn_plan_trace_emitters, scn_plan_merge_trace), each allocated at the first call that needs
+  // it and grown on demand: the tiles' five arrays and the total ([5 * kEmitTilesMax + 1]), an accumulator per emitter of the window,
+  // the page of records that goes to the host; and what a merge uploads ([2][cells] float bits, [cells] counts)
+  ScnDeviceMem<uint32_t> d_emit_tiles, d_merge_bits;
+  ScnDeviceMem<ScnEmitterAcc> d_emit_acc;
+  ScnDeviceMem<scn_emitter> d_emit_page;
+  ScnDeviceMem<unsigned long long> d_merge_count;
   // the level histogram (scn_levels.hip; scn_plan_set_levels, kept allocated when dropped): the counters [cells][n_edges + 1], the
   // table's padded keys as the fold kernel stages them (scn_levels.h), and the summary kernel's outputs, grown to the largest
   // window asked for.  Written as the trace is: by calls that return synchronised only.

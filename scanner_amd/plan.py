@@ -218,6 +218,37 @@ class Plan:
                                               count.ctypes.data_as(C.c_void_p)), "scn_plan_get_trace")
         return max_db, min_db, count
 
+    def merge_trace(self, max_db, min_db, count, first=0):
+        """scn_plan_merge_trace: the host window (max_db float32, min_db float32, count uint64) joined into cells [first, first +
+        len(max_db)) of the plan's trace, on the GPU, as capi.trace_merge joins two host traces -- the counts added, the larger
+        maximum and the smaller minimum kept.  How the root of a sharded sweep takes the ranks' traces in before it asks for the
+        band's emitters.  A NaN in max_db or min_db is refused; allowed while slots are pending."""
+        max_db, min_db, count = (np.ascontiguousarray(a, dt).reshape(-1) for a, dt in zip((max_db, min_db, count), (np.float32, np.float32, np.uint64)))
+        assert max_db.size == min_db.size == count.size
+        capi.check(self._L.scn_plan_merge_trace(self._h, int(first), max_db.size, max_db.ctypes.data_as(C.c_void_p), min_db.ctypes.data_as(C.c_void_p),
+                                                count.ctypes.data_as(C.c_void_p)), "scn_plan_merge_trace")
+
+    def trace_emitters(self, threshold_db, line=capi.TRACE_LINE_MAX, max_gap=0, first_cell=0, cells=None, first=0, cap=None):
+        """scn_plan_trace_emitters: the emitters of cells [first_cell, first_cell + cells) of the plan's trace (to its end by default),
+        segmented on the GPU (EMITTER_DTYPE array, ordered by first_cell): one record per run of cells whose `line` (capi.TRACE_LINE_*)
+        is above threshold_db, runs joined across up to max_gap off cells -- in absolute hertz, whatever units, centres and sweeps the
+        cells were folded from.  cap=None returns records [first, end) (one call for the total, one for the records); with an
+        explicit cap the C-ABI's own behaviour shows: ScannerError(E_TRUNCATED) when first + cap falls short of the total.
+        last_n_emitters holds the total."""
+        cells = max(0, self._trace_cells - int(first_cell)) if cells is None else int(cells)
+        total = C.c_uint32()
+        args = (self._h, int(first_cell), cells, int(line), float(threshold_db), int(max_gap), int(first))
+        if cap is None:
+            st = self._L.scn_plan_trace_emitters(*args, None, 0, C.byref(total))
+            if st != capi.E_TRUNCATED:
+                capi.check(st, "scn_plan_trace_emitters")
+            cap = max(0, total.value - int(first))
+        out = np.zeros(cap, capi.EMITTER_DTYPE)
+        st = self._L.scn_plan_trace_emitters(*args, out.ctypes.data_as(C.c_void_p) if cap else None, cap, C.byref(total))
+        self.last_n_emitters = total.value
+        capi.check(st, "scn_plan_trace_emitters")
+        return out[: max(0, min(cap, total.value - int(first)))]
+
     def set_levels(self, f0_hz, cell_hz, cells, edges_db):
         """scn_plan_set_levels: give the plan a level histogram of `cells` cells of cell_hz hertz from f0_hz up and the
         len(edges_db) + 1 levels the edges (float32, strictly increasing, no NaN) cut the dB axis into, every counter 0 (0 cells
