@@ -156,6 +156,16 @@ inline const SlotLifeRow *slot_life_table(size_t *count) {
       {"scn_plan_update_history", {on_device, {SlotReq::Unfolded, ""}}, SlotMove::Fold},
       {"scn_plan_get_history", {none, none}, SlotMove::None},
       {"scn_collect_confirmed", {on_device, {SlotReq::LatestFold, ""}}, SlotMove::None},
+      // (the trace and the level histogram: a fold reads the spectrum and the centres of the slot's list, and moves no slot)
+      {"scn_plan_set_trace", {none, none}, SlotMove::None},
+      {"scn_plan_update_trace", {on_device, none}, SlotMove::None},
+      {"scn_plan_get_trace", {none, none}, SlotMove::None},
+      {"scn_plan_merge_trace", {none, none}, SlotMove::None},
+      {"scn_plan_trace_emitters", {none, none}, SlotMove::None},
+      {"scn_plan_set_levels", {none, none}, SlotMove::None},
+      {"scn_plan_update_levels", {on_device, none}, SlotMove::None},
+      {"scn_plan_get_levels", {none, none}, SlotMove::None},
+      {"scn_plan_levels_summary", {none, none}, SlotMove::None},
       {"scn_collect_time_domain", {{SlotReq::Pending, ""}, none}, SlotMove::CollectTimeDomain},
       {"scn_convert_raw", {none, none}, SlotMove::None},
       {"scn_wait", {{SlotReq::Pending, ""}, none}, SlotMove::None},

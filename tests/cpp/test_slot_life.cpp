@@ -69,6 +69,15 @@ static const Expect EXPECT[] = {
     {"scn_plan_update_history", "SSooSSS"},  // a list that has not been folded yet
     {"scn_plan_get_history", "ooooooo"},
     {"scn_collect_confirmed", "SSSSSoS"},  // a list that is the history's latest fold
+    {"scn_plan_set_trace", "ooooooo"},
+    {"scn_plan_update_trace", "SSooSoo"},  // a list: its spectrum and its centres are what the fold reads (0 units: nothing to fold)
+    {"scn_plan_get_trace", "ooooooo"},
+    {"scn_plan_merge_trace", "ooooooo"},
+    {"scn_plan_trace_emitters", "ooooooo"},
+    {"scn_plan_set_levels", "ooooooo"},
+    {"scn_plan_update_levels", "SSooSoo"},
+    {"scn_plan_get_levels", "ooooooo"},
+    {"scn_plan_levels_summary", "ooooooo"},
     {"scn_collect_time_domain", "SoSSSSS"},
     {"scn_convert_raw", "ooooooo"},
     {"scn_wait", "SoSSSSS"},
@@ -94,6 +103,8 @@ static bool applies(const char *name, int k) {
   if (is("scn_collect_more") || is("scn_hits_view") || is("scn_collect_signals") || is("scn_gather_hits_device") || is("scn_gather_post") ||
       is("scn_plan_set_history") || is("scn_plan_update_history") || is("scn_plan_get_history") || is("scn_collect_confirmed"))
     return kind_hits(k);
+  // (a trace or a level histogram: a plan with hits whose submits store a spectrum -- a fixed plan with SCN_OUT_SPECTRUM beside its hits)
+  if (!std::strncmp(name, "scn_plan_", 9) && (std::strstr(name, "_trace") || std::strstr(name, "_levels"))) return kind_hits(k);
   return true;
 }
 

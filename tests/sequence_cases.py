@@ -7,11 +7,15 @@ samples (scene() makes them), and carries the status it must return: OK, or the 
 
 The generator keeps a small state of its own (pending slots, table, window, baseline rows) so that every step it draws is legal
 under include/scanner_hip.h; tests/sequence_model.py restates those rules independently and the CPU test holds the two together.
+
+The steps of the hit history, the sweep trace, the level histogram and the trace emitters (NEW_OPS) are drawn in a second pass, from
+a random stream of their own, and laid between the steps of the first: they change nothing a step of the first pass depends on, and
+strip_new(script) gives the script of the first pass back exactly (tests/test_sequence_cases_cpu.py pins its sha256 per seed).
 """
 import numpy as np
 
 from scanner_amd import capi
-from tests import detector_cases, local_floor_ref
+from tests import detector_cases, emitters_ref, local_floor_ref, trace_ref
 from tests import tolerances as tol
 
 FS = 8000000
@@ -39,7 +43,18 @@ REFUSALS = ("state_pending", "bad_nb", "rows_mismatch", "collect_idle")
 OVERFLOW_AMPLITUDE = 2.0 ** 68  # its transform's peak exceeds 2^64 under every window: the bin's power is +inf, far bins stay finite
 
 # The committed seed list: chosen by search_seeds() until tests/test_sequence_cases_cpu.py's coverage conditions hold
-SEEDS = (2414, 2240, 488, 119, 386, 237, 362, 280, 49)
+SEEDS = (2414, 2240, 488, 119, 386, 237, 362, 280, 49, 10)
+
+# the second pass: the hit history, the sweep trace, the level histogram, the trace emitters
+NEW_OPS = ("set_history", "update_history", "get_history", "confirmed", "set_trace", "update_trace", "get_trace", "merge_trace", "emitters",
+           "set_levels", "update_levels", "get_levels", "levels_summary")
+MAX_NEW_STEPS = 45  # per script
+CONFIRMS = ((1, 1), (1, 2), (2, 2), (2, 3), (3, 4), (1, 32), (32, 32))  # (m, window)
+CELL_COUNTS = (1, 37, 200, 1023, 1024, 1025, 1300)  # the emitters' kernels work a wave per 1024 cells; 1300: a run can cross the seam
+LEVEL_CELLS = (1, 8, 37, 200)
+EDGE_KINDS = ("one", "few", "many")
+GAPS = (0, 1, 7, "cells")
+LINES = (capi.TRACE_LINE_MAX, capi.TRACE_LINE_MIN, capi.TRACE_LINE_SPREAD)
 
 
 def max_units(n):
@@ -119,6 +134,39 @@ def headers(plan, step):
 
 def table_of(step):
     return step["base"] + 6e6 * ((7 * np.arange(step["count"])) % max(1, step["count"]))
+
+
+def edges_of(plan, kind):
+    """the level table of a set_levels step: one edge at the scene's noise level, a few straddling it, or all 255"""
+    q = quant(plan)[1]
+    e = [q] if kind == "one" else [q - 3.0, q - 0.5, q + 0.5, q + 3.0, q + 8.0] if kind == "few" else q - 40.0 + 60.0 * np.arange(255) / 254.0
+    return np.asarray(e, np.float32)
+
+
+def merge_window(step):
+    """the host window of a merge_trace step: emitters_ref.seeded_trace, with empty cells; nan: a NaN in max_db (even) or min_db (odd)"""
+    max_db, min_db, count = emitters_ref.seeded_trace(step["cells"], step["seed"], 0.3)
+    if step["nan"] is not None:
+        (max_db, min_db)[step["nan"] % 2][(step["nan"] // 2) % step["cells"]] = np.nan
+    return max_db, min_db, count
+
+
+def emitter_threshold(plan, step):
+    """about the scene's noise level, or about its tone level (max and min lines); a spread of a few dB"""
+    return float(np.float32(step["level"] + (0.0 if step["line"] == capi.TRACE_LINE_SPREAD else quant(plan)[1])))
+
+
+def unit_centres(plan, step, table):
+    """the centre of every unit of an accepted submit: its own, or the run of the table (a set_table step) it names"""
+    if step["indexed"]:
+        fc = table_of(table)
+        return fc[(step["first_index"] + np.arange(step["units"])) % fc.size]
+    return step["fc0"] + 6e6 * np.arange(step["units"])
+
+
+def strip_new(script):
+    """the script of the first pass: without the steps of NEW_OPS and the caller's-buffer mark of a submit"""
+    return dict(plan=script["plan"], steps=[{k: v for k, v in st.items() if k != "out"} for st in script["steps"] if st["op"] not in NEW_OPS])
 
 
 # ---- the generator ---------------------------------------------------------------------------------------------------------------
@@ -341,9 +389,440 @@ class _Gen:
         return dict(plan=self.plan, steps=self.steps)
 
 
+# ---- the second pass ---------------------------------------------------------------------------------------------------------------
+class Track:
+    """What a script's steps so far have left behind, as far as the steps of NEW_OPS depend on it: fed every step in order, it says
+    which status such a step must carry (status) and why (reason), and keeps which cells of the trace are occupied, by which slots.
+    The second pass labels its steps with it and coverage() reads its conditions from it."""
+
+    def __init__(self, plan):
+        self.plan = plan
+        self.has_hits = bool(plan["flags"] & capi.OUT_HITS)
+        self.can_trace = self.has_hits and (bool(plan["flags"] & capi.OUT_SPECTRUM) or plan["detect"] != "fixed")
+        self.pending, self.sub, self.last, self.before, self.listed = [], {}, {}, {}, set()
+        self.table = None
+        self.rows, self.epoch, self.folded, self.set_history_since = 0, 0, {}, set()
+        self.trace = self.levels = None
+        self.last_submitted = None
+        self.ev = trace_ref.evaluated(plan["n"], plan["dc_ignore_bins"], plan["use_bandwidth"])
+        self.seen = set()  # the conditions met so far (coverage's labels)
+        self.ever = set()  # the folds whose accumulator was set at some time
+
+    # -- what a step must return ------------------------------------------------------------------------------------------------------
+    def reason(self, st):
+        """None where the step is accepted, else (status, why)"""
+        op, slot = st["op"], st.get("slot")
+        history = op in ("set_history", "update_history", "get_history", "confirmed")
+        if not (self.has_hits if history else self.can_trace):
+            return capi.E_INVALID, "a hits-only fixed plan" if self.has_hits else "a plan without SCN_OUT_HITS"
+        if op in ("update_history", "update_trace", "update_levels", "confirmed"):
+            if slot in self.pending:
+                return capi.E_STATE, "a pending slot"
+            if slot not in self.last:
+                return capi.E_STATE, "a slot never collected"
+            if slot not in self.listed:
+                return capi.E_STATE, "after set_table"
+            sub = self.last[slot]
+            if op == "update_trace" and self.trace is None or op == "update_levels" and self.levels is None:
+                return capi.E_STATE, "dropped" if op in self.ever else "none set"
+            if op == "update_history":
+                if not self.rows:
+                    return capi.E_STATE, "dropped" if op in self.ever else "none set"
+                if sub["units"] > self.rows:
+                    return capi.E_INVALID, "more units than rows"
+                if sub["indexed"] and sub["units"] and self.rows not in (1, self.table["count"]):
+                    return capi.E_STATE, "indexed, rows neither 1 nor the table's count"
+                if self.folded.get(slot):
+                    return capi.E_STATE, "folded twice"
+            if op == "confirmed":
+                if not self.folded.get(slot):
+                    return capi.E_STATE, "not folded"
+                if self.folded[slot] != self.epoch or not self.rows:
+                    return capi.E_STATE, "after set_history" if slot in self.set_history_since else "after another slot's fold"
+        if op == "merge_trace":
+            if self.trace is None:
+                return capi.E_STATE, "none set"
+            if st["nan"] is not None:
+                return capi.E_INVALID, "a NaN in the window"
+        if op == "emitters" and self.trace is None:
+            return capi.E_STATE, "none set"
+        return None
+
+    def status(self, st):
+        r = self.reason(st)
+        return capi.OK if r is None else r[0]
+
+    # -- what a step leaves --------------------------------------------------------------------------------------------------------------
+    def _cells_of(self, geometry, centre):
+        f = trace_ref.bin_freqs(self.plan["n"], FS, centre)[self.ev]
+        below = f < np.uint64(geometry["f0"])
+        c = (f[~below] - np.uint64(geometry["f0"])) // np.uint64(geometry["cell_hz"])
+        inside = c < np.uint64(geometry["cells"])
+        return bool(below.any()), bool((~inside).any()), np.unique(c[inside]).astype(np.int64)
+
+    def _fold(self, st):
+        op, slot, seen = st["op"], st["slot"], self.seen
+        sub = self.last[slot]
+        k, what = self.plan["average"], op.split("_")[1]
+        seen.add(("fold", what, "overlap" if self.plan["overlap"] else "no overlap"))
+        if not sub["units"]:
+            seen.add(("fold", what, "zero units"))
+        if sub["units"] and sub["units"] < self.before.get(slot, 0):
+            seen.add(("fold", what, "smaller resubmit"))
+        if self.pending:
+            seen.add(("fold", what, "another slot pending"))
+        if slot != self.last_submitted:
+            seen.add(("fold", what, "not the last slot submitted"))
+        if sub["indexed"] and k > 1 and any(g * (k - 1) % self.table["count"] for g in range(sub["units"])):
+            seen.add(("fold", what, "averaged indexed"))
+        if sub["indexed"] and sub["units"] and sub["first_index"] % max(1, self.rows) and op == "update_history":
+            seen.add(("fold", what, "first_index"))
+        if sub.get("out"):
+            seen.add(("fold", what, "the caller's buffer"))
+        for w, _ in sub["specials"].values():
+            seen.add(("fold", what, "special", w))
+        if op == "update_history":
+            self.epoch += 1
+            self.folded[slot] = self.epoch
+            self.set_history_since.discard(slot)
+            return
+        if op == "update_levels":
+            self.levels["fed"].add((slot, sub["seed"]))
+        if op == "update_trace":
+            t = self.trace
+            t["fed"].add((slot, sub["seed"]))
+            if t["was_reset_after_a_fold"]:
+                seen.add(("trace", "a reset between folds"))
+            t["folds"] += 1
+            nan = {int(u) for u, (w, _) in sub["specials"].items() if w == "nan"}
+            centres = unit_centres(self.plan, sub, self.table)
+            for u in range(sub["units"]):
+                if u in nan:
+                    continue
+                below, above, cells = self._cells_of(t, centres[u])
+                if below:
+                    seen.add(("trace", "bins below f0"))
+                if above:
+                    seen.add(("trace", "bins above the last cell"))
+                if (t["unit"][cells] == t["folds"]).any():
+                    seen.add(("trace", "a cell of two units of one submit"))
+                t["unit"][cells] = t["folds"]
+                if ((t["slots"][cells] != 0) & (t["slots"][cells] != 1 << slot)).any():
+                    seen.add(("trace", "a cell of two slots"))
+                t["slots"][cells] |= 1 << slot
+                t["count"][cells] += 1
+        if self.trace is not None and self.levels is not None and self.trace["fed"] & self.levels["fed"] and \
+                any(self.trace[key] != self.levels[key] for key in ("f0", "cell_hz", "cells")):
+            seen.add(("geometry", "levels and trace differ, fed by one submit"))
+
+    def feed(self, st):
+        op, slot, seen = st["op"], st.get("slot"), self.seen
+        r = self.reason(st) if op in NEW_OPS else None
+        if op in NEW_OPS:
+            assert st["expect"] == (capi.OK if r is None else r[0]), (st, r)
+        if st["expect"] != capi.OK:
+            if r is not None:
+                seen.add(("refusal", op, r[1]))
+            return
+        if op in ("set_history", "set_trace", "set_levels") and st.get("rows", st.get("cells")):
+            self.ever.add("update_" + op[4:])
+        if op == "submit":
+            self.pending.append(slot)
+            if slot in self.sub or slot in self.last:
+                self.before[slot] = self.last.get(slot, {"units": 0})["units"]
+            self.sub[slot] = st
+            self.listed.discard(slot)
+            self.last_submitted = slot
+        elif op in ("collect", "counts"):
+            self.pending.remove(slot)
+            self.last[slot] = self.sub.pop(slot)
+            self.folded[slot] = 0
+            if self.has_hits:
+                self.listed.add(slot)
+        elif op == "set_table":
+            self.table = st
+            self.listed.clear()
+        elif op == "set_history":
+            self.epoch += 1
+            self.rows = st["rows"]
+            self.set_history_since |= {s for s, e in self.folded.items() if e}
+            seen.add(("set_history", "slots pending" if self.pending else "no slot pending"))
+            seen.add(("set_history", "rows", "table" if self.table and st["rows"] == self.table["count"] else "0" if not st["rows"] else "other"))
+        elif op in ("update_history", "update_trace", "update_levels"):
+            self._fold(st)
+        elif op == "confirmed":
+            if st["first"] > 1.0:
+                seen.add(("confirmed", "past the end"))
+            seen.add(("confirmed", st["m"], st["window"]))
+        elif op == "set_trace":
+            old = self.trace
+            if st["cells"]:
+                self.trace = dict(f0=st["f0"], cell_hz=st["cell_hz"], cells=st["cells"], count=np.zeros(st["cells"], np.int64), slots=np.zeros(st["cells"], np.int64),
+                                  unit=np.zeros(st["cells"], np.int64), folds=0, fed=set(), merged=False, was_reset_after_a_fold=bool(old and old["folds"]))
+                seen.add(("cells", "<64" if 1 < st["cells"] < 64 else st["cells"]))
+                if old and all(old[key] == st[key] for key in ("f0", "cell_hz", "cells")) and (old["folds"] or old["merged"]):
+                    seen.add(("set_trace", "the same geometry again"))
+            else:
+                self.trace = None
+                seen.add(("set_trace", "dropped"))
+        elif op == "set_levels":
+            old = self.levels
+            if st["cells"]:
+                self.levels = dict(f0=st["f0"], cell_hz=st["cell_hz"], cells=st["cells"], edges=st["edges"], fed=set())
+                seen.add(("edges", st["edges"]))
+                if old and all(old[key] == st[key] for key in ("f0", "cell_hz", "cells", "edges")) and old["fed"]:
+                    seen.add(("set_levels", "the same geometry again"))
+            else:
+                self.levels = None
+                seen.add(("set_levels", "dropped"))
+        elif op == "merge_trace":
+            self.trace["count"][st["first"]:st["first"] + st["cells"]] += merge_window(st)[2].astype(np.int64)
+            self.trace["merged"] = True
+        elif op in ("get_trace", "emitters"):
+            t = self.trace
+            lo, hi = st["first_cell"], st["first_cell"] + st["cells"]
+            occupied = np.flatnonzero(t["count"][lo:hi])
+            if occupied.size and occupied.size < occupied[-1] - occupied[0] + 1:
+                seen.add(("trace", "an empty cell inside, read"))
+            if op == "emitters":
+                seen.add(("line", st["line"]))
+                seen.add(("max_gap", "cells" if st["max_gap"] == t["cells"] else st["max_gap"]))
+                seen.add(("threshold", "tone" if st["level"] > 5.0 else "noise"))
+                if st["first"] > 1.0:
+                    seen.add(("emitters", "past the end"))
+                if t["merged"]:
+                    seen.add(("emitters", "after a merge"))
+                if 0 < lo or hi < t["cells"]:
+                    seen.add(("emitters", "a window of the trace"))
+                # (a run across the seam of two 1024-cell tiles, as far as the script alone can tell: cells that units were folded into on
+                # either side of it inside the window, the max line, a threshold below the noise's median, every gap bridged;
+                # tests/sequence_run.py counts the records that do cross it)
+                if lo <= 1023 and hi > 1024 and t["unit"][lo:1024].any() and t["unit"][1024:hi].any() and st["line"] == capi.TRACE_LINE_MAX and st["level"] < 0.0 \
+                        and st["max_gap"] == t["cells"]:
+                    seen.add(("emitters", "across the 1024-cell seam"))
+        if op in NEW_OPS:
+            seen.add(("op", op))
+
+
+class _Extra:
+    """the second pass over one script of the first"""
+
+    def __init__(self, plan, steps, rng):
+        self.plan, self.old, self.rng = plan, steps, rng
+        self.t = Track(plan)
+        self.out, self.n_new = [], 0
+        self.top = plan["max_batch"] // plan["average"]
+        self.want = dict(history=rng.random() < 0.75, trace=rng.random() < 0.85, levels=rng.random() < 0.7)
+        self.same_grid = rng.random() < 0.3
+        self.geometry = None
+
+    def add(self, op, **kw):
+        if self.n_new >= MAX_NEW_STEPS:
+            return -1  # (the budget is spent: not added)
+        st = dict(op=op, expect=capi.OK, **kw)
+        st["expect"] = int(self.t.status(st))
+        self.out.append(st)
+        self.t.feed(st)
+        self.n_new += 1
+        return st["expect"]
+
+    # -- what is drawn ------------------------------------------------------------------------------------------------------------------
+    def _target(self, at):
+        """the accepted submit whose centres a grid is laid over: the next one with units, else the last"""
+        table, found = self.t.table, None
+        for st in self.old[at:]:
+            if st["op"] == "set_table" and st["expect"] == capi.OK:
+                table = st
+            if st["op"] == "submit" and st["expect"] == capi.OK and st["units"]:
+                return unit_centres(self.plan, st, table)
+        for st in self.old[:at]:
+            if st["op"] == "set_table" and st["expect"] == capi.OK:
+                table = st
+            if st["op"] == "submit" and st["expect"] == capi.OK and st["units"]:
+                found = unit_centres(self.plan, st, table)
+        return np.array([100e6]) if found is None else found
+
+    def grid(self, at, counts):
+        """(f0, cell_hz, cells): the first unit's band starts below f0, and the last cell ends inside a unit's band"""
+        rng = self.rng
+        centres = np.sort(self._target(at))
+        cells = int(rng.choice(counts))
+        f0 = int(centres[0]) - int(rng.choice([1500000, 700000, 2100000]))
+        last = centres[int(rng.integers(centres.size))] if rng.random() < 0.7 else centres[min(1, centres.size - 1)]
+        end = int(last) + int(rng.choice([900000, -400000, 1700000]))
+        return f0, max(1, (end - f0) // cells), cells
+
+    def set_history(self):
+        t, rng = self.t, self.rng
+        rows = [0, 1, self.top, self.top + 2] + ([t.table["count"]] * 3 if t.table else [])
+        self.add("set_history", rows=int(rng.choice(rows)))
+
+    def set_trace(self, at, again=False):
+        t = self.t
+        if again and t.trace is not None and self.rng.random() < 0.5:
+            return self.add("set_trace", f0=t.trace["f0"], cell_hz=t.trace["cell_hz"], cells=t.trace["cells"])
+        f0, cell_hz, cells = self.grid(at, CELL_COUNTS)
+        self.geometry = (f0, cell_hz, cells)
+        return self.add("set_trace", f0=f0, cell_hz=cell_hz, cells=cells)
+
+    def set_levels(self, at, again=False):
+        t, rng = self.t, self.rng
+        if again and t.levels is not None and rng.random() < 0.5:
+            return self.add("set_levels", f0=t.levels["f0"], cell_hz=t.levels["cell_hz"], cells=t.levels["cells"], edges=t.levels["edges"])
+        edges = str(rng.choice(EDGE_KINDS))
+        if self.same_grid and t.trace is not None and t.trace["cells"] <= 200:
+            f0, cell_hz, cells = t.trace["f0"], t.trace["cell_hz"], t.trace["cells"]
+        else:
+            f0, cell_hz, cells = self.grid(at, LEVEL_CELLS)
+        return self.add("set_levels", f0=f0, cell_hz=cell_hz, cells=cells, edges=edges)
+
+    def confirmed(self, slot):
+        m, window = CONFIRMS[int(self.rng.integers(len(CONFIRMS)))]
+        self.add("confirmed", slot=slot, m=m, window=window, first=float(self.rng.choice([0.0, 0.37, 0.61, 1.1])), cap=float(self.rng.choice([0.21, 0.5, 1.0])))
+
+    def emitters(self):
+        t, rng = self.t.trace, self.rng
+        line = int(rng.choice(LINES))
+        level = float(rng.choice([2.0, 6.0, 12.0])) if line == capi.TRACE_LINE_SPREAD else float(rng.choice([-3.0, -3.0, 1.0, 6.0, 10.0]))
+        gap = rng.choice(len(GAPS))
+        first_cell, cells = 0, t["cells"]
+        if cells > 1025 and rng.random() < 0.4:  # across the seam of two tiles, every gap bridged
+            first_cell, line, level, gap = int(rng.integers(0, 1024)), capi.TRACE_LINE_MAX, -3.0, GAPS.index("cells")
+            cells -= first_cell
+        elif cells > 2 and rng.random() < 0.5:  # a window that may start or end inside a run
+            first_cell = int(rng.integers(0, cells // 2))
+            cells = int(rng.integers(1, cells - first_cell + 1))
+        self.add("emitters", line=line, level=level, max_gap=t["cells"] if GAPS[gap] == "cells" else int(GAPS[gap]), first_cell=first_cell, cells=cells,
+                 first=float(rng.choice([0.0, 0.37, 0.61, 1.1])), cap=float(rng.choice([0.21, 0.5, 1.0])))
+
+    def merge(self, nan=False):
+        t, rng = self.t.trace, self.rng
+        first = int(rng.integers(0, t["cells"]))
+        cells = int(rng.integers(1, t["cells"] - first + 1))
+        if t["cells"] >= 1025 and rng.random() < 0.6:  # over the seam of two tiles
+            first = int(rng.integers(900, 1020))
+            cells = t["cells"] - first
+        self.add("merge_trace", first=first, cells=cells, seed=int(rng.integers(1 << 30)), nan=int(rng.integers(0, 2 * cells)) if nan else None)
+
+    def reads(self, share=0.5):
+        t, rng = self.t, self.rng
+        if t.trace is not None and rng.random() < share:
+            if rng.random() < 0.5:
+                self.add("get_trace", first_cell=0, cells=t.trace["cells"])
+            else:
+                first = int(rng.integers(0, t.trace["cells"]))
+                self.add("get_trace", first_cell=first, cells=int(rng.integers(0, t.trace["cells"] - first + 1)))
+        for _ in range(int(rng.integers(0, 3)) if t.trace is not None else 0):
+            self.emitters()
+        if t.levels is not None and rng.random() < share:
+            self.add("get_levels")
+        if t.levels is not None and rng.random() < share:
+            n_edges = edges_of(self.plan, t.levels["edges"]).size
+            self.add("levels_summary", permille=int(rng.choice([0, 250, 500, 999, 1000])), level=int(rng.choice([0, n_edges // 2, n_edges])))
+        if t.has_hits and t.rows and rng.random() < share:
+            self.add("get_history")
+
+    def folds(self, slot, share=0.85):
+        """the folds of one slot, in a drawn order; a confirmation behind an accepted fold into the history"""
+        t, rng = self.t, self.rng
+        for what in rng.permutation(["history", "trace", "levels"]):
+            if not self.want[str(what)] and rng.random() < 0.9 or rng.random() > share:
+                continue
+            st = self.add("update_" + str(what), slot=slot)
+            if what == "history" and st == capi.OK:
+                for _ in range(int(rng.integers(1, 3))):
+                    self.confirmed(slot)
+                if rng.random() < 0.25:
+                    self.add("update_history", slot=slot)  # (once per submit)
+            elif what != "history" and st == capi.OK and rng.random() < 0.15:
+                self.add("update_" + str(what), slot=slot)  # (twice is allowed: it counts twice)
+
+    # -- the pass ---------------------------------------------------------------------------------------------------------------------
+    def setup(self, at):
+        t = self.t
+        if self.want["history"] and t.has_hits:
+            self.set_history()
+        if self.want["trace"] and t.can_trace:
+            self.set_trace(at)
+        if self.want["levels"] and t.can_trace:
+            self.set_levels(at)
+
+    def run(self):
+        t, rng, old = self.t, self.rng, self.old
+        late = rng.random() < 0.25  # nothing is set until the first collect: a fold before that finds none
+        if not t.has_hits:
+            self.add("set_history", rows=2)
+        if not t.can_trace:
+            self.add("set_trace", f0=99000000, cell_hz=100000, cells=64)
+            if rng.random() < 0.5:
+                self.add("set_levels", f0=99000000, cell_hz=100000, cells=8, edges="few")
+        if not late:
+            self.setup(0)
+        if t.has_hits and rng.random() < 0.3:
+            self.add(str(rng.choice(["update_history", "update_trace", "update_levels"])), slot=int(rng.integers(capi.NUM_SLOTS)))  # never collected
+        done_setup = not late
+        for at, st in enumerate(old):
+            ok = st["expect"] == capi.OK
+            if ok and st["op"] == "submit" and not st["pinned"] and st["units"] and self.plan["flags"] & capi.OUT_SPECTRUM and rng.random() < 0.4:
+                st = dict(st, out=True)  # the spectrum goes into the caller's device buffer
+            self.out.append(st)
+            t.feed(st)
+            if not ok or not t.has_hits:
+                continue
+            op, slot = st["op"], st.get("slot")
+            if op == "submit":
+                if rng.random() < 0.15:
+                    self.add(str(rng.choice(["update_history", "update_trace", "update_levels"])), slot=slot)  # a pending slot
+                if self.want["history"] and rng.random() < 0.12:
+                    self.set_history()
+                if t.can_trace and rng.random() < 0.08:
+                    self.set_trace(at, again=True)
+                if t.can_trace and rng.random() < 0.06:
+                    self.set_levels(at, again=True)
+                if t.trace is not None and rng.random() < 0.12:
+                    self.merge(nan=rng.random() < 0.3)
+                if t.listed and rng.random() < 0.2:
+                    self.folds(int(rng.choice(sorted(t.listed))), 0.6)  # with this slot pending, and not the last one submitted
+                if rng.random() < 0.15:
+                    self.reads(0.4)
+            elif op in ("collect", "counts"):
+                if not done_setup:
+                    if rng.random() < 0.7:
+                        self.add(str(rng.choice(["update_history", "update_trace", "update_levels"])), slot=slot)  # none set
+                    self.setup(at + 1)
+                    done_setup = True
+                if rng.random() < 0.8:
+                    self.folds(slot)
+                others = sorted(t.listed - {slot})
+                if others and rng.random() < 0.35:
+                    other = int(rng.choice(others))
+                    self.folds(other, 0.7)
+                    if t.folded.get(slot) and t.folded.get(other, 0) > t.folded[slot]:
+                        self.confirmed(slot)  # another slot was folded since
+                if t.folded.get(slot) == t.epoch and t.rows and rng.random() < 0.2:
+                    self.set_history()
+                    self.confirmed(slot)  # after set_history
+                if t.trace is not None and rng.random() < 0.2:
+                    self.merge(nan=rng.random() < 0.25)
+                self.reads()
+                if t.can_trace and rng.random() < 0.1:
+                    (self.set_trace if rng.random() < 0.6 else self.set_levels)(at + 1, again=True)
+                if t.can_trace and rng.random() < 0.04:
+                    self.add("set_trace", f0=0, cell_hz=0, cells=0) if rng.random() < 0.5 else self.add("set_levels", f0=0, cell_hz=0, cells=0, edges="one")
+            elif op == "set_table":
+                gone = sorted(t.last)
+                if gone and rng.random() < 0.6:
+                    self.add(str(rng.choice(["update_history", "update_trace", "update_levels"])), slot=int(rng.choice(gone)))  # the list is gone
+                if self.want["history"] and rng.random() < 0.6:
+                    self.add("set_history", rows=st["count"])
+        self.reads(0.8)
+        return dict(plan=self.plan, steps=self.out)
+
+
 def draw(seed):
     """the plan scripts of one seed"""
-    return [_Gen(np.random.default_rng([int(seed), index])).run() for index in range(SCRIPTS_PER_SEED)]
+    first = [_Gen(np.random.default_rng([int(seed), index])).run() for index in range(SCRIPTS_PER_SEED)]
+    return [_Extra(sc["plan"], sc["steps"], np.random.default_rng([int(seed), index, 1])).run() for index, sc in enumerate(first)]
 
 
 # ---- what a list of scripts covers (tests/test_sequence_cases_cpu.py's conditions; search_seeds() below) -------------------------
@@ -371,9 +850,13 @@ def coverage(scripts):
             got.add(("average", k))
         pending, units, window, table, rows = [], {}, (0, 0), 0, 0
         nan_held = False  # a max-hold of a NaN unit that no later SET or set_baseline has overwritten
+        track = Track(plan)  # (the second pass's conditions)
         learnt, submitted, nan_units = False, set(), set()  # the baseline holds finite rows; slots with something to fold; slots whose last submit has a NaN unit
         for st in steps:
             op, ok = st["op"], st["expect"] == capi.OK
+            track.feed(st)
+            if op in NEW_OPS:
+                continue
             if not ok:
                 if op == "submit":
                     got.add(("refusal", "rows_mismatch" if st["indexed"] else "bad_nb"))
@@ -451,6 +934,7 @@ def coverage(scripts):
                     nan_held = True
             elif op == "get_baseline" and nan_held:
                 got.add(("update", "MAX of a NaN unit, read back"))
+        got |= track.seen
     return got
 
 
@@ -473,12 +957,36 @@ def required():
              ("update", "not the lowest slot"), ("update", "MAX of a NaN unit, read back"), ("three slots in flight",), ("collect order differs",),
              ("small max_hits",), ("overlap", True), ("overlap", False)}
     need |= {("flags", d, f) for d in DETECTORS for f in (BOTH, capi.OUT_HITS)} | {("flags", "fixed", capi.OUT_SPECTRUM)}
+    # the second pass: the hit history, the sweep trace, the level histogram, the trace emitters
+    folds = ("update_history", "update_trace", "update_levels")
+    need |= {("op", o) for o in NEW_OPS}
+    need |= {("refusal", o, why) for o in folds for why in ("a pending slot", "a slot never collected", "after set_table", "none set")}
+    need |= {("refusal", "update_history", why) for why in ("folded twice", "more units than rows", "indexed, rows neither 1 nor the table's count")}
+    need |= {("refusal", "confirmed", why) for why in ("after another slot's fold", "after set_history")}
+    need |= {("refusal", o, "dropped") for o in folds}
+    need |= {("refusal", "set_history", "a plan without SCN_OUT_HITS"), ("refusal", "set_trace", "a plan without SCN_OUT_HITS"),
+             ("refusal", "set_trace", "a hits-only fixed plan"), ("refusal", "merge_trace", "a NaN in the window")}
+    need |= {("fold", w, c) for w in ("history", "trace", "levels")
+             for c in ("smaller resubmit", "zero units", "another slot pending", "not the last slot submitted", "averaged indexed", "overlap", "no overlap")}
+    need |= {("fold", w, "special", sp) for w in ("trace", "levels") for sp in ("nan", "overflow", "zero")}
+    need |= {("fold", "trace", "the caller's buffer"), ("fold", "levels", "the caller's buffer"), ("fold", "history", "first_index")}
+    need |= {("trace", c) for c in ("bins below f0", "bins above the last cell", "a cell of two units of one submit", "a cell of two slots", "an empty cell inside, read",
+                                    "a reset between folds")}
+    need |= {("geometry", "levels and trace differ, fed by one submit"), ("set_trace", "the same geometry again"), ("set_levels", "the same geometry again"),
+             ("set_trace", "dropped"), ("set_levels", "dropped")}
+    need |= {("set_history", c) for c in ("slots pending", "no slot pending")} | {("set_history", "rows", r) for r in ("table", "0", "other")}
+    need |= {("cells", c) for c in (1, "<64", 1023, 1024, 1025)} | {("edges", e) for e in EDGE_KINDS} | {("line", l) for l in LINES} | {("max_gap", g) for g in GAPS}
+    need |= {("threshold", "noise"), ("threshold", "tone"), ("emitters", "past the end"), ("emitters", "after a merge"), ("emitters", "a window of the trace"),
+             ("emitters", "across the 1024-cell seam"), ("confirmed", "past the end")} | {("confirmed", m, w) for m, w in CONFIRMS}
     return need
 
 
-def search_seeds(candidates=range(4000), cost=None):
-    """a greedy cover of required() by seeds (how SEEDS was chosen): repeatedly the seed that covers most of what is still missing"""
-    need, chosen = required(), []
+def search_seeds(candidates=range(4000), cost=None, start=()):
+    """a greedy cover of required() by seeds (how SEEDS was chosen): repeatedly the seed that covers most of what is still missing;
+    start: the seeds that stay, in front"""
+    need, chosen = required(), list(start)
+    for s in start:
+        need -= coverage(draw(s))
     covers = {s: coverage(draw(s)) & need for s in candidates}
     while need:
         best = max(covers, key=lambda s: (len(covers[s] & need), -s))

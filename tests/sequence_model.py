@@ -1,7 +1,8 @@
 """ModelPlan: the methods of scanner_amd.Plan that tests/sequence_cases.py's scripts use, restated in numpy from the text of
-include/scanner_hip.h and the reference modules (tests/floor_ref.py, local_floor_ref.py, baseline_ref.py, signals_ref.py).  What a
-plan does over its life -- the table, the floor window, the baseline's rows, each slot's pending and last collected submit -- is
-plain numpy state here, and every refusal carries the header's status.
+include/scanner_hip.h and the reference modules (tests/floor_ref.py, local_floor_ref.py, baseline_ref.py, signals_ref.py, history_ref.py,
+trace_ref.py, levels_ref.py, emitters_ref.py).  What a plan does over its life -- the table, the floor window, the baseline's rows, each
+slot's pending and last collected submit, the hit history with its epoch, the sweep trace and the level histogram with their
+geometries -- is plain numpy state here, and every refusal carries the header's status.
 
 The spectrum source is pluggable: every output but the spectrum is an equality on the plan's own stored spectrum, so any
 deterministic source does.  numpy_source() is the CPU's: numpy's FFT in float64 on the oracle's converted, windowed samples, rounded
@@ -11,7 +12,7 @@ The small `_...` hooks exist so that tests/test_sequence_cases_cpu.py can break 
 import numpy as np
 
 from scanner_amd import capi
-from tests import baseline_ref, floor_ref, local_floor_ref, signals_ref
+from tests import baseline_ref, emitters_ref, floor_ref, history_ref, levels_ref, local_floor_ref, signals_ref, trace_ref
 from tests.sequence_cases import FS, members
 
 
@@ -53,6 +54,10 @@ class _Slot:
         self.base = None        # (spectra, first, units) of the last accepted submit: what update_baseline folds in
         self.host = None
         self.counts = np.zeros(0, np.int64)  # hits per unit of the last accepted submit
+        self.folded = 0         # the plan's history epoch when the last collected submit was folded into the history (0: it was not)
+        self.units_before = 0   # units of the accepted submit before the last one
+        self.spec = None        # float32 [top, n]: the slot's spectrum memory -- a submit of u units writes rows [0, u), the rest stays
+        self.centres = None     # float64 [top]: the same for the centres a submit without an index stages
 
 
 class ModelPlan:
@@ -69,7 +74,13 @@ class ModelPlan:
         self.window = (0, 0)
         self.rows = None  # float32 [rows, n]
         self.slot = [_Slot() for _ in range(capi.NUM_SLOTS)]
-        self.last_n_hits = self.last_n_signals = 0
+        self.last_n_hits = self.last_n_signals = self.last_n_confirmed = self.last_n_emitters = 0
+        self.can_history = bool(self.flags & capi.OUT_HITS)
+        self.can_trace = self.can_history and (bool(self.flags & capi.OUT_SPECTRUM) or plan["detect"] != "fixed")
+        self.hist = None   # (words uint32 [rows, n] by fftshift index, visits uint32 [rows])
+        self.epoch = 0     # grows with every set_history and every accepted update_history
+        self.tr = None     # dict(f0, cell_hz, trace=(max_db, min_db, count))
+        self.lv = None     # dict(f0, cell_hz, edges, hist)
 
     def close(self):
         pass
@@ -190,7 +201,14 @@ class ModelPlan:
             fc_units = np.asarray(fc, np.float64)[first_of] if units else np.zeros(0)
         seq_units = np.asarray(first_of, np.uint64) if seq is None else np.asarray(seq, np.uint64)[first_of]
         spectra = self.spectra(raw[:nb]) if units else np.zeros((0, self.n), np.float32)
-        sub = dict(units=units, spectra=spectra, windowed=self.window != (0, 0), first=first)
+        sub = dict(units=units, spectra=spectra, windowed=self.window != (0, 0), first=first, indexed=indexed and units > 0, fc=fc_units, seq=seq_units)
+        s.units_before = (s.last or {}).get("units", 0)  # (of the slot's last collected submit: it is free, nothing is pending)
+        top = max(1, self.max_batch // k)
+        if s.spec is None:
+            s.spec, s.centres = np.full((top, self.n), np.nan, np.float32), np.zeros(top)
+        s.spec[:units] = spectra
+        if not indexed:
+            s.centres[:units] = fc_units
         if have_hits:
             sub["hits"], sub["trig"], sub["floors"], counts = self._detect(spectra, fc_units, seq_units, first)
             sub["total"] = self._total(slot, counts)
@@ -206,6 +224,7 @@ class ModelPlan:
             refuse(capi.E_STATE, "nothing submitted")
         s.last, s.pending = s.pending, None
         s.list_valid = bool(self.flags & capi.OUT_HITS)
+        s.folded = 0  # (a new collected submit: not yet part of the history)
         self.last_n_hits = s.last.get("total", 0)
         return s.last
 
@@ -311,3 +330,217 @@ class ModelPlan:
         if first_row + rows > have:
             refuse(capi.E_INVALID, "rows outside the baseline")
         return np.zeros((0, self.n), np.float32) if not rows else self.rows[first_row:first_row + rows].copy()
+
+    # -- the hit history ("Hit history") ------------------------------------------------------------------------------------------------
+    def _history_first(self, sub):
+        """the `first` of a unit's row (first + u) % rows: the submit's first_index, 0 for a submit that named its own centres"""
+        return sub["first"] if sub["indexed"] else 0
+
+    def _already_folded(self, s):
+        return s.folded != 0
+
+    def _is_latest(self, s):
+        """no other fold and no set_history since the slot's own"""
+        return s.folded != 0 and s.folded == self.epoch
+
+    def _fold_list_ok(self, s):
+        """a fold needs what a list needs: a collected submit, no submit and no set_table since"""
+        return s.pending is None and s.list_valid
+
+    def _need_history_plan(self):
+        if not self.can_history:
+            refuse(capi.E_INVALID, "no SCN_OUT_HITS")
+
+    def set_history(self, rows):
+        self._need_history_plan()
+        self.epoch += 1
+        self.hist = history_ref.new(int(rows), self.n) if rows else None
+
+    def update_history(self, slot):
+        self._need_history_plan()
+        s = self.slot[slot]
+        if not self._fold_list_ok(s):
+            refuse(capi.E_STATE, "no collected submit whose list is still on the device")
+        sub = s.last
+        if self.hist is None:
+            refuse(capi.E_STATE, "no history")
+        rows = self.hist[0].shape[0]
+        if sub["units"] > rows:
+            refuse(capi.E_INVALID, "more units than rows")
+        if sub["indexed"] and rows not in (1, self.table.size):
+            refuse(capi.E_STATE, "an indexed submit, rows neither 1 nor the table's count")
+        if self._already_folded(s):
+            refuse(capi.E_STATE, "already folded")
+        self.epoch += 1
+        s.folded = self.epoch
+        if sub["units"]:
+            self.hist = history_ref.fold(*self.hist, sub["hits"], sub["units"], self._history_first(sub), sub["seq"])
+
+    def history(self, first_row=0, rows=None):
+        self._need_history_plan()
+        have = 0 if self.hist is None else self.hist[0].shape[0]
+        rows = max(0, have - first_row) if rows is None else rows
+        if first_row + rows > have:
+            refuse(capi.E_INVALID, "rows outside the history")
+        if not rows:
+            return np.zeros((0, self.n), np.uint32), np.zeros(0, np.uint32)
+        return self.hist[0][first_row:first_row + rows].copy(), self.hist[1][first_row:first_row + rows].copy()
+
+    def confirmed_window(self, slot, m, window, first, cap):
+        """scn_collect_confirmed as the C-ABI has it: (status, records [first, first + cap), the total)"""
+        self._need_history_plan()
+        if not 1 <= m <= window <= 32:
+            refuse(capi.E_INVALID, "1 <= m <= window <= 32")
+        s = self.slot[slot]
+        if not self._fold_list_ok(s):
+            refuse(capi.E_STATE, "no collected submit whose list is still on the device")
+        if not self._is_latest(s) or self.hist is None:
+            refuse(capi.E_STATE, "not the history's latest fold")
+        sub = s.last
+        conf = history_ref.confirm(self.hist[0], sub["hits"], sub["units"], m, window, self._history_first(sub), sub["seq"]) if sub["units"] else sub["hits"][:0]
+        self.last_n_confirmed = len(conf)
+        return (capi.E_TRUNCATED if first + cap < len(conf) else capi.OK), conf[first:first + cap].copy(), len(conf)
+
+    def collect_confirmed(self, slot, m, window, first=0, cap=None):
+        st, got, total = self.confirmed_window(slot, m, window, first, 1 << 31 if cap is None else cap)
+        if st != capi.OK:
+            refuse(st, "truncated")
+        return got
+
+    # -- the sweep trace and the level histogram ("Sweep trace", "Level histogram") --------------------------------------------------------
+    def _source_slot(self, slot):
+        """the slot whose spectrum and centres a fold of `slot` reads"""
+        return slot
+
+    def _fold_count(self, s):
+        """how many units of the slot's spectrum memory a fold takes: those of its last collected submit"""
+        return s.last["units"]
+
+    def _fold_entry(self, g):
+        """the table entry, relative to first_index, whose centre unit g of an indexed submit is folded at: the GROUP's"""
+        return g
+
+    def _resets(self, old, new):
+        """every set_trace and every set_levels empties what it sets, whatever was there"""
+        return True
+
+    def _levels_grid(self):
+        return self.lv["f0"], self.lv["cell_hz"]
+
+    def _need_trace_plan(self):
+        if not self.can_trace:
+            refuse(capi.E_INVALID, "a plan that cannot have a trace")
+
+    def _fold_source(self, slot, have):
+        """the refusals of a fold, then (spectra, centres) of what it folds -- None where the submit had no units"""
+        self._need_trace_plan()
+        if not self._fold_list_ok(self.slot[slot]):
+            refuse(capi.E_STATE, "no collected submit whose list is still on the device")
+        if not have:
+            refuse(capi.E_STATE, "no trace / no level histogram")
+        s = self.slot[self._source_slot(slot)]
+        units = self._fold_count(s)
+        if not units:
+            return None
+        sub = s.last
+        if sub["indexed"]:
+            centres = np.array([self.table[(sub["first"] + self._fold_entry(g)) % self.table.size] for g in range(units)], np.float64)
+        else:
+            centres = s.centres[:units].copy()
+        return s.spec[:units].copy(), centres
+
+    def set_trace(self, f0_hz, cell_hz, cells):
+        self._need_trace_plan()
+        if cells and (cell_hz == 0 or cells > capi.TRACE_CELLS_MAX):
+            refuse(capi.E_INVALID, "the trace's limits")
+        new = (int(f0_hz), int(cell_hz), int(cells))
+        if not cells:
+            self.tr = None
+        elif self.tr is None or self._resets((self.tr["f0"], self.tr["cell_hz"], self.tr["trace"][0].size), new):
+            self.tr = dict(f0=new[0], cell_hz=new[1], trace=trace_ref.new(new[2]))
+
+    def update_trace(self, slot):
+        src = self._fold_source(slot, self.tr is not None)
+        if src is not None:
+            self.tr["trace"] = trace_ref.fold(self.tr["trace"], self.tr["f0"], self.tr["cell_hz"], src[0], FS, src[1], **self.mask)
+
+    def _trace_window(self, first, cells):
+        self._need_trace_plan()
+        have = 0 if self.tr is None else self.tr["trace"][0].size
+        cells = max(0, have - first) if cells is None else cells
+        if first + cells > have:
+            refuse(capi.E_INVALID, "cells outside the trace")
+        if not cells:
+            return trace_ref.new(0)
+        return tuple(a[first:first + cells].copy() for a in self.tr["trace"])
+
+    def trace(self, first=0, cells=None):
+        return self._trace_window(first, cells)
+
+    def _merge(self, window, first):
+        t = self.tr["trace"]
+        merged = trace_ref.merge(tuple(a[first:first + window[0].size] for a in t), window)
+        out = tuple(a.copy() for a in t)
+        for a, m in zip(out, merged):
+            a[first:first + window[0].size] = m
+        self.tr["trace"] = out
+
+    def merge_trace(self, max_db, min_db, count, first=0):
+        self._need_trace_plan()
+        window = tuple(np.ascontiguousarray(a, dt).reshape(-1) for a, dt in zip((max_db, min_db, count), (np.float32, np.float32, np.uint64)))
+        if self.tr is None:
+            refuse(capi.E_STATE, "no trace")
+        if first + window[0].size > self.tr["trace"][0].size or np.isnan(window[0]).any() or np.isnan(window[1]).any():
+            refuse(capi.E_INVALID, "a range outside the trace, or a NaN in the window")
+        if window[0].size:
+            self._merge(window, first)
+
+    def emitters_window(self, first_cell, cells, line, threshold_db, max_gap, first, cap):
+        """scn_plan_trace_emitters as the C-ABI has it: (status, records [first, first + cap), the total)"""
+        self._need_trace_plan()
+        if line > capi.TRACE_LINE_SPREAD or np.isnan(np.float32(threshold_db)):
+            refuse(capi.E_INVALID, "the line, or a NaN threshold")
+        if self.tr is None:
+            refuse(capi.E_STATE, "no trace")
+        window = self._trace_window(first_cell, cells)
+        em = emitters_ref.emitters(window, self.tr["f0"], self.tr["cell_hz"], line, threshold_db, max_gap, first_cell) if window[0].size else np.zeros(0, capi.EMITTER_DTYPE)
+        self.last_n_emitters = len(em)
+        return (capi.E_TRUNCATED if first + cap < len(em) else capi.OK), em[first:first + cap].copy(), len(em)
+
+    def trace_emitters(self, threshold_db, line=capi.TRACE_LINE_MAX, max_gap=0, first_cell=0, cells=None, first=0, cap=None):
+        st, got, total = self.emitters_window(first_cell, cells, line, threshold_db, max_gap, first, 1 << 31 if cap is None else cap)
+        if st != capi.OK:
+            refuse(st, "truncated")
+        return got
+
+    def set_levels(self, f0_hz, cell_hz, cells, edges_db):
+        self._need_trace_plan()
+        if not cells:
+            self.lv = None
+            return
+        edges = np.ascontiguousarray(edges_db, np.float32).reshape(-1)
+        if cell_hz == 0 or cells > capi.TRACE_CELLS_MAX or not levels_ref.edges_valid(edges) or cells * (edges.size + 1) > capi.LEVELS_WORDS_MAX:
+            refuse(capi.E_INVALID, "the histogram's limits, or its edges")
+        new = (int(f0_hz), int(cell_hz), int(cells), edges.tobytes())
+        if self.lv is None or self._resets((self.lv["f0"], self.lv["cell_hz"], self.lv["hist"].shape[0], self.lv["edges"].tobytes()), new):
+            self.lv = dict(f0=new[0], cell_hz=new[1], edges=edges.copy(), hist=levels_ref.new(new[2], edges.size))
+
+    def update_levels(self, slot):
+        src = self._fold_source(slot, self.lv is not None)
+        if src is not None:
+            f0, cell_hz = self._levels_grid()
+            self.lv["hist"] = levels_ref.fold(self.lv["hist"], f0, cell_hz, self.lv["edges"], src[0], FS, src[1], **self.mask)
+
+    def levels(self, first=0, cells=None):
+        self._need_trace_plan()
+        have = 0 if self.lv is None else self.lv["hist"].shape[0]
+        cells = max(0, have - first) if cells is None else cells
+        if first + cells > have:
+            refuse(capi.E_INVALID, "cells outside the histogram")
+        return np.zeros((0, 0), np.uint64) if self.lv is None else self.lv["hist"][first:first + cells].copy()
+
+    def levels_summary(self, permille=500, level=0, first=0, cells=None):
+        hist = self.levels(first, cells)
+        if permille > 1000 or level >= (hist.shape[1] if self.lv is not None else 1):
+            refuse(capi.E_INVALID, "permille above 1000, or a level the table does not have")
+        return levels_ref.summary(hist, permille, level)

@@ -2,13 +2,16 @@
 against the numpy model of tests/sequence_model.py.  What the per-feature files do not vary is what is varied here: the state one
 submit inherits from the calls before it -- the floor window's table, the frequency table, the baseline's rows and their row count,
 each slot's last spectrum, the two generations of hit regions, a smaller resubmit's counts -- over averaged and plain plans, every
-detector, every wire format, up to four slots in flight, with the refusals the header names in between.
+detector, every wire format, up to four slots in flight, with the refusals the header names in between.  Between those steps lie the
+folds, read-outs and pages of the four accumulators a plan keeps across submits -- the hit history with its confirmed lists, the sweep
+trace with its emitters, the level histogram with its summary --, each fold reading what some earlier submit of some slot left: its
+spectrum (the plan's or the caller's), its unit count, its centres or its run of the table, the history's epoch.
 
 Every comparison is an equality on the plan's own stored spectrum (NaN positions compare as NaN): no guard band, no tolerance, no
 exempt bin.  The spectrum itself is byte-identical to a twin's -- a fixed SCN_OUT_SPECTRUM-only plan with the same transform on the
 same input, which also stands in for the spectrum a hits-only plan never returns -- and once per plan it is held at the suite's
 usual bar (tolerances.compare_spectra) on ordinary units: against the oracle for K = 1, against the float64 mean power for K > 1.
-tests/test_sequence_cases_cpu.py proves on the CPU that this runner fails on eight state faults; profiles/plan_sequences.md has the
+tests/test_sequence_cases_cpu.py proves on the CPU that this runner fails on eighteen state faults; profiles/plan_sequences.md has the
 times, the counts and three mutants of the library itself."""
 import time
 
@@ -92,3 +95,5 @@ def test_every_comparison_was_an_equality(built_lib):
     assert TOTAL["scripts"] == len(cases.SEEDS) * cases.SCRIPTS_PER_SEED == TOTAL["bar_checks"]
     assert min(TOTAL[key] for key in ("steps", "refusals", "spectrum_floats", "records", "windows", "window_records", "signals", "floors",
                                       "baseline_floats", "special_units")) > 0
+    assert min(TOTAL[key] for key in ("history_words", "confirmed_records", "trace_cells", "level_counters", "emitter_records", "seam_emitters",
+                                      "caller_buffer_folds")) > 0

@@ -6,7 +6,8 @@ scn_collect_confirmed, which must be the table's for that state.
 
 The plans are as small as plans get -- 16 points, max_batch 2, max_hits 64, a threshold every evaluated bin of noise exceeds, a table
 of two entries and a history of two rows: a fixed-threshold plan, a floor plan, a baseline plan with one row, and a time-domain plan
-for scn_collect_time_domain."""
+for scn_collect_time_domain.  The floor and the baseline plan -- a hits-only fixed plan can have neither -- also get a trace of eight
+cells and a level histogram of four, on grids of their own around the two centres."""
 import ctypes as C
 import os
 
@@ -25,6 +26,9 @@ with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sl
     TABLE = {(e, s): STATUS[st] for e, s, st in (line.split() for line in _fh if line.strip())}
 FC = np.array([100e6, 106e6])
 TABLE_FC = np.array([200e6, 206e6])
+TRACE = (97000000, 1000000, 8)   # f0_hz, cell_hz, cells: the first unit's band starts below it, the second's ends above it
+LEVELS = (98000000, 2000000, 4)
+EDGES = np.array([-10.0, 0.0, 10.0], np.float32)
 
 
 class Rig:
@@ -50,6 +54,10 @@ class Rig:
         if not self.td:
             self.ok(self.L.scn_plan_set_table(self.plan, TABLE_FC.ctypes.data_as(VP), 2))
             self.ok(self.L.scn_plan_set_history(self.plan, 2))
+        if kind in ("floor", "baseline"):
+            self.ok(self.L.scn_plan_set_trace(self.plan, *TRACE))
+            self.ok(self.L.scn_plan_set_levels(self.plan, *LEVELS, EDGES.ctypes.data_as(VP), EDGES.size))
+            self.src = (np.full(2, 1.0, np.float32), np.full(2, -1.0, np.float32), np.full(2, 3, np.uint64))  # a window to merge
         if kind == "baseline":
             self.row = np.zeros(N, np.float32)
             self.ok(self.L.scn_plan_set_baseline(self.plan, 1, self.row.ctypes.data_as(VP)))
@@ -129,6 +137,18 @@ ENTRY = {
     "scn_plan_update_history": ("baseline", lambda r: r.L.scn_plan_update_history(r.plan, 0), lambda s: "folded"),
     "scn_plan_get_history": ("fixed", lambda r: r.L.scn_plan_get_history(r.plan, 0, 2, np.empty(2 * N, np.uint32).ctypes.data_as(VP), None), None),
     "scn_collect_confirmed": ("baseline", lambda r: r.L.scn_collect_confirmed(r.plan, 0, 1, 2, 0, r.hits.ctypes.data_as(VP), 64, C.byref(r.n)), None),
+    "scn_plan_set_trace": ("floor", lambda r: r.L.scn_plan_set_trace(r.plan, *TRACE), None),
+    "scn_plan_update_trace": ("floor", lambda r: r.L.scn_plan_update_trace(r.plan, 0), None),
+    "scn_plan_get_trace": ("baseline", lambda r: r.L.scn_plan_get_trace(r.plan, 1, 7, np.empty(7, np.float32).ctypes.data_as(VP), np.empty(7, np.float32).ctypes.data_as(VP),
+                                                                       np.empty(7, np.uint64).ctypes.data_as(VP)), None),
+    "scn_plan_merge_trace": ("floor", lambda r: r.L.scn_plan_merge_trace(r.plan, 3, 2, *(a.ctypes.data_as(VP) for a in r.src)), None),
+    "scn_plan_trace_emitters": ("baseline", lambda r: r.L.scn_plan_trace_emitters(r.plan, 0, 8, capi.TRACE_LINE_MAX, -200.0, 0, 0, np.empty(8, capi.EMITTER_DTYPE).ctypes.data_as(VP),
+                                                                                 8, C.byref(r.n)), None),
+    "scn_plan_set_levels": ("baseline", lambda r: r.L.scn_plan_set_levels(r.plan, *LEVELS, EDGES.ctypes.data_as(VP), EDGES.size), None),
+    "scn_plan_update_levels": ("baseline", lambda r: r.L.scn_plan_update_levels(r.plan, 0), None),
+    "scn_plan_get_levels": ("floor", lambda r: r.L.scn_plan_get_levels(r.plan, 0, 4, np.empty(16, np.uint64).ctypes.data_as(VP)), None),
+    "scn_plan_levels_summary": ("floor", lambda r: r.L.scn_plan_levels_summary(r.plan, 1, 3, 500, 2, np.empty(3, np.uint32).ctypes.data_as(VP), np.empty(3, np.uint64).ctypes.data_as(VP),
+                                                                              np.empty(3, np.uint64).ctypes.data_as(VP)), None),
     "scn_collect_time_domain": ("time_domain", lambda r: r.L.scn_collect_time_domain(r.plan, 0, None, None, None), lambda s: "no_list"),
     "scn_convert_raw": ("fixed", lambda r: r.L.scn_convert_raw(r.plan, r.x.ctypes.data_as(VP), 2, np.empty(4 * N, np.float32).ctypes.data_as(VP)), None),
     "scn_wait": ("floor", lambda r: r.L.scn_wait(r.plan, 0), None),
